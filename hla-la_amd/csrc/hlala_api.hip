@@ -28,7 +28,6 @@
 #include "kernel_exonpos.hip"
 #include "kernel_kmer.hip"
 #include "kernel_dp_band.hip"
-#include "kernel_dp_band2.hip"
 
 namespace hlala {
 size_t proj_slab_bytes_host(int stride, int maxNodesPerLevel) { return proj_slab_bytes(stride, maxNodesPerLevel); }
@@ -80,17 +79,14 @@ struct hlala_ctx {
     bool side_after_pair = false; // HLALA_SIDE_AFTER_PAIR=1: the side-stream classes are queued behind the main stream's stitch and pairing passes instead of beside them (measured: the pairing pass 20.9 -> 4.1 ms, but the next batch's projection 35.5 -> 54.8 ms beside the wide class instead; step 183.4 -> 185.5 ms)
     bool rows_all = false;        // HLALA_ROWS_ALL=1: column rows for every chain of a batch, the filters run with the projection (rounds 1-4)
     bool band_risky = false;      // HLALA_DP_BAND_RISKY=1 (tests: force fail-overs of the band kernel)
-    int band2_maxj = B2_MAXJ64;
-    int band2_grid = 0, band2_margin = 12; u64* band2_slabs = nullptr;      // the two-track band kernels (kernel_dp_band2.hip): blocks (0: HLALA_DP_BAND2=0), levels beyond the read bases left that the track run must cover (HLALA_DP_BAND2_MARGIN), back-pointer slabs
     int band_grid = 0, band_margin = 8;      // the band kernel in front of the 16-lane class (kernel_dp_band.hip): blocks (0: HLALA_DP_BAND=0) and the levels beyond the read bases left a call is taken to reach (HLALA_DP_BAND_MARGIN)
-    char* tiny_slabs = nullptr; size_t tiny_slab_bytes = 0; int tiny_grid = 0; int jf_grid = 0;      // jf_grid: blocks of the jump-free instantiation of the 16-lane class (0: not used)
+    char* tiny_slabs = nullptr; size_t tiny_slab_bytes = 0; int tiny_grid = 0; int jf_grid = 0;      // jf_grid: blocks of the jump-free instantiation of the 16-lane class
     char* ext_slabs = nullptr; size_t ext_slab_bytes = 0; char* wide_slabs = nullptr; char* mid_slabs = nullptr; char* large_slabs = nullptr; size_t large_slab_bytes = 0; char* huge_slabs = nullptr; size_t huge_slab_bytes = 0; int huge_grid = 0; int ext_grid = 0; int wide_grid = 0; int broad_grid = 0; int retry_grid = 0; int stitch_grid = 0; int mid_grid = 0; size_t mid_slab_bytes = 0;
     char* proj_slabs = nullptr; size_t proj_slab_bytes = 0; int proj_grid = 0, pair_grid = 0, pair_lean_grid = 0;
     char* rethread_slabs = nullptr; size_t rethread_slab_bytes = 0; int rethread_grid = 0;      // k_rethread_chains: back pointers of one chain per wave (short reads; HLALA_RETHREAD=0 turns the kernel off)
     double* pair_scratch = nullptr;   // [2 * pair_grid][PAIR_COMB]: combination tables of the rare pairs with more than PAIR_COMB_LDS combinations (main- and side-stream pass)
     char* proj_long_slabs = nullptr; size_t proj_long_slab_bytes = 0;      // long reads only (max_columns > 512): column / window arrays of k_project_chains<ProjLdsLong>
     void* create_scratch = nullptr; size_t create_scratch_bytes = 0; bool create_scratch_pinned = false;      // host scratch of hlala_batch_create (page-locked when the runtime grants it; one caller thread per context)
-    int proj_long_stagger = 0;              // long-read projection: wavefront w starts (w mod 64) x this many cycles after the kernel does (HLALA_PROJ_LONG_STAGGER; k_project_chains)
     int long_chunk_nodes = 1 << 20, long_max_segs = 1 << 20;      // (batch.h; the kernel clamps them to its array sizes)
     int order_cost = 0;                     // long-read layout: heaviest windows first (batch.h: order_cost; HLALA_LONG_ORDER=0: position order)
     int order_shift = 8, order_nb = 0;      // position buckets of a batch's chains (kernel_order.hip); order_nb 0: input order (HLALA_LOCALITY=0)
@@ -121,7 +117,7 @@ struct hlala_batch {
     // timing events of THIS batch (created with its first stage call): ev = start / end per stage, [7] / [6] / [10] / [8] = before the 16-lane class / after it /
     // after the 64-lane class / after the last class; evC = start / end of each DP class on the stream it ran on; evSide[0] fork point on the main stream,
     // [1] first side-stream class starts, [6] second pairing pass done
-    hipEvent_t ev[14]{}; hipEvent_t evC[7][2]{}; hipEvent_t evSide[8]{}; hipEvent_t evJF = nullptr; /* end of the jump-free instantiation of the 16-lane class */ hipEvent_t evBand[2]{}; /* the band kernel */ bool band_used = false; hipEvent_t evBand2[2]{}; bool band2_used = false; bool eventsMade = false;
+    hipEvent_t ev[14]{}; hipEvent_t evC[7][2]{}; hipEvent_t evSide[8]{}; hipEvent_t evJF = nullptr; /* end of the jump-free instantiation of the 16-lane class */ hipEvent_t evBand[2]{}; /* the band kernel */ bool band_used = false; bool eventsMade = false;
     uint32_t first_chain = 0;    // absolute index of the batch's chain 0 in the caller's numbering (hlala_batch_set_first_chain): offsets the random seeds
     float ms[3] = {0, 0, 0};
 };
@@ -161,7 +157,6 @@ static int batch_events(hlala_ctx* c, hlala_batch* b)
     for(int i = 0; i < 14; i++) HIP_TRY(c, hipEventCreate(&b->evC[i / 2][i % 2]));
     HIP_TRY(c, hipEventCreate(&b->evJF));
     for(int i = 0; i < 2; i++) HIP_TRY(c, hipEventCreate(&b->evBand[i]));
-    for(int i = 0; i < 2; i++) HIP_TRY(c, hipEventCreate(&b->evBand2[i]));
     HIP_TRY(c, hipEventCreateWithFlags(&b->evMain, hipEventDisableTiming));
     b->eventsMade = true;
     return HLALA_OK;
@@ -438,7 +433,6 @@ int hlala_create(hlala_ctx** out, int device, void* stream, const hlala_graph_de
     UPG(jf_lvl, F.djf_lvl); UPG(jb_lvl, F.djb_lvl);
     UPG(jfree_out, F.jfree_out); UPG(jfree_in, F.jfree_in);
     UPG(lin_label, F.lin_label); UPG(lin_out, F.lin_out); UPG(lin_in, F.lin_in); UPG(lin_eid, F.lin_eid);
-    UPG(trk_w_out, F.trk_w_out); UPG(trk_w_in, F.trk_w_in); UPG(trk_out, F.trk_out); UPG(trk_in, F.trk_in); UPG(trk_j_out, F.trk_j_out); UPG(trk_j_in, F.trk_j_in); UPG(trk_jp_out, F.trk_jp_out); UPG(trk_jp_in, F.trk_jp_in);
     UPG(out_prank, F.out_prank); UPG(in_prank, F.in_prank); UPG(jf_prank, F.jf_prank); UPG(jb_prank, F.jb_prank);
     { int* p_ = nullptr; rc = dev_upload(c, c->allocs, F.nrec_out.data(), F.nrec_out.size(), &p_); if(rc) return fail(rc); G.nrec_out = (const int4*)p_;
       rc = dev_upload(c, c->allocs, F.nrec_in.data(), F.nrec_in.size(), &p_); if(rc) return fail(rc); G.nrec_in = (const int4*)p_; }
@@ -475,7 +469,6 @@ int hlala_create(hlala_ctx** out, int device, void* stream, const hlala_graph_de
         return 0;
     };
     c->tiny_grid = cus * 4 * DpTiny::WAVES;
-    if(const char* e = getenv("HLALA_TINY_WAVES_PER_CU")) { const int w = atoi(e); if(w >= 1 && w <= 4 * DpTiny::WAVES) c->tiny_grid = cus * w; }      // (experiment: blocks of the 16-lane kernel per CU, tools/gpu_tiny_waves.sh)
     c->tiny_slab_bytes = dp_slab_bytes<DpTiny>();
     c->jf_grid = cus * 4 * DpTinyJF::WAVES;
     c->band_grid = cus * 20;          // a few KB of LDS per block, five waves per SIMD (96 VGPRs, nothing spilled)
@@ -484,19 +477,7 @@ int hlala_create(hlala_ctx** out, int device, void* stream, const hlala_graph_de
     if(const char* e = getenv("HLALA_ROWS_ALL")) c->rows_all = atoi(e) != 0;
     if(const char* e = getenv("HLALA_SIDE_AFTER_PAIR")) c->side_after_pair = atoi(e) != 0;
     if(const char* e = getenv("HLALA_POOL_CAP_GB")) { const long g = atol(e); if(g >= 0 && g <= 1024) c->pool_cap = (size_t)g << 30; }
-    if(const char* e = getenv("HLALA_TAIL_POOL")) { const int k = atoi(e); if(k >= 1 && k <= DP_POOL_MAX) c->tail_pool_k = k; }      // (experiments and the parity suite: hlala_set_tail_pool without touching the caller)
     if(const char* e = getenv("HLALA_DP_BAND_MARGIN")) { const int m = atoi(e); if(m >= 0 && m <= 24) c->band_margin = m; }
-    // The two-track band kernels are bit-exact and SLOWER than the hashed-frontier classes they would relieve (profiles/r06_experiments.txt 6: 1 000 vector instructions
-    // per iteration for two bands of two tracks -- the per-call cost of the hashed machine): not part of the default path.  HLALA_DP_BAND2=1 switches them on (the parity
-    // suite runs them: tests/test_gpu_align.py); the slabs are only allocated then.
-    c->band2_grid = 0;
-    if(const char* e = getenv("HLALA_DP_BAND2")) { if(atoi(e) != 0) c->band2_grid = cus * 6; }      // 19-25 KB of LDS per block (the ring of the early band's cells)
-    if(const char* e = getenv("HLALA_DP_BAND2_MAXJ")) { const int m = atoi(e); if(m >= 1 && m <= B2_MAXJ64) c->band2_maxj = m; }
-    if(const char* e = getenv("HLALA_DP_BAND2_MARGIN")) { const int m = atoi(e); if(m >= 0 && m <= 200) c->band2_margin = m; }
-    if(const char* e = getenv("HLALA_DP_BAND2_WAVES")) { const int w = atoi(e); if(w >= 1 && w <= 16 && c->band2_grid) c->band2_grid = cus * w; }
-    if(c->band2_grid) { char* p_ = nullptr; if((rc = slab_pool(&p_, (size_t)c->band2_grid * (size_t)B2_MAXD * 64 * sizeof(u64), "two-track band slabs"))) return fail(rc); c->band2_slabs = (u64*)p_; }
-    if(const char* e = getenv("HLALA_DP_BAND_WAVES")) { const int w = atoi(e); if(w >= 1 && w <= 32 && c->band_grid) c->band_grid = cus * w; }
-    if(const char* e = getenv("HLALA_DP_JF")) { if(atoi(e) == 0) c->jf_grid = 0; }      // (A/B: every call in the general instantiation -- the kernels' lists are built either way)
     if(const char* e = getenv("HLALA_DP_JF_MARGIN")) { const int m = atoi(e); if(m >= 0 && m <= 200) c->jf_margin = m; }      // (A/B: levels beyond the read bases left that a jump-free call may reach)
     c->ext_grid = cus * 20;
     c->mid_grid = cus * 16; c->mid_slab_bytes = dp_slab_bytes<DpMid>();
@@ -504,17 +485,13 @@ int hlala_create(hlala_ctx** out, int device, void* stream, const hlala_graph_de
     c->broad_grid = cus * 3;         // three DpBroad blocks per CU (48 KB of LDS each), slabs of the large layout
 
     c->wide_grid = cus * 7;          // LDS: seven DpWide blocks per CU (22 KB each); slabs of the 64-lane layout
-    if(const char* e = getenv("HLALA_DP_WIDE_BLOCKS")) { const int w = atoi(e); if(w >= 1 && w <= 7) c->wide_grid = cus * w; }      // (experiment: the class runs on the side stream since round 5 -- how much LDS it may hold beside the main stream's kernels)
     c->stitch_grid = cus * 20;        // k_stitch_chains: five waves per SIMD (92 VGPRs, nothing spilled)
-    if(const char* e = getenv("HLALA_STITCH_WAVES")) { const int w = atoi(e); if(w >= 1 && w <= 20) c->stitch_grid = cus * w; }      // (experiments: waves per CU and chains per wave and round of k_stitch_chains)
     if(const char* e = getenv("HLALA_STITCH_BY_ROW")) c->stitch_by_row = atoi(e) != 0;
-    if(const char* e = getenv("HLALA_STITCH_DRAW")) { const int d = atoi(e); if(d >= 1 && d <= 64) c->stitch_draw = d; }
     c->ext_slab_bytes = dp_slab_bytes<DpSmall>() > dp_slab_bytes<DpWide>() ? dp_slab_bytes<DpSmall>() : dp_slab_bytes<DpWide>();
     c->large_slab_bytes = dp_slab_bytes<DpLarge>() > dp_slab_bytes<DpBroad>() ? dp_slab_bytes<DpLarge>() : dp_slab_bytes<DpBroad>();       // one / three blocks per CU: a few MB each
     c->huge_grid = cus / 4 > 0 ? cus / 4 : 1;      // the in-memory backstop class: a handful of DP calls per million pairs
-    if(const char* e = getenv("HLALA_DP_HUGE_BLOCKS")) { const int v = atoi(e); if(v >= 1 && v <= 2 * cus) c->huge_grid = v; }      // (experiment: blocks of the in-memory class -- 128 calls per million pairs on 64 blocks run in two rounds)
     c->huge_slab_bytes = dp_inmemory_bytes<DpHuge>();
-    if((rc = slab_pool(&c->tiny_slabs, c->tiny_slab_bytes * (size_t)(64 / DpTiny::GW) * (size_t)(c->tiny_grid > c->jf_grid ? c->tiny_grid : c->jf_grid), "16-lane DP slabs"))) return fail(rc);
+    if((rc = slab_pool(&c->tiny_slabs, c->tiny_slab_bytes * (size_t)(64 / DpTiny::GW) * (size_t)std::max(c->tiny_grid, c->jf_grid), "16-lane DP slabs"))) return fail(rc);
     if((rc = slab_pool(&c->mid_slabs, c->mid_slab_bytes * (size_t)(64 / DpMid::GW) * (size_t)c->mid_grid, "32-lane DP slabs"))) return fail(rc);
     if((rc = slab_pool(&c->ext_slabs, c->ext_slab_bytes * (size_t)c->ext_grid, "64-lane DP slabs"))) return fail(rc);
     if((rc = slab_pool(&c->wide_slabs, c->ext_slab_bytes * (size_t)c->wide_grid, "wide-class DP slabs"))) return fail(rc);
@@ -523,14 +500,11 @@ int hlala_create(hlala_ctx** out, int device, void* stream, const hlala_graph_de
     // k_project_chains<384 columns>: 143 VGPRs = three waves per SIMD = 12 resident blocks per CU (its 11.7 KB of LDS would allow 13); the 512-column
     // layout: 173 VGPRs = two per SIMD (-Rpass-analysis=kernel-resource-usage; a cap of 128 VGPRs for a fourth wave costs 287 spilled SGPRs and wins one block)
     c->proj_grid = cus * (c->params.max_columns <= PROJ_CAP_SHORT ? 12 : 8); c->pair_grid = cus * 16; c->pair_lean_grid = cus * 24;      // k_pair_multi<., false>: four waves per SIMD (125 registers, nothing spilled); k_pair_chains (0.7 KB of LDS, 80 registers): six
-    if(const char* e = getenv("HLALA_PAIR_WAVES")) { const int w = atoi(e); if(w >= 1 && w <= 32) c->pair_grid = cus * w; }      // (experiments)
-    if(const char* e = getenv("HLALA_PROJ_WAVES")) { const int w = atoi(e); if(w >= 1 && w <= 14) c->proj_grid = cus * w; }      // (experiment: waves of the projection kernel per CU)
     { int rcp = dev_alloc(c, c->allocs, (size_t)2 * c->pair_grid * PAIR_COMB, &c->pair_scratch, false); if(rcp) return fail(rcp); }
     if(c->params.max_columns > PROJ_CAP) {       // long reads: the projection keeps its column / window arrays in HBM, fewer and bigger blocks
         c->proj_grid = cus * 20;       // (round 6: 20 waves per CU -- 95 VGPRs, five per SIMD, 6.3 KB of LDS each; round 5: 16 waves per CU -- 103 VGPRs, four per SIMD; with 4 per CU the kernel ran one wave per SIMD, waiting 72 % of its cycles: 71 k -> 82 k reads/s in batches of 10 000, 223 k in one batch of 50 000)
-        if(const char* e = getenv("HLALA_PROJ_LONG_WAVES")) { const int w = atoi(e); if(w >= 1 && w <= 20) c->proj_grid = cus * w; }      // (experiment: waves of the long-read projection per CU)
         c->proj_long_slab_bytes = proj_long_slab_bytes();
-        if(!getenv("HLALA_STITCH_DRAW")) c->stitch_draw = 1;       // rows of 16 384 columns: one chain per draw (12: 11.0 ms per 50 000 reads, 1: 8.8; a batch of 12 500: 7.9 -> 4.0 ms)
+        c->stitch_draw = 1;       // rows of 16 384 columns: one chain per draw (12: 11.0 ms per 50 000 reads, 1: 8.8; a batch of 12 500: 7.9 -> 4.0 ms)
         if(device_malloc_retry(c->device, nullptr, (void**)&c->proj_long_slabs, c->proj_long_slab_bytes * (size_t)c->proj_grid) != hipSuccess) { c->err = "hipMalloc(long-read projection slabs) failed"; return fail(HLALA_E_DEVICE); }
         c->allocs.push_back(c->proj_long_slabs);
     }
@@ -544,8 +518,7 @@ int hlala_create(hlala_ctx** out, int device, void* stream, const hlala_graph_de
             size_t ent = (size_t)c->params.max_columns * (size_t)RT_SN; if(ent < 1024) ent = 1024;
             c->rethread_slab_bytes = (ent * sizeof(ChoiceRec) + 255) & ~(size_t)255;
             if(c->rethread_slab_bytes > c->proj_slab_bytes) c->rethread_slab_bytes = c->proj_slab_bytes;
-            int wv = 24; if(const char* w = getenv("HLALA_RETHREAD_WAVES")) { const int v = atoi(w); if(v >= 1 && v <= 24) wv = v; }
-            c->rethread_grid = cus * wv;
+            c->rethread_grid = cus * 24;
             if(device_malloc_retry(c->device, nullptr, (void**)&c->rethread_slabs, c->rethread_slab_bytes * (size_t)c->rethread_grid) != hipSuccess) { c->err = "hipMalloc(re-threading slabs) failed"; return fail(HLALA_E_DEVICE); }
             c->allocs.push_back(c->rethread_slabs);
         }
@@ -553,7 +526,6 @@ int hlala_create(hlala_ctx** out, int device, void* stream, const hlala_graph_de
     // position buckets: a few hundred levels each, at most 16 384 of them (the scan is one block)
     { const char* e = getenv("HLALA_LOCALITY");
       if(!(e && atoi(e) == 0)) { int sh = 8; if(e && atoi(e) >= 2 && atoi(e) <= 20) sh = atoi(e); while((F.L >> sh) + 2 > 16384) sh++; c->order_shift = sh; c->order_nb = (F.L >> sh) + 2; } }
-    if(const char* e = getenv("HLALA_PROJ_LONG_STAGGER")) c->proj_long_stagger = atoi(e);
     if(const char* e = getenv("HLALA_LONG_CHUNK_NODES")) { const int v = atoi(e); if(v >= 1) c->long_chunk_nodes = v; }
     if(const char* e = getenv("HLALA_LONG_MAXSEGS")) { const int v = atoi(e); if(v >= 0) c->long_max_segs = v; }
     if(c->proj_long_slabs && c->order_nb > 0) { const char* e = getenv("HLALA_LONG_ORDER"); c->order_cost = (e && atoi(e) == 0) ? 0 : 1; }
@@ -563,12 +535,9 @@ int hlala_create(hlala_ctx** out, int device, void* stream, const hlala_graph_de
     if(hipEventCreateWithFlags(&c->evSideTail, hipEventDisableTiming) != hipSuccess) { c->err = "hipEventCreate failed"; return fail(HLALA_E_DEVICE); }
     { int prLow = 0, prHigh = 0; (void)hipDeviceGetStreamPriorityRange(&prLow, &prHigh);       // (numerically greatest = lowest priority)
       // the upload and the reader stream carry copies and a few small kernels (filters, position order, unpacking; export, packing) that the host WAITS for beside the
-      // persistent kernels of the alignment streams: highest priority, so that they get the first wave slots that come free (HLALA_IO_PRIORITY=normal: as before round 6)
-      int prIo = prHigh; if(const char* e = getenv("HLALA_IO_PRIORITY")) { if(!strcmp(e, "normal")) prIo = (prLow + prHigh) / 2; else if(!strcmp(e, "low")) prIo = prLow; }
-      if(hipStreamCreateWithPriority(&c->up, hipStreamNonBlocking, prIo) != hipSuccess || hipStreamCreateWithPriority(&c->rs, hipStreamNonBlocking, prIo) != hipSuccess) { c->err = "hipStreamCreate failed"; return fail(HLALA_E_DEVICE); } }
-    { int prLow = 0, prHigh = 0; (void)hipDeviceGetStreamPriorityRange(&prLow, &prHigh);       // (numerically greatest = lowest priority)
-      int pr = prLow; if(const char* e = getenv("HLALA_SIDE_PRIORITY")) { if(!strcmp(e, "high")) pr = prHigh; else if(!strcmp(e, "normal")) pr = (prLow + prHigh) / 2; }      // (tools/gpu_side_prio.sh)
-      if(hipStreamCreateWithPriority(&c->side, hipStreamNonBlocking, pr) != hipSuccess) { c->err = "hipStreamCreate failed"; return fail(HLALA_E_DEVICE); } }
+      // persistent kernels of the alignment streams: highest priority, so that they get the first wave slots that come free.  The side stream's classes: lowest
+      if(hipStreamCreateWithPriority(&c->up, hipStreamNonBlocking, prHigh) != hipSuccess || hipStreamCreateWithPriority(&c->rs, hipStreamNonBlocking, prHigh) != hipSuccess ||
+         hipStreamCreateWithPriority(&c->side, hipStreamNonBlocking, prLow) != hipSuccess) { c->err = "hipStreamCreate failed"; return fail(HLALA_E_DEVICE); } }
     if(hipStreamSynchronize(c->active) != hipSuccess) { c->err = "upload failed"; return fail(HLALA_E_DEVICE); }
     { std::lock_guard<std::mutex> g(g_ctx_mu); g_ctxs.push_back(c); }
     *out = c;
@@ -659,10 +628,8 @@ static int batch_alloc_outputs(hlala_ctx* c, hlala_batch* b)
     AL(pair_deferred, np, true); AL(pair_multi, 4 * np, false); AL(counters, 32, true); AL(work_counter, WC_N, true); AL(retry_list, 16 * nc, false);
     { DpItem* it = nullptr; rc = dev_alloc(c, b->allocs, 2 * nc, &it, false); if(rc) return rc; B.dp_items = it; }
     B.dp_nblk = (int)((nc + 255) / 256); if(B.dp_nblk < 1) B.dp_nblk = 1;
-    B.dp_jf = c->jf_grid > 0 ? c->jf_margin + 1 : 0;
+    B.dp_jf = c->jf_margin + 1;
     B.dp_band = c->band_grid > 0 ? c->band_margin + 1 : 0;
-    B.dp_band2 = c->band2_grid > 0 ? c->band2_margin + 1 : 0;
-    B.dp_band2_maxj = c->band2_maxj;
     B.dp_band_risky = c->band_risky ? 1 : 0;
     AL(dp_blk, (size_t)DPL_N * B.dp_nblk + 1, false); AL(dp_list, 2 * nc, false);
     if(!b->prepared) {
@@ -924,7 +891,6 @@ void hlala_batch_destroy(hlala_batch* b)
     for(int i = 0; i < 8; i++) if(b->evSide[i]) (void)hipEventDestroy(b->evSide[i]);
     if(b->evJF) (void)hipEventDestroy(b->evJF);
     for(int i = 0; i < 2; i++) if(b->evBand[i]) (void)hipEventDestroy(b->evBand[i]);
-    for(int i = 0; i < 2; i++) if(b->evBand2[i]) (void)hipEventDestroy(b->evBand2[i]);
     delete b;
 }
 
@@ -961,7 +927,7 @@ int hlala_project_chains(hlala_ctx* c, hlala_batch* b)
         int grid = B.n_chains < c->proj_grid ? B.n_chains : c->proj_grid;
         if(c->proj_long_slabs)
             hipLaunchKernelGGL((k_project_chains<ProjLdsLong>), dim3(grid), dim3(64), 0, c->active, c->dG, b->dB, c->d_contig_off, c->d_contig_seq, c->d_contig_level,
-                               c->proj_slabs, c->proj_slab_bytes, c->proj_long_slabs, c->proj_long_slab_bytes, c->proj_long_stagger);      // (long layout: the last argument staggers the wavefronts' starts)
+                               c->proj_slabs, c->proj_slab_bytes, c->proj_long_slabs, c->proj_long_slab_bytes, 0);
         else
             if(c->params.max_columns <= PROJ_CAP_SHORT)
                 hipLaunchKernelGGL((k_project_chains<ProjLdsShort>), dim3(grid), dim3(64), 0, c->active, c->dG, b->dB, c->d_contig_off, c->d_contig_seq, c->d_contig_level,
@@ -1047,14 +1013,12 @@ static int extend_impl(hlala_ctx* c, hlala_batch* b, bool fused, int phase)
             if(!fused && tier == DP_SIDE_TIER && c->sideTailValid) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->evSideTail, 0));
             HIP_TRY(c, hipEventRecord(b->evC[tier][0], ws));
             switch(tier) {
-            case 0:
+            case 0: {
                 // the calls that meet no gap-path jump in the instantiation without the early-cell machinery, then the others (same slabs: one after the other)
-                if(c->jf_grid > 0) {
-                    hipLaunchKernelGGL((k_dp<DpTinyJF, 0>), dim3(c->jf_grid), dim3(DpTinyJF::THREADS), 0, ws, c->dG, b->dB, items, c->tiny_slabs, c->tiny_slab_bytes, seed, c->G.nrec_out, c->G.nrec_in, B.read_bases, noPool);
-                    int rcj = check_launch(c, "k_dp<DpTinyJF>"); if(rcj) return rcj;
-                    HIP_TRY(c, hipEventRecord(b->evJF, ws));
-                }
-                hipLaunchKernelGGL((k_dp<DpTiny, 0>), dim3(c->tiny_grid), dim3(DpTiny::THREADS), 0, ws, c->dG, b->dB, items, c->tiny_slabs, c->tiny_slab_bytes, seed, c->G.nrec_out, c->G.nrec_in, B.read_bases, noPool); break;
+                hipLaunchKernelGGL((k_dp<DpTinyJF, 0>), dim3(c->jf_grid), dim3(DpTinyJF::THREADS), 0, ws, c->dG, b->dB, items, c->tiny_slabs, c->tiny_slab_bytes, seed, c->G.nrec_out, c->G.nrec_in, B.read_bases, noPool);
+                int rcj = check_launch(c, "k_dp<DpTinyJF>"); if(rcj) return rcj;
+                HIP_TRY(c, hipEventRecord(b->evJF, ws));
+                hipLaunchKernelGGL((k_dp<DpTiny, 0>), dim3(c->tiny_grid), dim3(DpTiny::THREADS), 0, ws, c->dG, b->dB, items, c->tiny_slabs, c->tiny_slab_bytes, seed, c->G.nrec_out, c->G.nrec_in, B.read_bases, noPool); break; }
             case 1: hipLaunchKernelGGL((k_dp<DpMid, 1>), dim3(c->mid_grid), dim3(DpMid::THREADS), 0, ws, c->dG, b->dB, items, c->mid_slabs, c->mid_slab_bytes, seed, c->G.nrec_out, c->G.nrec_in, B.read_bases, noPool); break;
             case 2: hipLaunchKernelGGL((k_dp<DpSmall, 2>), dim3(c->ext_grid), dim3(DpSmall::THREADS), 0, ws, c->dG, b->dB, items, c->ext_slabs, c->ext_slab_bytes, seed, c->G.nrec_out, c->G.nrec_in, B.read_bases, noPool); break;
             case 3: hipLaunchKernelGGL((k_dp<DpWide, 3>), dim3(c->wide_grid), dim3(DpWide::THREADS), 0, ws, c->dG, b->dB, items, c->wide_slabs, c->ext_slab_bytes, seed, c->G.nrec_out, c->G.nrec_in, B.read_bases, noPool); break;
@@ -1077,16 +1041,6 @@ static int extend_impl(hlala_ctx* c, hlala_batch* b, bool fused, int phase)
             hipLaunchKernelGGL((k_dp_band<64>), dim3(c->band_grid), dim3(64), 0, c->active, c->dG, b->dB, (const DpItem*)items, seed, (const uint8_t*)B.read_bases, c->G.lin_label, c->G.lin_eid);
             rc = check_launch(c, "k_dp_band"); if(rc) return rc;
             HIP_TRY(c, hipEventRecord(b->evBand[1], c->active));
-        }
-        // calls beside gap stretches next: two tracks and one gap-path jump in registers (kernel_dp_band2.hip); same fail-over list
-        b->band2_used = c->band2_grid > 0;
-        if(b->band2_used) {
-            HIP_TRY(c, hipEventRecord(b->evBand2[0], c->active));
-            hipLaunchKernelGGL((k_dp_band2<16>), dim3(c->band2_grid), dim3(64), 0, c->active, c->dG, b->dB, (const DpItem*)items, seed, (const uint8_t*)B.read_bases, c->band2_slabs);
-            hipLaunchKernelGGL((k_dp_band2<32>), dim3(c->band2_grid), dim3(64), 0, c->active, c->dG, b->dB, (const DpItem*)items, seed, (const uint8_t*)B.read_bases, c->band2_slabs);
-            hipLaunchKernelGGL((k_dp_band2<64>), dim3(c->band2_grid), dim3(64), 0, c->active, c->dG, b->dB, (const DpItem*)items, seed, (const uint8_t*)B.read_bases, c->band2_slabs);
-            rc = check_launch(c, "k_dp_band2"); if(rc) return rc;
-            HIP_TRY(c, hipEventRecord(b->evBand2[1], c->active));
         }
         HIP_TRY(c, hipEventRecord(b->ev[7], c->active));
         rc = run_class(0); if(rc) return rc;
@@ -1725,14 +1679,12 @@ int hlala_batch_get_stats(hlala_ctx* c, hlala_batch* b, hlala_batch_stats* out)
     if((b->staged & 1) && !b->B.from_seeds) (void)hipEventElapsedTime(&out->ms_project, b->ev[0], b->ev[1]);
     if(b->staged & 2) { (void)hipEventElapsedTime(&out->ms_extend, b->ev[2], b->ev[3]); if(b->B.n_chains > 0) { (void)hipEventElapsedTime(&out->ms_extend_retry, b->ev[6], b->side_used ? b->ev[10] : b->ev[8]); (void)hipEventElapsedTime(&out->ms_dp_main, b->ev[7], b->ev[6]);
           for(int k = 0; k <= DP_LAST_TIER; k++) (void)hipEventElapsedTime(&out->ms_dp_class[k], b->evC[k][0], b->evC[k][1]);
-          if(c->jf_grid > 0) (void)hipEventElapsedTime(&out->ms_dp_jump_free, b->evC[0][0], b->evJF);
+          (void)hipEventElapsedTime(&out->ms_dp_jump_free, b->evC[0][0], b->evJF);
           if(b->band_used) (void)hipEventElapsedTime(&out->ms_dp_band, b->evBand[0], b->evBand[1]);
-          if(b->band2_used) (void)hipEventElapsedTime(&out->ms_dp_band2, b->evBand2[0], b->evBand2[1]);
           if(b->side_used) (void)hipEventElapsedTime(&out->ms_side, b->evSide[1], b->evSide[6]); } }
     { int wc[WC_N]; HIP_TRY(c, hipMemcpyAsync(wc, b->B.work_counter, sizeof(wc), hipMemcpyDeviceToHost, c->active)); HIP_TRY(c, hipStreamSynchronize(c->active)); out->n_chains_retried = 0; for(int k = 1; k <= 6; k++) out->n_chains_retried += wc[12 + 4 * (k - 1)] + wc[14 + 4 * (k - 1)]; out->n_dp_retried_large = wc[28] + wc[30];
       out->n_dp_band = b->band_used ? wc[WC_BAND_CALLS] : 0; out->n_dp_band_failed = b->band_used ? wc[WC_BAND_FAILED] : 0; out->n_dp_jump_free_failed = wc[WC_JF_FAILED];
-      out->n_dp_band2 = b->band2_used ? wc[WC_B2_CALLS] : 0; out->n_dp_band2_failed = b->band2_used ? wc[WC_B2_FAILED] : 0;
-      out->n_dp_class[0] = wc[8] + wc[9] - out->n_dp_band + out->n_dp_band_failed - out->n_dp_band2 + out->n_dp_band2_failed; out->n_dp_jump_free = c->jf_grid > 0 ? wc[6] : 0; for(int k = 1; k <= 6; k++) out->n_dp_class[k] = wc[12 + 4 * (k - 1)] + wc[14 + 4 * (k - 1)]; }
+      out->n_dp_class[0] = wc[8] + wc[9] - out->n_dp_band + out->n_dp_band_failed; out->n_dp_jump_free = wc[6]; for(int k = 1; k <= 6; k++) out->n_dp_class[k] = wc[12 + 4 * (k - 1)] + wc[14 + 4 * (k - 1)]; }
     if(b->staged & 4) (void)hipEventElapsedTime(&out->ms_pair, b->ev[4], b->ev[5]);
     out->n_chains_extended = (int64_t)cnt[CNT_CHAINS_EXT]; out->n_dp_calls = (int64_t)cnt[CNT_DP_CALLS];
     out->n_dp_iterations = (int64_t)cnt[CNT_DP_ITERS]; out->n_dp_cells = (int64_t)cnt[CNT_DP_CELLS];

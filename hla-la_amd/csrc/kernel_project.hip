@@ -230,7 +230,6 @@ __global__ __launch_bounds__(64, PL::LONG ? HLALA_PROJ_LONG_WPS : HLALA_PROJ_WPS
     __shared__ PL P;
     const int lane = lane_id();
     if(PL::LONG) { if(lane == 0) proj_bind(P, longSlabs + (size_t)blockIdx.x * longSlabBytes); WSYNC(); }
-    if(PL::LONG && deferRethread > 0) { const long long tGo = clock64() + (long long)(blockIdx.x & 63) * (long long)deferRethread; while(clock64() < tGo) __builtin_amdgcn_s_sleep(64); }      // (experiment: staggered starts)
     ChoiceRec* slabCh = (ChoiceRec*)(slabs + (size_t)blockIdx.x * slabBytes);
     const int slabEnt = (int)(slabBytes / sizeof(ChoiceRec));
     const int stride = B.stride;

@@ -352,10 +352,10 @@ typedef struct {
                                      n_dp_class[0])                                                                                                                */
     int32_t n_dp_jump_free_failed;/* of n_dp_jump_free: calls that met a gap-path jump after all and were re-run in the general 16-lane instantiation                  */
     float   ms_dp_band;           /* time of the band kernel (before the 16-lane class on the main stream; not part of ms_dp_class[0])                                 */
-    int32_t n_dp_band2;           /* round 6: DP calls listed for the two-track band kernels (kernel_dp_band2.hip: one or two nodes per level within reach, at most one
-                                     gap-path jump -- the neighbourhood of a gap stretch); they do not enter the 16-lane class ...                                     */
-    int32_t n_dp_band2_failed;    /* ... except these: calls that reached the end of their track steps and were re-run in the general 16-lane instantiation            */
-    float   ms_dp_band2;          /* time of those kernels (after the band kernels, before the 16-lane class; not part of ms_dp_class[0])                              */
+    int32_t n_dp_band2;           /* always 0 (the two-track band kernels of round 6 were slower than the classes they relieved and were removed; the three fields keep
+                                     the layout)                                                                                                                    */
+    int32_t n_dp_band2_failed;    /* always 0                                                                                                                           */
+    float   ms_dp_band2;          /* always 0                                                                                                                           */
     int32_t reserved_stats;
 } hlala_batch_stats;
 int  hlala_batch_get_stats(hlala_ctx* ctx, hlala_batch* b, hlala_batch_stats* out);
