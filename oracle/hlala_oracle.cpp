@@ -4,16 +4,18 @@
  * THIS IS TEST INFRASTRUCTURE.  Only tests/, __graft_entry__.smoke() and bench.py's
  * cpu_baseline leg may load it.  The product (libhlala_gpu.so) never links or calls it.
  *
- * Pinning status (see DESIGN.md "Oracle"):  the reference cannot be compiled in this image
- * (every translation unit on the path includes Boost and BamTools headers, which are absent,
- * and stand-ins are not allowed), so there is no oracle/_ref.  The restatement is pinned on
- * the known-answer material the reference itself carries for this path -- the
+ * Pinning status (see DESIGN.md "Oracle"):  the part of the reference that the Aligner below
+ * restates -- node ranks and edge order (alignerBase), Graph::computeGapEdgePaths,
+ * extensionAligner::extendSeedChain with its frontier DP, scoreOneAlignment -- compiles from a
+ * checkout of the reference against the stand-in headers of oracle/ref/ (its sources use Boost
+ * and BamTools only in their #include lines) into oracle/_ref/libhlala_ref.so, and
+ * tests/test_reference_pin.py holds this file against it chain by chain.  The rest
+ * (processBAM.cpp: projection, pairing, mapping qualities; hla/HLATyper.cpp) does not compile
+ * that way and stays pinned only on the known-answer material the reference carries -- the
  * intervalsOverlap asserts (HLA-LA.cpp:94-102), the Phred round-trip table
  * (mapper/processBAM.cpp:4229-4239), the `--action testChainExtension` protocol
- * (HLA-LA.cpp:1733-1861: extended chain must re-spell the read) and the paranoid invariants
+ * (HLA-LA.cpp:1733-1861: extended chain must re-spell the read), the paranoid invariants
  * (verboseSeedChain.cpp:48-77, verboseSeedChain.h:282-315) -- and on glibc's own rand_r.
- * The DP cell values / tie-breaks themselves have NO golden vectors in the reference:
- * for those, parity is UNPINNED beyond the line-by-line restatement below.
  *
  * Every function cites the reference file:line it follows.  Data structures deliberately
  * keep the reference's std::map / std::set iteration orders (with node/edge creation index
@@ -313,8 +315,10 @@ struct DpStats {
     long long max_frontier = 0, max_targets = 0, max_kept_cells = 0, max_completed = 0;
     long long ovf_calls = 0, ovf_first_iter = 0, ovf_total_iter = 0;   /* calls whose frontier passes 16 cells or whose target set passes 24: the iteration where it first happens, and their iterations in all */
     long long hist_frontier[16] = {0}, hist_targets[16] = {0};   /* per DP call: bucket ceil(log2) of its widest frontier / target set (tools: capacity classes) */
+    long long tied_draws = 0, jumps_taken = 0;   /* DP calls whose end cell was drawn among several best sequence-complete cells; gap-path jumps on the returned backtraces */
     bool h4_hit = false;
     void add(const DpStats& o) {
+        tied_draws += o.tied_draws; jumps_taken += o.jumps_taken;
         cells += o.cells; iters += o.iters; calls += o.calls; edges += o.edges;
         max_frontier = std::max(max_frontier, o.max_frontier); max_targets = std::max(max_targets, o.max_targets);
         for(int i = 0; i < 16; i++) { hist_frontier[i] += o.hist_frontier[i]; hist_targets[i] += o.hist_targets[i]; }
@@ -613,6 +617,7 @@ struct Aligner {
                     }
                 } else {                                              /* gap-path jump, :1282-1307 */
                     std::vector<int> edgePath = g->paths.at(-2 - step.edge);
+                    t_stats.jumps_taken++;
                     std::vector<int> graph_levels;
                     for(int e : edgePath) graph_levels.push_back(g->node_level[g->efrom[e]]);
                     if(directionPositive) { std::reverse(graph_levels.begin(), graph_levels.end()); std::reverse(edgePath.begin(), edgePath.end()); }
@@ -655,6 +660,7 @@ struct Aligner {
             if(best.size() > 0) {
                 /* Utilities::randomNumber_nonCritical, Utilities.cpp:922-927 */
                 int selectedIndex = rand_r(rng_seed) % (int)best.size();
+                if(best.size() > 1) t_stats.tied_draws++;
                 const std::string& coordinates = best.at(selectedIndex);
                 size_t sl = coordinates.find('/');
                 int cl = atoi(coordinates.substr(0, sl).c_str()), cs = atoi(coordinates.substr(sl + 1).c_str());
@@ -1211,6 +1217,16 @@ int orc_dp_maxima(orc_handle* h, int64_t* out4, int reset)
     (void)h;
     out4[0] = t_stats.max_frontier; out4[1] = t_stats.max_targets; out4[2] = t_stats.max_kept_cells; out4[3] = t_stats.max_completed;
     if(reset) t_stats.max_frontier = t_stats.max_targets = t_stats.max_kept_cells = t_stats.max_completed = 0;
+    return 0;
+}
+
+/* of this thread so far: DP calls whose end cell was drawn among more than one best sequence-complete cell, and gap-path jumps on
+ * returned backtraces (what a comparison with the reference has to reach to mean something); reset != 0 clears them */
+int orc_dp_draws(orc_handle* h, int64_t* out2, int reset)
+{
+    (void)h;
+    out2[0] = t_stats.tied_draws; out2[1] = t_stats.jumps_taken;
+    if(reset) t_stats.tied_draws = t_stats.jumps_taken = 0;
     return 0;
 }
 

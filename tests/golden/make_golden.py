@@ -1,8 +1,9 @@
 """Regenerates tests/golden/r01_small.npz.
 
-The reference cannot be built or imported in this image (C++ needing Boost + BamTools), so these are NOT
-reference outputs: they are the oracle's outputs on a fixed small input, committed as a regression pin for the
-oracle itself and as an input/expected-output vector the GPU path is checked against on the GPU box.
+These are NOT reference outputs: they are the oracle's outputs on a fixed small input through all three stages (the
+reference's projection and pairing, processBAM.cpp, do not build here), committed as a regression pin for the oracle
+itself and as an input/expected-output vector the GPU path is checked against.  Fixtures written by the reference's own
+extension aligner are ref_*.npz (make_ref_golden.py).
 Run:  python tests/golden/make_golden.py
 """
 import os

@@ -94,6 +94,13 @@ class Oracle:
         lib().orc_dp_histogram(self.h, a.ctypes.data_as(P.c_i64p), int(reset))
         return dict(frontier=a[:16].copy(), targets=a[16:].copy())
 
+    def dp_draws(self, reset=False):
+        """Of the calling thread so far: DP calls whose end cell was drawn among more than one best sequence-complete cell; gap-path jumps on returned backtraces."""
+        a = np.zeros(2, np.int64)
+        lib().orc_dp_draws.argtypes = [C.c_void_p, P.c_i64p, C.c_int]
+        lib().orc_dp_draws(self.h, a.ctypes.data_as(P.c_i64p), int(reset))
+        return dict(tied_draws=int(a[0]), jumps_taken=int(a[1]))
+
     def graph_info(self):
         gi = P.GraphInfo()
         lib().orc_graph_info(self.h, C.byref(gi))

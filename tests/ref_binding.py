@@ -1,0 +1,124 @@
+"""ctypes binding of oracle/_ref/libhlala_ref.so: the reference's own extension aligner (oracle/ref/), the referee of the oracle.
+
+The library is built from a checkout of the reference by oracle/ref/Makefile; it is never committed.  `available()` builds it on
+demand when the reference directory is present and says why not otherwise."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+
+from conftest import load_package
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+P = load_package()
+REF_DIR = os.environ.get("HLALA_REF_DIR", "/root/reference")
+_dir = os.path.join(ROOT, "oracle", "_ref")
+_so = os.path.join(_dir, "libhlala_ref.so")
+_lib = None
+
+INT_KEYS = ("status", "n_cols", "seq_begin", "seq_end")
+COL_KEYS = ("col_level", "col_edge", "col_gchar", "col_schar", "col_fromseed")
+
+
+def have_reference():
+    return os.path.exists(os.path.join(REF_DIR, "mapper", "aligner", "extensionAligner.cpp"))
+
+
+def available():
+    """(True, "") when the library can be loaded (built now if the reference is here), else (False, reason)."""
+    if have_reference():
+        subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle", "ref"), "HLALA_REF_DIR=" + REF_DIR])
+    if os.path.exists(_so):
+        return True, ""
+    return False, "no oracle/_ref/libhlala_ref.so and no reference sources at %s to build it from (oracle/ref/Makefile)" % REF_DIR
+
+
+def sources_hash():
+    """Hash over the reference sources the library was compiled from (written by oracle/ref/Makefile)."""
+    with open(os.path.join(_dir, "ref_sources.sha256")) as f:
+        return f.read().strip()
+
+
+def lib():
+    global _lib
+    if _lib is None:
+        _lib = C.CDLL(_so)
+        vp = C.c_void_p
+        _lib.ref_create.argtypes = [C.POINTER(P.GraphDesc)]
+        _lib.ref_create.restype = vp
+        _lib.ref_destroy.argtypes = [vp]
+        _lib.ref_last_error.restype = C.c_char_p
+        _lib.ref_graph_n_paths.argtypes = [vp]
+        _lib.ref_graph_paths.argtypes = [vp, P.c_i32p, P.c_i32p, P.c_i32p]
+        _lib.ref_extend_seeds.argtypes = [vp, C.POINTER(P.SeedsIn), C.POINTER(P.ChainsOut), C.c_uint32, C.c_int, C.c_int, C.c_int]
+    return _lib
+
+
+class ReferenceError_(RuntimeError):
+    pass
+
+
+class Reference:
+    """Graph + mapper::aligner::extensionAligner of the reference over a graph description dict."""
+
+    def __init__(self, graph, rng_seed=12345, long_read_mode=0, max_columns=384):
+        self.rng_seed, self.long_read_mode, self.max_columns = rng_seed, long_read_mode, max_columns
+        g, self._kg = P.fill_struct(P.GraphDesc, graph)
+        self.h = lib().ref_create(C.byref(g))
+        if not self.h:
+            raise ReferenceError_(lib().ref_last_error().decode())
+
+    def _check(self, rc):
+        if rc != 0:
+            raise ReferenceError_(lib().ref_last_error().decode())
+
+    def graph_paths(self):
+        """Graph::completedGapEdgePaths as (first node, last node, length) arrays."""
+        n = lib().ref_graph_n_paths(self.h)
+        a = [np.zeros(n, np.int32) for _ in range(3)]
+        self._check(lib().ref_graph_paths(self.h, *[x.ctypes.data_as(P.c_i32p) for x in a]))
+        return a
+
+    def extend_seeds(self, seeds_in, mode=0):
+        """extendSeedChain + scoreOneAlignment per chain.  mode 0: the oracle's and the product's seed discipline (two reference calls for a chain
+        clipped at both ends); mode 1: one call per chain.  dp_iters / dp_score / removed_cols stay zero: the reference does not report them."""
+        s, keep = P.fill_struct(P.SeedsIn, seeds_in)
+        o, d = P.alloc_chains_out(seeds_in["n_chains"], self.max_columns)
+        self._check(lib().ref_extend_seeds(self.h, C.byref(s), C.byref(o), self.rng_seed & 0xFFFFFFFF, self.long_read_mode, self.max_columns, mode))
+        return d
+
+    def close(self):
+        if self.h:
+            lib().ref_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def chain_diffs(got, exp, n_chains, upto=None):
+    """Per chain, the names of the integer / byte outputs in which `got` and `exp` differ (all chains, none left out).  upto[c] limits
+    the column comparison of chain c to its first upto[c] columns (and leaves n_cols / seq_end out)."""
+    st = exp["_stride"]
+    assert got["_stride"] == st
+    out = {}
+    for c in range(n_chains):
+        bad = []
+        for k in INT_KEYS:
+            if upto is not None and k in ("n_cols", "seq_end"):
+                continue
+            if got[k][c] != exp[k][c]:
+                bad.append(k)
+        n = int(exp["n_cols"][c]) if upto is None else int(upto[c])
+        if upto is not None and (got["n_cols"][c] < n or exp["n_cols"][c] < n):
+            bad.append("n_cols")
+        for k in COL_KEYS:
+            if not np.array_equal(got[k][c * st:c * st + n], exp[k][c * st:c * st + n]):
+                bad.append(k)
+        if bad:
+            out[c] = bad
+    return out

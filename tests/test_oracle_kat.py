@@ -1,6 +1,8 @@
 """CPU: pin the oracle on the known-answer material the reference itself carries for this path, plus hand-derived cases.
 
-The reference cannot be built in this image (Boost/BamTools absent), so these are the reference-held checks that exist:
+The reference's extension aligner is built locally and faces the oracle chain by chain in tests/test_reference_pin.py (which also runs the
+hand-derived DP cases below through the reference itself).  For what does not compile that way (HLA-LA.cpp, processBAM.cpp) these are the
+reference-held checks that exist:
   * Utilities::intervalsOverlap start-up asserts          HLA-LA.cpp:94-102
   * Phred round-trip table of assignMappingQualities       mapper/processBAM.cpp:4216-4239
   * glibc rand_r as used by randomNumber_nonCritical        Utilities.cpp:922-927
