@@ -1,4 +1,5 @@
-"""ctypes binding of oracle/_ref/libhlala_ref.so: the reference's own extension aligner (oracle/ref/), the referee of the oracle.
+"""ctypes binding of oracle/_ref/libhlala_ref.so: the reference's own extension aligner and the static members of its processBAM around it
+(projection, pairing, mapping qualities; oracle/ref/), the referee of the oracle.
 
 The library is built from a checkout of the reference by oracle/ref/Makefile; it is never committed.  `available()` builds it on
 demand when the reference directory is present and says why not otherwise."""
@@ -34,10 +35,18 @@ def available():
     return False, "no oracle/_ref/libhlala_ref.so and no reference sources at %s to build it from (oracle/ref/Makefile)" % REF_DIR
 
 
-def sources_hash():
-    """Hash over the reference sources the library was compiled from (written by oracle/ref/Makefile)."""
-    with open(os.path.join(_dir, "ref_sources.sha256")) as f:
+def sources_hash(pipeline=False):
+    """Hash over the reference sources the library was compiled from (written by oracle/ref/Makefile): over the aligner's sources, which
+    wrote the ref_*.npz fixtures of the extension stage, or (pipeline=True) over those plus processBAM.cpp and what its link needs."""
+    with open(os.path.join(_dir, "ref_sources_pipeline.sha256" if pipeline else "ref_sources.sha256")) as f:
         return f.read().strip()
+
+
+PROJ_OK, PROJ_REFUSED, PROJ_NOT_KEPT = 0, 1, -100       # status of Reference.project_chains (the last one is this binding's filler)
+STAGE_KEYS = ("n_cols", "seq_begin", "seq_end", "col_level", "col_gchar", "col_schar")
+
+
+from ref_pipeline import gap_stretch_rule          # noqa: E402,F401  (the NumPy statement of the inGraphGapStretch rule: an input of project_chains)
 
 
 def lib():
@@ -52,6 +61,9 @@ def lib():
         _lib.ref_graph_n_paths.argtypes = [vp]
         _lib.ref_graph_paths.argtypes = [vp, P.c_i32p, P.c_i32p, P.c_i32p]
         _lib.ref_extend_seeds.argtypes = [vp, C.POINTER(P.SeedsIn), C.POINTER(P.ChainsOut), C.c_uint32, C.c_int, C.c_int, C.c_int]
+        _lib.ref_project_chains.argtypes = [vp, C.POINTER(P.ContigsDesc), C.POINTER(P.BatchIn), C.c_int, P.c_u8p, P.c_u8p, C.c_int, C.POINTER(P.ChainsOut), C.POINTER(P.ChainsOut)]
+        _lib.ref_pair_chains.argtypes = [vp, C.POINTER(P.ContigsDesc), C.POINTER(P.Params), C.POINTER(P.SeedsIn), P.c_i32p, C.c_int, C.POINTER(P.ChainsOut), C.POINTER(P.PairsOut), P.c_u8p]
+        _lib.ref_mapq_unpaired.argtypes = [vp, C.POINTER(P.SeedsIn), P.c_f64p, C.c_int, C.c_int, C.POINTER(P.PairsOut)]
     return _lib
 
 
@@ -87,6 +99,49 @@ class Reference:
         o, d = P.alloc_chains_out(seeds_in["n_chains"], self.max_columns)
         self._check(lib().ref_extend_seeds(self.h, C.byref(s), C.byref(o), self.rng_seed & 0xFFFFFFFF, self.long_read_mode, self.max_columns, mode))
         return d
+
+    def project_chains(self, contigs, batch_in, keep, gap_stretch, unpaired=False, stages=False):
+        """processBAM::alignment2Chain on every chain with keep != 0 (transformBAMreadToInternalAlignment, checkAlignmentConcordanceWithSequence,
+        PRGContigAlignment2Seed).  status: PROJ_OK / PROJ_REFUSED (transform returned false) / PROJ_NOT_KEPT.  With stages=True also returns the three
+        intermediate alignments (after transform, after cleanInitialAlignment, after restrictInitialAlignmentToNoGapAreas) as a list of dicts."""
+        c, kc = P.fill_struct(P.ContigsDesc, contigs)
+        b, kb = P.fill_struct(P.BatchIn, batch_in)
+        n = int(batch_in["n_chains"])
+        keep = np.ascontiguousarray(keep, np.uint8); gap = np.ascontiguousarray(gap_stretch, np.uint8)
+        assert len(keep) == n
+        o, d = P.alloc_chains_out(n, self.max_columns)
+        d["status"][:] = PROJ_NOT_KEPT
+        st, sd = None, None
+        if stages:
+            st = (P.ChainsOut * 3)(); sd = []
+            for i in range(3):
+                x, dd = P.alloc_chains_out(n, self.max_columns)
+                st[i] = x; sd.append(dd)
+        n_reads = int(batch_in["n_pairs"]) * (1 if unpaired else 2)
+        self._check(lib().ref_project_chains(self.h, C.byref(c), C.byref(b), n_reads, keep.ctypes.data_as(P.c_u8p), gap.ctypes.data_as(P.c_u8p), self.max_columns, C.byref(o), st))
+        return (d, sd) if stages else d
+
+    def pair_chains(self, contigs, seeds_in, chain_abs, n_pairs, insert_mean, insert_sd):
+        """The kept seed chains extended and scored (ref_extend_seeds mode 0 with the seeds rng_seed + 2 * chain_abs[c] + d), then the pairing loop, the
+        selection and assignMappingQualities of processBAM::alignOneReadPair.  Returns (pairs, extended chains, best_is_penalty)."""
+        c, kc = P.fill_struct(P.ContigsDesc, contigs)
+        s, ks = P.fill_struct(P.SeedsIn, seeds_in)
+        prm = P.Params(insert_mean, insert_sd, self.rng_seed & 0xFFFFFFFF, self.long_read_mode, self.max_columns, 0)
+        ca = np.ascontiguousarray(chain_abs, np.int32)
+        eo, ed = P.alloc_chains_out(seeds_in["n_chains"], self.max_columns)
+        po, pd = P.alloc_pairs_out(n_pairs, self.max_columns)
+        pen = np.zeros(n_pairs, np.uint8)
+        self._check(lib().ref_pair_chains(self.h, C.byref(c), C.byref(prm), C.byref(s), ca.ctypes.data_as(P.c_i32p), n_pairs, C.byref(eo), C.byref(po), pen.ctypes.data_as(P.c_u8p)))
+        return pd, ed, pen
+
+    def mapq_unpaired(self, chains_in, ll, n_reads):
+        """Utilities::findVectorMax + assignMappingQualities_unpaired per read over finished chains (hlala_seeds_in layout, grouped by read) and their
+        log-likelihoods.  Per-read outputs in the layout of hlala_pairs_out; best_chain indexes `chains_in`."""
+        s, ks = P.fill_struct(P.SeedsIn, chains_in)
+        ll = np.ascontiguousarray(ll, np.float64)
+        po, pd = P.alloc_pairs_out(n_reads, self.max_columns)         # (allocates 2n rows; the first n are used)
+        self._check(lib().ref_mapq_unpaired(self.h, C.byref(s), ll.ctypes.data_as(P.c_f64p), n_reads, self.max_columns, C.byref(po)))
+        return pd
 
     def close(self):
         if self.h:
