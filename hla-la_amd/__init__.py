@@ -304,6 +304,13 @@ class SeedBatch:
         self.lib.hlala_seed_batch_timing(self.h, s.ctypes.data_as(c_f64p), t.ctypes.data_as(c_i32p))
         return dict(zip(("index", "inflate", "parse", "group", "name_sort", "layout"), [float(x) for x in s]), threads=int(t[0]))
 
+    def inflate_counts(self):
+        """(blocks inflated on the GPU, blocks the GPU rejected and the host engine ran again, blocks inflated on the host only)"""
+        cnt = (C.c_int64 * 3)()
+        self.lib.hlala_seed_batch_inflate_counts.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        self.lib.hlala_seed_batch_inflate_counts(self.h, cnt)
+        return int(cnt[0]), int(cnt[1]), int(cnt[2])
+
     def pin(self, on=True):
         self.lib.hlala_seed_batch_pin.argtypes = [C.c_void_p, C.c_int]
         return self.lib.hlala_seed_batch_pin(self.h, 1 if on else 0) == 0
@@ -333,6 +340,79 @@ def bam_open_seeds(lib, path, intervals, long_read_mode=False, threads=0, flags=
     if lib.hlala_bam_extract_seeds_opt(str(path).encode(), len(intervals), arr, int(bool(long_read_mode)), int(threads), int(flags), C.byref(h)) != 0:
         raise HlalaError(lib.hlala_bam_last_error().decode(errors="replace"))
     return SeedBatch(lib, h, long_read_mode)
+
+
+class BgzfBlock(C.Structure):
+    _fields_ = [("coff", C.c_uint64), ("clen", C.c_uint32), ("isize", C.c_uint32), ("uoff", C.c_uint64)]
+
+
+class InflateStats(C.Structure):
+    _fields_ = [("n_blocks", C.c_int64), ("n_ok", C.c_int64), ("n_rejected", C.c_int64), ("ms_h2d", C.c_double), ("ms_kernel", C.c_double), ("ms_d2h", C.c_double), ("ms_wall", C.c_double)]
+
+
+INFLATE_MIN_CHUNK, INFLATE_DEFAULT_CHUNK = 1 << 17, 32 << 20          # HLALA_INFLATE_MIN_CHUNK, HLALA_INFLATE_DEFAULT_CHUNK
+INFLATE_STATUS = ("ok", "reserved block type", "stored LEN != ~NLEN", "bad code lengths", "invalid symbol", "distance too far", "input exhausted", "output size")
+
+
+class Inflater:
+    """hlala_inflater: BGZF blocks (raw DEFLATE streams) inflated on the GPU, one wavefront per block.  Its own light handle: no graph, no Context."""
+
+    def __init__(self, lib=None, device=0, chunk_bytes=0):
+        self.lib = lib or load_library(); self.h = None
+        lib = self.lib
+        lib.hlala_inflater_create.argtypes = [C.c_int32, C.c_size_t, C.POINTER(C.c_void_p)]
+        lib.hlala_inflater_destroy.argtypes = [C.c_void_p]; lib.hlala_inflater_destroy.restype = None
+        lib.hlala_inflater_last_error.argtypes = [C.c_void_p]; lib.hlala_inflater_last_error.restype = C.c_char_p
+        lib.hlala_bgzf_inflate.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(BgzfBlock), C.c_int64, C.c_void_p, C.c_size_t, c_i32p, C.POINTER(InflateStats)]
+        lib.hlala_bam_extract_seeds_gpu.argtypes = [C.c_void_p, C.c_char_p, C.c_int32, C.POINTER(BamInterval), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
+        h = C.c_void_p()
+        rc = lib.hlala_inflater_create(int(device), int(chunk_bytes), C.byref(h))
+        if rc != 0:
+            raise HlalaError(f"hlala_inflater_create failed ({rc}): {lib.hlala_inflater_last_error(None).decode(errors='replace')}")
+        self.h = h
+
+    def inflate(self, comp, blocks, out):
+        """comp, out: contiguous uint8 arrays; blocks = [(coff, clen, isize, uoff)].  Writes the accepted blocks into `out`; returns (int32 status per block, InflateStats)."""
+        comp = np.ascontiguousarray(comp, np.uint8)
+        assert out.dtype == np.uint8 and out.flags["C_CONTIGUOUS"] and out.flags["WRITEABLE"]
+        arr = (BgzfBlock * max(1, len(blocks)))()
+        for i, b in enumerate(blocks):
+            arr[i] = BgzfBlock(*[int(x) for x in b])
+        status = np.full(max(1, len(blocks)), -1, np.int32); st = InflateStats()
+        rc = self.lib.hlala_bgzf_inflate(self.h, comp.ctypes.data, comp.size, arr, len(blocks), out.ctypes.data, out.size, status.ctypes.data_as(c_i32p), C.byref(st))
+        if rc != 0:
+            raise HlalaError(f"hlala_bgzf_inflate failed ({rc}): {self.lib.hlala_inflater_last_error(self.h).decode(errors='replace')}")
+        return status[:len(blocks)], st
+
+    def bam_open_seeds(self, path, intervals, long_read_mode=False, threads=0, flags=0) -> SeedBatch:
+        """hlala_bam_extract_seeds_gpu: the sample of bam_open_seeds, its blocks inflated by this handle (SeedBatch.inflate_counts says how many)"""
+        arr = (BamInterval * max(1, len(intervals)))()
+        for i, (nm, a, b, c) in enumerate(intervals):
+            arr[i] = BamInterval(nm.encode(), int(a), int(b), int(c))
+        h = C.c_void_p()
+        self.lib.hlala_bam_last_error.restype = C.c_char_p
+        if self.lib.hlala_bam_extract_seeds_gpu(self.h, str(path).encode(), len(intervals), arr, int(bool(long_read_mode)), int(threads), int(flags), C.byref(h)) != 0:
+            raise HlalaError(self.lib.hlala_bam_last_error().decode(errors="replace"))
+        return SeedBatch(self.lib, h, long_read_mode)
+
+    def bam_extract_seeds_gpu(self, path, intervals, long_read_mode=False, threads=0, flags=0):
+        """as bam_extract_seeds, plus the inflate counts: (batch dict, names, counters, (gpu, rejected, host))"""
+        S = self.bam_open_seeds(path, intervals, long_read_mode, threads, flags)
+        try:
+            b = S.to_dict(); b.pop("first_chain")
+            return b, S.names(), S.counts, S.inflate_counts()
+        finally:
+            S.close()
+
+    def close(self):
+        if self.h:
+            self.lib.hlala_inflater_destroy(self.h); self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def bam_extract_seeds(lib, path, intervals, long_read_mode=False, threads=0):
@@ -673,7 +753,7 @@ def load_library(path: str | None = None):
     return lib
 
 
-ABI_VERSION = 5              # HLALA_ABI_VERSION of include/hlala_gpu.h
+ABI_VERSION = 6              # HLALA_ABI_VERSION of include/hlala_gpu.h
 DEBUG_WC_N, DEBUG_WC_BAND_FETCH, DEBUG_WC_BAND_WHY, DEBUG_WC_BAND_TIED = 88, 48, 62, 68      # include/hlala_gpu.h: debug section
 BUILD_AGENT_RELEASE = 2      # hlala_build_flags(): the in-memory DP class releases at agent scope (make EXTRA=-DHLALA_DP_AGENT_RELEASE)
 
@@ -694,6 +774,7 @@ EXPORTED_SYMBOLS = [
     "hlala_contigs_load_dir", "hlala_contigs_open_dir", "hlala_contigs_load_translations", "hlala_contigs_file_desc", "hlala_contigs_file_intervals", "hlala_contigs_file_free",
     "hlala_typer_open", "hlala_typer_close", "hlala_typer_last_error", "hlala_typer_n_levels", "hlala_typer_level_name", "hlala_typer_level_of", "hlala_typer_n_genes",
     "hlala_typer_gene", "hlala_typer_load_g_groups", "hlala_typer_g_translate", "hlala_typer_locus", "hlala_locus_free", "hlala_locus_get", "hlala_locus_cluster_id", "hlala_locus_type_cluster",
+    "hlala_inflater_create", "hlala_inflater_destroy", "hlala_inflater_last_error", "hlala_bgzf_inflate", "hlala_bam_extract_seeds_gpu", "hlala_seed_batch_inflate_counts",
     "hlala_locus_cluster_kmers", "hlala_type_locus", "hlala_kmer_presence", "hlala_kmer_keep_reads", "hlala_kmer_presence_kept", "hlala_kmer_forget_reads", "hlala_unit_alignment_stats", "hlala_typer_write_summary", "hlala_typer_begin_output", "hlala_locus_write_files", "hlala_locus_write_pairs_file", "hlala_typer_end_output",
 ]
 

@@ -28,6 +28,7 @@
 #include "kernel_exonpos.hip"
 #include "kernel_kmer.hip"
 #include "kernel_dp_band.hip"
+#include "kernel_inflate.hip"
 
 namespace hlala {
 size_t proj_slab_bytes_host(int stride, int maxNodesPerLevel) { return proj_slab_bytes(stride, maxNodesPerLevel); }
@@ -2263,13 +2264,174 @@ extern "C" int hlala_seed_batch_pin(hlala_seed_batch* S, int pin)
     return HLALA_OK;
 }
 
+// ---- BGZF inflate on the GPU (include/hlala_gpu.h; kernel_inflate.hip).  A call is cut into chunks of consecutive blocks (at most `chunk` compressed bytes, `outCap`
+// inflated bytes, `maxBlocks` blocks); chunk k uses slot k % 3, every slot has a stream of its own: gather the compressed bytes into the slot's page-locked
+// staging buffer -> upload -> kernel -> download into page-locked staging, all queued at once; the slot is drained (synchronise, copy the accepted blocks to their
+// places in the caller's pageable buffer) before it is used again, so the upload of chunk k + 1 and the download of chunk k - 1 run beside the kernel of chunk k.
+struct InflateSlot {
+    hipStream_t stream = nullptr; hipEvent_t ev[4]{};      // before the upload, before the kernel, after it, after the download
+    uint8_t* hComp = nullptr; uint8_t* dComp = nullptr; uint8_t* hOut = nullptr; uint8_t* dOut = nullptr;
+    hlala_bgzf_block* hDesc = nullptr; hlala_bgzf_block* dDesc = nullptr; int* hStatus = nullptr; int* dStatus = nullptr;
+    int64_t first = 0, count = 0; size_t outBytes = 0; bool busy = false;
+};
+struct hlala_inflater {
+    int device = 0; size_t chunk = 0, outCap = 0; int64_t maxBlocks = 0;
+    InflateSlot slot[3];
+    std::string err;
+};
+static thread_local std::string g_inflater_create_error;
+
+extern "C" const char* hlala_inflater_last_error(const hlala_inflater* f) { return f ? f->err.c_str() : g_inflater_create_error.c_str(); }
+extern "C" void hlala_inflater_destroy(hlala_inflater* f)
+{
+    if(!f) return;
+    DevGuard g(f->device);
+    for(InflateSlot& s : f->slot) {
+        if(s.stream) { (void)hipStreamSynchronize(s.stream); (void)hipStreamDestroy(s.stream); }
+        for(hipEvent_t e : s.ev) if(e) (void)hipEventDestroy(e);
+        if(s.hComp) (void)hipHostFree(s.hComp); if(s.hOut) (void)hipHostFree(s.hOut); if(s.hDesc) (void)hipHostFree(s.hDesc); if(s.hStatus) (void)hipHostFree(s.hStatus);
+        if(s.dComp) (void)hipFree(s.dComp); if(s.dOut) (void)hipFree(s.dOut); if(s.dDesc) (void)hipFree(s.dDesc); if(s.dStatus) (void)hipFree(s.dStatus);
+    }
+    delete f;
+}
+extern "C" int hlala_inflater_create(int32_t device, size_t chunk_bytes, hlala_inflater** out)
+{
+    if(!out) { g_inflater_create_error = "null argument"; return HLALA_E_ARG; }
+    *out = nullptr;
+    if(chunk_bytes == 0) chunk_bytes = HLALA_INFLATE_DEFAULT_CHUNK;
+    if(device < 0 || chunk_bytes < HLALA_INFLATE_MIN_CHUNK || chunk_bytes > ((size_t)1 << 30)) { g_inflater_create_error = "hlala_inflater_create: chunk_bytes outside [128 KiB, 1 GiB] or a negative device"; return HLALA_E_ARG; }
+    int ndev = 0;
+    hipError_t e = hipGetDeviceCount(&ndev);
+    if(e != hipSuccess || ndev <= 0 || device >= ndev) {
+        g_inflater_create_error = std::string("no HIP device available (") + (e != hipSuccess ? hipGetErrorString(e) : "device index out of range") + "); this library has no CPU fallback";
+        (void)hipGetLastError();
+        return HLALA_E_DEVICE;
+    }
+    hlala_inflater* f = new hlala_inflater();
+    f->device = device; f->chunk = chunk_bytes; f->outCap = 4 * chunk_bytes + 65536; f->maxBlocks = (int64_t)(chunk_bytes / 256) + 64;
+    DevGuard g(device);
+    auto fail = [&](const char* what) { g_inflater_create_error = std::string("hlala_inflater_create: ") + what + " failed"; (void)hipGetLastError(); hlala_inflater_destroy(f); return HLALA_E_DEVICE; };
+    { int cur = -1; if(hipGetDevice(&cur) != hipSuccess || cur != device) return fail("hipSetDevice"); }
+    for(InflateSlot& s : f->slot) {
+        if(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking) != hipSuccess) return fail("hipStreamCreate");
+        for(hipEvent_t& ev : s.ev) if(hipEventCreate(&ev) != hipSuccess) return fail("hipEventCreate");
+        const size_t nd = (size_t)f->maxBlocks;
+        if(hipHostMalloc((void**)&s.hComp, f->chunk, hipHostMallocDefault) != hipSuccess || hipHostMalloc((void**)&s.hOut, f->outCap, hipHostMallocDefault) != hipSuccess ||
+           hipHostMalloc((void**)&s.hDesc, nd * sizeof(hlala_bgzf_block), hipHostMallocDefault) != hipSuccess || hipHostMalloc((void**)&s.hStatus, nd * sizeof(int), hipHostMallocDefault) != hipSuccess) return fail("hipHostMalloc");
+        if(hipMalloc((void**)&s.dComp, f->chunk) != hipSuccess || hipMalloc((void**)&s.dOut, f->outCap) != hipSuccess ||
+           hipMalloc((void**)&s.dDesc, nd * sizeof(hlala_bgzf_block)) != hipSuccess || hipMalloc((void**)&s.dStatus, nd * sizeof(int)) != hipSuccess) return fail("hipMalloc");
+    }
+    *out = f;
+    return HLALA_OK;
+}
+
+// `landed` (may be null) is told about every chunk, in ascending block order, once its accepted blocks stand in `out` and its statuses in `status`; a non-zero
+// answer ends the call (HLALA_E_STATE) after the chunks in flight have been drained.
+static int inflate_run(hlala_inflater* f, const uint8_t* comp, size_t comp_bytes, const hlala_bgzf_block* blocks, int64_t n, uint8_t* out, size_t out_bytes, int32_t* status,
+                       hlala_inflate_stats* stats, int (*landed)(void*, int64_t, int64_t), void* user)
+{
+    if(!f) return HLALA_E_ARG;
+    f->err.clear();
+    if(n < 0 || (n > 0 && (!blocks || !status)) || (comp_bytes && !comp) || (out_bytes && !out)) { f->err = "hlala_bgzf_inflate: null argument"; return HLALA_E_ARG; }
+    const auto tWall = std::chrono::steady_clock::now();
+    // ---- the descriptors, before anything is launched
+    for(int64_t i = 0; i < n; i++) {
+        const hlala_bgzf_block& b = blocks[i];
+        if(b.isize > 65536u || b.coff > comp_bytes || b.clen > comp_bytes - b.coff || b.uoff > out_bytes || b.isize > out_bytes - b.uoff || b.clen > f->chunk) {
+            f->err = "hlala_bgzf_inflate: block " + std::to_string(i) + ": a range outside its buffer, more than 65536 bytes of payload, or more compressed bytes than a chunk holds";
+            return HLALA_E_ARG;
+        }
+    }
+    {
+        std::vector<int64_t> by; by.reserve((size_t)n);
+        for(int64_t i = 0; i < n; i++) if(blocks[i].isize) by.push_back(i);
+        std::sort(by.begin(), by.end(), [&](int64_t a, int64_t b) { return blocks[a].uoff < blocks[b].uoff; });
+        for(size_t k = 1; k < by.size(); k++)
+            if(blocks[by[k - 1]].uoff + blocks[by[k - 1]].isize > blocks[by[k]].uoff) { f->err = "hlala_bgzf_inflate: the output ranges of blocks " + std::to_string(by[k - 1]) + " and " + std::to_string(by[k]) + " overlap"; return HLALA_E_ARG; }
+    }
+    DevGuard g(f->device);
+    hlala_inflate_stats st{}; st.n_blocks = n;
+    int rc = HLALA_OK;
+    auto drain = [&](InflateSlot& s, bool deliver) {
+        if(!s.busy) return;
+        s.busy = false;
+        const hipError_t e = hipStreamSynchronize(s.stream);
+        if(e != hipSuccess) { if(rc == HLALA_OK) { f->err = std::string("hlala_bgzf_inflate: ") + hipGetErrorString(e); rc = HLALA_E_DEVICE; } return; }
+        float ms = 0;
+        if(hipEventElapsedTime(&ms, s.ev[0], s.ev[1]) == hipSuccess) st.ms_h2d += ms;
+        if(hipEventElapsedTime(&ms, s.ev[1], s.ev[2]) == hipSuccess) st.ms_kernel += ms;
+        if(hipEventElapsedTime(&ms, s.ev[2], s.ev[3]) == hipSuccess) st.ms_d2h += ms;
+        if(!deliver || rc != HLALA_OK) return;
+        for(int64_t k = 0; k < s.count; k++) {
+            const hlala_bgzf_block& b = blocks[s.first + k];
+            const int v = s.hStatus[k];
+            status[s.first + k] = v;
+            if(v == HLALA_INFLATE_OK) { st.n_ok++; if(b.isize) memcpy(out + b.uoff, s.hOut + s.hDesc[k].uoff, b.isize); } else st.n_rejected++;
+        }
+        if(landed && landed(user, s.first, s.count) != 0) { f->err = "hlala_bgzf_inflate: ended by the caller"; rc = HLALA_E_STATE; }
+    };
+    int64_t i = 0; int k = 0;
+    while(i < n && rc == HLALA_OK) {
+        InflateSlot& s = f->slot[k % 3]; k++;
+        drain(s, true);
+        if(rc != HLALA_OK) break;
+        size_t cb = 0, ob = 0; int64_t cnt = 0;
+        while(i + cnt < n && cnt < f->maxBlocks) {
+            const hlala_bgzf_block& b = blocks[i + cnt];
+            const size_t ca = (cb + 15) & ~(size_t)15;      // (every block starts on 16 bytes of the staging buffer)
+            if(ca + b.clen > f->chunk || ob + b.isize > f->outCap) break;
+            if(b.clen) memcpy(s.hComp + ca, comp + b.coff, b.clen);
+            hlala_bgzf_block& d = s.hDesc[cnt]; d.coff = ca; d.clen = b.clen; d.isize = b.isize; d.uoff = ob;
+            cb = ca + b.clen; ob += b.isize; cnt++;
+        }
+        // (cnt >= 1: a single block fits an empty chunk -- clen <= chunk was checked, isize <= 65536 < outCap)
+        s.first = i; s.count = cnt; s.outBytes = ob; i += cnt;
+        hipError_t e = hipEventRecord(s.ev[0], s.stream);
+        if(e == hipSuccess && cb) e = hipMemcpyAsync(s.dComp, s.hComp, cb, hipMemcpyHostToDevice, s.stream);
+        if(e == hipSuccess) e = hipMemcpyAsync(s.dDesc, s.hDesc, (size_t)cnt * sizeof(hlala_bgzf_block), hipMemcpyHostToDevice, s.stream);
+        if(e == hipSuccess) e = hipEventRecord(s.ev[1], s.stream);
+        if(e == hipSuccess) { hipLaunchKernelGGL(k_bgzf_inflate, dim3((unsigned)cnt), dim3(64), 0, s.stream, (const uint8_t*)s.dComp, (const hlala_bgzf_block*)s.dDesc, (int)cnt, s.dOut, s.dStatus); e = hipGetLastError(); }
+        if(e == hipSuccess) e = hipEventRecord(s.ev[2], s.stream);
+        if(e == hipSuccess && ob) e = hipMemcpyAsync(s.hOut, s.dOut, ob, hipMemcpyDeviceToHost, s.stream);
+        if(e == hipSuccess) e = hipMemcpyAsync(s.hStatus, s.dStatus, (size_t)cnt * sizeof(int), hipMemcpyDeviceToHost, s.stream);
+        if(e == hipSuccess) e = hipEventRecord(s.ev[3], s.stream);
+        s.busy = true;
+        if(e != hipSuccess) { f->err = std::string("hlala_bgzf_inflate: ") + hipGetErrorString(e); rc = HLALA_E_DEVICE; }
+    }
+    // the chunks still in flight, oldest first (slots are used round-robin: the oldest is the one that would be used next)
+    for(int j = 0; j < 3; j++) drain(f->slot[(k + j) % 3], rc == HLALA_OK);
+    st.ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tWall).count();
+    if(stats) *stats = st;
+    return rc;
+}
+extern "C" int hlala_bgzf_inflate(hlala_inflater* f, const uint8_t* comp, size_t comp_bytes, const hlala_bgzf_block* blocks, int64_t n_blocks, uint8_t* out, size_t out_bytes,
+                                  int32_t* status, hlala_inflate_stats* stats)
+{
+    return inflate_run(f, comp, comp_bytes, blocks, n_blocks, out, out_bytes, status, stats, nullptr, nullptr);
+}
+static int bam_inflate_hook(void* inflater, const uint8_t* comp, size_t comp_bytes, const hlala_bgzf_block* blocks, int64_t n, uint8_t* out, size_t out_bytes, int32_t* status,
+                            int (*landed)(void*, int64_t, int64_t), void* user, std::string* err)
+{
+    hlala_inflater* f = (hlala_inflater*)inflater;
+    const int rc = inflate_run(f, comp, comp_bytes, blocks, n, out, out_bytes, status, nullptr, landed, user);
+    if(rc != HLALA_OK && err) *err = f->err;
+    return rc;
+}
+extern "C" int hlala_bam_extract_seeds_gpu(hlala_inflater* f, const char* path, int32_t n_intervals, const hlala_bam_interval* iv, int32_t long_read_mode, int32_t n_threads, int32_t flags,
+                                           hlala_seed_batch** out)
+{
+    static std::once_flag hookOnce;                  // (samples may decode on several threads)
+    std::call_once(hookOnce, []() { hlala_host::g_bam_inflate_hook = bam_inflate_hook; });
+    return hlala_host::bam_extract_seeds_impl(path, n_intervals, iv, long_read_mode, n_threads, flags, true, f, out);
+}
+
 extern "C" int hlala_abi_sizeof(const char* name)
 {
     if(!name) return -1;
     const std::string n(name);
 #define SZ(t) if(n == #t) return (int)sizeof(t);
     SZ(hlala_graph_desc) SZ(hlala_contigs_desc) SZ(hlala_params) SZ(hlala_graph_info) SZ(hlala_batch_in) SZ(hlala_seeds_in)
-    SZ(hlala_chains_out) SZ(hlala_pairs_out) SZ(hlala_batch_stats) SZ(hlala_exon_in) SZ(hlala_call_out) SZ(hlala_locus_desc) SZ(hlala_exon_positions_out) SZ(hlala_filter_params) SZ(hlala_filter_stats) SZ(hlala_insert_size_out) SZ(hlala_locus_info) SZ(hlala_locus_report_in) SZ(hlala_locus_report_out) SZ(hlala_unit_stats_out) SZ(hlala_pairs_packed_out)
+    SZ(hlala_chains_out) SZ(hlala_pairs_out) SZ(hlala_batch_stats) SZ(hlala_exon_in) SZ(hlala_call_out) SZ(hlala_locus_desc) SZ(hlala_exon_positions_out) SZ(hlala_filter_params) SZ(hlala_filter_stats) SZ(hlala_insert_size_out) SZ(hlala_locus_info) SZ(hlala_locus_report_in) SZ(hlala_locus_report_out) SZ(hlala_unit_stats_out) SZ(hlala_pairs_packed_out) SZ(hlala_bgzf_block) SZ(hlala_inflate_stats)
 #undef SZ
     return -1;
 }

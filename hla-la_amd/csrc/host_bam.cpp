@@ -232,6 +232,7 @@ struct hlala_seed_batch {
     Buf<char> name_chars; Buf<int64_t> name_off;          // names of the units, NUL-terminated
     int64_t n_units = 0; int32_t unpaired = 0; int64_t examined = 0, n_seeds = 0, n_incomplete = 0;
     double seconds[6] = {0, 0, 0, 0, 0, 0}; int32_t threads = 1;
+    int64_t inflate_counts[3] = {0, 0, 0};      // blocks inflated on the GPU, rejected there and inflated again on the host, inflated on the host only
     bool pinned = false;
     // page-locking window by window (hlala_seed_batch_pin(S, 2)): per bulk array the bytes locked so far, and the regions to unlock
     bool pin_lazy = false; std::mutex pin_mu; std::vector<size_t> pin_cursor; std::vector<std::pair<void*, size_t>> pin_regions;
@@ -372,6 +373,7 @@ std::vector<std::pair<void*, size_t>>& seed_batch_pin_regions(hlala_seed_batch* 
 void (*g_seed_batch_pin_upto)(hlala_seed_batch*, int64_t) = nullptr;      // set by the GPU library: page-locks what the units before unit_end occupy and is not locked yet
 bool& seed_batch_pinned_flag(hlala_seed_batch* S) { return S->pinned; }
 void (*g_seed_batch_unpin)(hlala_seed_batch*) = nullptr;       // set by the GPU library (hlala_seed_batch_pin): a pinned batch is unpinned before it is freed
+bam_inflate_hook_t g_bam_inflate_hook = nullptr;               // set by the GPU library (hlala_bam_extract_seeds_gpu)
 }  // namespace hlala_host
 
 // (host code: no device involved)
@@ -403,9 +405,36 @@ extern "C" int hlala_bam_extract_seeds_mt(const char* path, int32_t n_intervals,
 }
 
 extern "C" int hlala_bam_extract_seeds_opt(const char* path, int32_t n_intervals, const hlala_bam_interval* iv, int32_t long_read_mode, int32_t n_threads, int32_t flags, hlala_seed_batch** out)
+{
+    return hlala_host::bam_extract_seeds_impl(path, n_intervals, iv, long_read_mode, n_threads, flags, false, nullptr, out);
+}
+
+namespace {
+// what the hook's `landed` call needs: the statuses of a round's blocks, and how to inflate a rejected block again on the host
+struct GpuRound {
+    const Block* blocks; const uint8_t* comp; uint8_t* out; uint64_t u0; std::vector<int32_t>* status; std::atomic<uint8_t>* blockDone; Inflater* host;
+    int64_t nGpu = 0, nRetried = 0; std::exception_ptr err;
+    static int landed(void* user, int64_t first, int64_t count)
+    {
+        GpuRound& R = *(GpuRound*)user;
+        try {
+            for(int64_t k = first; k < first + count; k++) {
+                const Block& b = R.blocks[k];
+                if((*R.status)[(size_t)k] != 0) { R.host->run(R.comp + b.coff, b.clen, R.out + (size_t)(b.uoff - R.u0), b.isize); R.nRetried++; }      // the host engine's verdict stands (it throws what the host path throws)
+                else R.nGpu++;
+                R.blockDone[(size_t)k].store(1, std::memory_order_release);
+            }
+        } catch(...) { R.err = std::current_exception(); return 1; }
+        return 0;
+    }
+};
+}  // namespace
+
+int hlala_host::bam_extract_seeds_impl(const char* path, int32_t n_intervals, const hlala_bam_interval* iv, int32_t long_read_mode, int32_t n_threads, int32_t flags, bool gpu, void* gpuInflater, hlala_seed_batch** out)
 try {
     if(!path || !out || n_intervals < 0 || (n_intervals > 0 && !iv) || n_threads < 0) return HLALA_E_ARG;
     *out = nullptr; g_bam_error.clear();
+    if(gpu && (!gpuInflater || !g_bam_inflate_hook)) { g_bam_error = "hlala_bam_extract_seeds_gpu: no inflater"; return HLALA_E_ARG; }
     int T = n_threads;
     // Default: at most 32 threads.  Measured on a 256-thread host (tools/gpu_decode_threads.sh, 8.4 M pairs, 2.6 GB of BAM): 5.2 s on 8 threads, 3.5 on 16, 2.85 on 32,
     // 3.0 on 64, 3.3-3.7 on 128 -- the phases are passes over ~12 GB of inflated records bound by memory latency and by the first touch of their
@@ -496,11 +525,26 @@ try {
         const bool lastSegment = b1 == blocks.size();
         std::vector<size_t> recStart;
         recStart.reserve(dn / 200 + 16);
-        parallel_for_beside((int64_t)nBlk, T, [&](int64_t k, int t) {
+        // the round's blocks: on the host, handed out to T threads in ascending order; or on the GPU, fed by ONE thread (chunks land in ascending order; a block the
+        // GPU rejects is inflated again by the host engine as its chunk lands)
+        auto inflateHost = [&](int64_t k, int t) {
             const Block& b = blocks[b0 + (size_t)k];
             inflaters[(size_t)t].run(mf.p + b.coff, b.clen, bufp + carry + (size_t)(b.uoff - u0), b.isize);
             blockDone[(size_t)k].store(1, std::memory_order_release);
-        }, [&](const std::atomic<bool>& stop) {
+        };
+        auto inflateGpu = [&](int64_t, int) {
+            std::vector<hlala_bgzf_block> desc(nBlk); std::vector<int32_t> status(nBlk, 0);
+            for(size_t k = 0; k < nBlk; k++) { const Block& b = blocks[b0 + k]; desc[k].coff = b.coff; desc[k].clen = b.clen; desc[k].isize = b.isize; desc[k].uoff = b.uoff - u0; }
+            GpuRound R{blocks.data() + b0, mf.p, bufp + carry, u0, &status, blockDone.get(), &inflaters[0]};
+            std::string herr;
+            const int rc = g_bam_inflate_hook(gpuInflater, mf.p, mf.n, desc.data(), (int64_t)nBlk, bufp + carry, segBytes, status.data(), GpuRound::landed, &R, &herr);
+            if(R.err) std::rethrow_exception(R.err);
+            if(rc != HLALA_OK) throw Fail("BGZF inflate on the GPU failed: " + herr);
+            S->inflate_counts[0] += R.nGpu; S->inflate_counts[1] += R.nRetried;
+        };
+        if(!gpu) S->inflate_counts[2] += (int64_t)nBlk;
+        auto inflateItem = [&](int64_t k, int t) { if(gpu) inflateGpu(k, t); else inflateHost(k, t); };
+        parallel_for_beside(gpu ? (int64_t)1 : (int64_t)nBlk, gpu ? std::min(T, 2) : T, inflateItem, [&](const std::atomic<bool>& stop) {
             size_t ready = carry, kReady = 0;                   // bytes [0, ready) of the buffer are final: the carried bytes + the blocks before kReady
             // true when bytes [o, o + k) are there to be read (waits for the blocks that hold them); false: the round ends before o + k, or a worker failed
             auto avail = [&](size_t k) -> bool {
@@ -813,6 +857,12 @@ extern "C" const char* hlala_seed_batch_name(const hlala_seed_batch* S, int64_t 
     if(!S || unit < 0 || unit >= S->n_units) return nullptr;
     try { ensure_filled(S, unit, unit + 1); } catch(...) { return nullptr; }
     return S->name_chars.data() + S->name_off[(size_t)unit];
+}
+extern "C" int hlala_seed_batch_inflate_counts(const hlala_seed_batch* S, int64_t* counts)
+{
+    if(!S || !counts) return HLALA_E_ARG;
+    for(int i = 0; i < 3; i++) counts[i] = S->inflate_counts[i];
+    return HLALA_OK;
 }
 extern "C" int hlala_seed_batch_timing(const hlala_seed_batch* S, double* seconds6, int32_t* n_threads)
 {

@@ -4,6 +4,7 @@
 #include <string>
 
 #include "flat_graph.hpp"
+#include "inflate_core.h"
 
 static thread_local std::string g_err;
 
@@ -50,5 +51,39 @@ int hlala_host_linear(const hlala::FlatGraph* F, uint32_t* lin_label, int32_t* l
     memcpy(lin_label, F->lin_label.data(), F->lin_label.size() * 4); memcpy(lin_eid, F->lin_eid.data(), F->lin_eid.size() * 4);
     memcpy(lin_out, F->lin_out.data(), F->lin_out.size()); memcpy(lin_in, F->lin_in.data(), F->lin_in.size());
     return 0;
+}
+// The DEFLATE decoder core of the device kernel (inflate_core.h) with a serial copy loop around it: raw DEFLATE bytes comp[0, clen) -> out[0, isize).
+// Returns a HLALA_INFLATE_* status; never reads or writes outside the two ranges.
+int hlala_host_inflate_model(const uint8_t* comp, uint32_t clen, uint8_t* out, uint32_t isize)
+{
+    using namespace hlala_inflate;
+    static thread_local InfTables T;
+    InfBits b; bits_init(b, comp, clen, 0, 0xFFFFFFFFu, 0);
+    uint32_t produced = 0;
+    for(;;) {
+        int final = 0, type = 0; uint32_t at = 0, len = 0;
+        const int rc = read_block_header(b, T, &final, &type, &at, &len);
+        if(rc != HLALA_INFLATE_OK) return rc;
+        if(type == 0) {
+            if(len > isize - produced) return HLALA_INFLATE_OUTPUT_SIZE;
+            for(uint32_t k = 0; k < len; k++) out[produced + k] = comp[at + k];
+            produced += len;
+            bits_init(b, comp, clen, 0, 0xFFFFFFFFu, 8ull * ((uint64_t)at + len));
+        } else {
+            for(;;) {
+                uint32_t tok = 0;
+                const int r = token(b, T, &tok);
+                if(r == INF_END_OF_BLOCK) break;
+                if(r != INF_TOKEN) return r;
+                if(tok < 256) { if(produced >= isize) return HLALA_INFLATE_OUTPUT_SIZE; out[produced++] = (uint8_t)tok; continue; }
+                const uint32_t n = tok >> 16, d = tok & 0xFFFFu;
+                if(d > produced) return HLALA_INFLATE_FAR_DISTANCE;
+                if(n > isize - produced) return HLALA_INFLATE_OUTPUT_SIZE;
+                for(uint32_t k = 0; k < n; k++) out[produced + k] = out[produced + k - d];
+                produced += n;
+            }
+        }
+        if(final) return produced == isize ? HLALA_INFLATE_OK : HLALA_INFLATE_OUTPUT_SIZE;
+    }
 }
 }

@@ -37,5 +37,14 @@ std::vector<std::pair<void*, size_t>>& seed_batch_pin_regions(hlala_seed_batch* 
 extern void (*g_seed_batch_pin_upto)(hlala_seed_batch*, int64_t);
 extern void (*g_seed_batch_unpin)(hlala_seed_batch*);
 
+// The BAM decoder with its blocks inflated on the GPU (hlala_bam_extract_seeds_gpu).  host_bam.cpp holds no device code (it is part of libhlala_host.so as well), so
+// the GPU library sets this hook: inflate blocks[0, n) of comp into out in ascending order, write their statuses, and call landed(user, first, count) for every
+// chunk of blocks that has arrived (non-zero: stop).  Returns HLALA_OK or a HLALA_E_* code with its text in *err.
+typedef int (*bam_inflate_hook_t)(void* inflater, const uint8_t* comp, size_t comp_bytes, const hlala_bgzf_block* blocks, int64_t n, uint8_t* out, size_t out_bytes, int32_t* status,
+                                  int (*landed)(void*, int64_t, int64_t), void* user, std::string* err);
+extern bam_inflate_hook_t g_bam_inflate_hook;
+// hlala_bam_extract_seeds_opt (gpu = false) and hlala_bam_extract_seeds_gpu (gpu = true: the hook above inflates with `inflater`)
+int bam_extract_seeds_impl(const char* path, int32_t n_intervals, const hlala_bam_interval* iv, int32_t long_read_mode, int32_t n_threads, int32_t flags, bool gpu, void* inflater, hlala_seed_batch** out);
+
 }  // namespace hlala_host
 #endif

@@ -10,7 +10,7 @@
 // terminate), this program prints the message to stderr and exits with a non-zero status -- HLA-LA.pl treats any non-zero status as
 // failure (:567-570).  Extra, optional arguments of this program: --devices <gpu,gpu,...> (or --device <gpu>): the batches of the sample are
 // dealt round-robin to one context per listed GPU (a GPU may be listed twice: two contexts on it), results do not depend on the list;
-// --decodeSlots <samples that decode at one time, default CPUs / 16>, --tailPool <k: GPU batches per launch of the widest DP classes>, --decodeThreads <host threads of the BAM decoder, default all>, --batchPairs <units per GPU batch>, --rngSeed <base of the end-cell draws>,
+// --decodeSlots <samples that decode at one time, default CPUs / 16>, --tailPool <k: GPU batches per launch of the widest DP classes>, --decodeThreads <host threads of the BAM decoder, default all>, --gpuInflate 0|1 <BGZF blocks inflated on the first listed GPU, default 0>, --batchPairs <units per GPU batch>, --rngSeed <base of the end-cell draws>,
 // --loci A,B,... (default: the reference's 17 loci, hla/HLATyper.cpp:42).  Several samples in one call (BASELINE config 4): comma-separated lists of
 // equal length in --sampleID, --outputDirectory, --FASTQ1, --FASTQ2 (--FASTQU); sample i runs on device i % #devices, all samples side by side.
 // Not rebuilt: the --BAM entry (the Perl driver never uses it: it extracts reads itself and passes FASTQ files), read simulation /
@@ -237,6 +237,8 @@ int action_HLA_one(const std::map<std::string, std::string>& arguments, const st
     struct Joiner { std::thread& t; ~Joiner() { if(t.joinable()) t.join(); } } typerJoin{typerThread};
     const std::shared_ptr<mapper::GraphDirectory> graphDirectory = shared ? shared->dir : std::make_shared<mapper::GraphDirectory>(PRG_graph_dir, mapAgainstCompleteGenome);
     mapper::processBAM BAMprocessor(graphDirectory, longReads.length() ? 16384 : 384, rngSeed, devices, decodeThreads);
+    // --gpuInflate 1: the BGZF blocks of the BAM are inflated on the sample's first device instead of on the host's threads (include/hlala_gpu.h: hlala_bam_extract_seeds_gpu); the sample is the same
+    BAMprocessor.set_gpu_inflate(arguments.count("gpuInflate") && std::atoi(arguments.at("gpuInflate").c_str()) != 0);
     const double loadSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - tStart).count();
     turnGuard.begin_decode();
     std::cout << timestamp() << "Start seed extraction\n" << std::flush;
@@ -251,6 +253,8 @@ int action_HLA_one(const std::map<std::string, std::string>& arguments, const st
               << BAMprocessor.decode_phase_seconds[3] << ", name sort " << BAMprocessor.decode_phase_seconds[4] << ", layout (sizes and offsets; the windows are filled batch by batch beside the GPU) " << BAMprocessor.decode_phase_seconds[5] << "); beside it: contexts on " << BAMprocessor.n_devices()
               << " device(s) ready after " << BAMprocessor.context_seconds << " s (of which " << BAMprocessor.directory_wait_seconds << " s waiting for the graph directory: reference intervals after " << graphDirectory->intervals_seconds
               << " s -- the decoder starts with them --, graph read after " << graphDirectory->graph_seconds << " s, translation tables after " << graphDirectory->contigs_seconds << " s, typer files beside them); seed extraction in all " << openSeconds << " s\n" << std::flush;
+    if(BAMprocessor.gpu_inflate()) std::cout << "BGZF inflate: " << BAMprocessor.inflate_counts[0] << " blocks on the GPU, " << BAMprocessor.inflate_counts[1] << " rejected there and inflated again on the host, "
+                                             << BAMprocessor.inflate_counts[2] << " on the host only\n" << std::flush;
     if(!longReads.length() && !borrowed) std::cout << "Insert size: mean " << BAMprocessor.IS_mean << ", sd " << BAMprocessor.IS_sd << "\n" << std::flush;
     // the G-group table is looked up in the working directory, as the reference does (hla/HLATyper.cpp:4160-4166; HLA-LA.pl chdirs to the source directory)
     typerThread.join();

@@ -351,12 +351,20 @@ public:
         hlala_params pr{200.0, 35.0, rng_seed_, longReads ? 1 : 0, max_columns_, 0};
         if(!borrowed) ctxs_.assign(devices_.size(), nullptr);
         std::vector<std::string> errs(devices_.size());
+        // --gpuInflate 1: the BGZF blocks are inflated on the sample's first device (an hlala_inflater: a handle of its own, it needs no graph and works beside
+        // the contexts that are being created); made before the decoder thread starts, destroyed after the decode
+        struct InflaterOwner { hlala_inflater* f = nullptr; ~InflaterOwner() { if(f) hlala_inflater_destroy(f); } } inflater;
+        if(gpu_inflate_ && hlala_inflater_create(devices_[0], 0, &inflater.f) != HLALA_OK) throw std::runtime_error(std::string("hlala_inflater_create: ") + hlala_inflater_last_error(nullptr));
         ThreadJoiner tdec, th;
         // (the decoder needs the reference intervals only: it starts while the graph directory may still be reading its graph and translation tables)
         tdec.start([&]() {
             // (the bases stay 4-bit packed as the BAM records hold them: a copy instead of an unpacking pass here, half the bytes to upload, unpacked on the device)
             const int32_t seedFlags = std::getenv("HLALA_SEEDS_ASCII") ? 0 : HLALA_SEEDS_PACKED;          // (HLALA_SEEDS_ASCII=1: the decoder unpacks the bases on the host, as before round 4 -- for A/B runs)
-            try { if(hlala_bam_extract_seeds_opt(BAM.c_str(), (int32_t)intervals_.size(), intervals_.data(), longReads ? 1 : 0, threads_, seedFlags, &seeds_) != HLALA_OK) bamErr = std::string("BAM: ") + hlala_bam_last_error(); }
+            try {
+                const int rc = inflater.f ? hlala_bam_extract_seeds_gpu(inflater.f, BAM.c_str(), (int32_t)intervals_.size(), intervals_.data(), longReads ? 1 : 0, threads_, seedFlags, &seeds_)
+                                          : hlala_bam_extract_seeds_opt(BAM.c_str(), (int32_t)intervals_.size(), intervals_.data(), longReads ? 1 : 0, threads_, seedFlags, &seeds_);
+                if(rc != HLALA_OK) bamErr = std::string("BAM: ") + hlala_bam_last_error();
+            }
             catch(const std::exception& e) { bamErr = e.what(); }
             decode_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         });
@@ -369,17 +377,22 @@ public:
         th.join();
         context_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         tdec.join();
+        if(inflater.f) { hlala_inflater_destroy(inflater.f); inflater.f = nullptr; }
         if(!bamErr.empty()) throw std::runtime_error(bamErr);
         for(const std::string& e : errs) if(!e.empty()) throw std::runtime_error(e);
         // several devices: the merge steps of the sample's results that live on the devices (the per-level read counters; the per-pair records for callers that want
         // them) go over RCCL between the contexts (include/hlala_gpu.h: hlala_comm_*; contexts that share a device are served by copies)
         if(!borrowed && ctxs_.size() > 1 && hlala_comm_create(ctxs_.data(), (int)ctxs_.size(), &comm_) != HLALA_OK) throw std::runtime_error(std::string("hlala_comm_create: ") + hlala_comm_last_error(nullptr));
         hlala_seed_batch_timing(seeds_, decode_phase_seconds, &decode_threads);
+        hlala_seed_batch_inflate_counts(seeds_, inflate_counts);
         n_units = hlala_seed_batch_units(seeds_); longReadsMode = longReads; BAM_ = BAM;
         batchPairs_ = batchPairs > 0 ? batchPairs : (n_units > 0 ? (n_units > 0x7FFFFFFF ? 0x7FFFFFFF : (int32_t)n_units) : 1);
         live_.assign((size_t)n_batches(), nullptr); aligned_.assign((size_t)n_batches(), 0);
         if(!borrowed) finish_open();
     }
+    void set_gpu_inflate(bool on) { gpu_inflate_ = on; }       // before openBAM
+    bool gpu_inflate() const { return gpu_inflate_; }
+    int64_t inflate_counts[3] = {0, 0, 0};                     // hlala_seed_batch_inflate_counts of the sample: blocks inflated on the GPU, rejected there and redone on the host, host only
     // what openBAM does on the contexts once they are this sample's: page-locking mode, insert size
     void finish_open()
     {
@@ -457,7 +470,7 @@ private:
         if(hlala_seed_batch_window(seeds_, u0, n, &in) != HLALA_OK) throw std::runtime_error(std::string("alignReads: ") + hlala_bam_last_error());
     }
     std::shared_ptr<GraphDirectory> gdir_;
-    std::string graphDir_; bool extended_; int max_columns_; uint32_t rng_seed_; std::vector<int> devices_; int threads_;
+    std::string graphDir_; bool extended_; int max_columns_; uint32_t rng_seed_; std::vector<int> devices_; int threads_; bool gpu_inflate_ = false;
     hlala_graph_file* graph_ = nullptr; hlala_contigs_file* contigs_ = nullptr; const std::vector<hlala_bam_interval>& intervals_;      // owned by gdir_
     hlala_seed_batch* seeds_ = nullptr; std::vector<hlala_ctx*> ctxs_; hlala_comm* comm_ = nullptr; int tail_pool_ = 1; bool owns_ctx_ = true; std::string BAM_;
     int32_t batchPairs_ = 1; std::vector<hlala_batch*> live_; std::vector<char> aligned_;       // aligned_[bi]: hlala_align_batch has been queued for live_[bi]

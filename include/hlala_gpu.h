@@ -426,6 +426,52 @@ const char* hlala_bam_last_error(void);
  * keeps zlib).  The decoded sample does not depend on it. */
 const char* hlala_bam_inflate_engine(void);
 
+/* ------------------------------------------------------------------------------------------
+ * BGZF inflate on the GPU (opt-in; the entry points above inflate on the host).  BGZF blocks are independent raw DEFLATE streams (RFC 1951) of at
+ * most 64 KiB of payload: one wavefront decodes one block (csrc/kernel_inflate.hip; the serial part of the decoder is csrc/inflate_core.h, which the
+ * host can run as well).  The CRC-32 of a block is not verified (the host engines do not verify it either).
+ *
+ * An hlala_inflater is a light handle of its own, not an hlala_ctx: it needs no graph and can decode a sample while the contexts are still being
+ * created.  It owns its streams, its page-locked staging buffers and its device buffers.  Without a GPU hlala_inflater_create fails with
+ * HLALA_E_DEVICE: there is no CPU fallback.  A handle serves one call at a time.
+ * ---------------------------------------------------------------------------------------- */
+/* per-block status of the decoder */
+#define HLALA_INFLATE_OK               0
+#define HLALA_INFLATE_RESERVED_BTYPE   1   /* block type 3                                                                                   */
+#define HLALA_INFLATE_STORED_LEN       2   /* stored block: LEN is not the complement of NLEN                                                 */
+#define HLALA_INFLATE_BAD_CODE         3   /* code lengths: over-subscribed or incomplete set, repeat without a previous length, more than    */
+                                           /* 286 literal/length or 30 distance lengths, no end-of-block code.  Accepted although incomplete: */
+                                           /* a distance code of one 1-bit code, and no distance code at all in a block of literals           */
+#define HLALA_INFLATE_BAD_SYMBOL       4   /* literal/length symbol 286 or 287, distance symbol 30 or 31, or bits that are no code            */
+#define HLALA_INFLATE_FAR_DISTANCE     5   /* a match reaches before the first output byte of the block (there is no preset dictionary)      */
+#define HLALA_INFLATE_INPUT_EXHAUSTED  6   /* the stream wants bits beyond its last byte                                                      */
+#define HLALA_INFLATE_OUTPUT_SIZE      7   /* the stream does not produce exactly isize bytes                                                 */
+/* smallest and default number of compressed bytes staged per launch (chunk_bytes of hlala_inflater_create; smaller non-zero values are HLALA_E_ARG) */
+#define HLALA_INFLATE_MIN_CHUNK      ((size_t)1 << 17)
+#define HLALA_INFLATE_DEFAULT_CHUNK  ((size_t)32 << 20)
+typedef struct hlala_inflater hlala_inflater;
+/* raw DEFLATE bytes [coff, coff + clen) of comp -> [uoff, uoff + isize) of out; isize <= 65536, clen <= chunk_bytes */
+typedef struct { uint64_t coff; uint32_t clen; uint32_t isize; uint64_t uoff; } hlala_bgzf_block;
+/* blocks of the last call and how many the decoder accepted / rejected; summed device times of the uploads, kernels and downloads (they overlap: chunk
+ * k + 1 is uploaded and chunk k - 1 downloaded beside the kernel of chunk k), wall clock of the call */
+typedef struct { int64_t n_blocks, n_ok, n_rejected; double ms_h2d, ms_kernel, ms_d2h, ms_wall; } hlala_inflate_stats;
+int  hlala_inflater_create(int32_t device, size_t chunk_bytes /* compressed bytes staged per launch; 0 = default */, hlala_inflater** out);
+void hlala_inflater_destroy(hlala_inflater* inf);
+const char* hlala_inflater_last_error(const hlala_inflater* inf);
+/* comp, blocks, out and status are host memory.  The descriptors are checked before anything is launched (HLALA_E_ARG: a range outside comp or out, isize
+ * beyond 65536, a block larger than a chunk, output ranges that overlap).  status[i] receives the HLALA_INFLATE_* status of block i; the output range of a
+ * rejected block holds unspecified bytes, nothing else of out is written.  Returns HLALA_OK whenever the call itself worked. */
+int  hlala_bgzf_inflate(hlala_inflater* inf, const uint8_t* comp, size_t comp_bytes, const hlala_bgzf_block* blocks, int64_t n_blocks,
+                        uint8_t* out, size_t out_bytes, int32_t* status /* [n_blocks] */, hlala_inflate_stats* stats /* or NULL */);
+/* The sample of hlala_bam_extract_seeds_opt, the BGZF blocks inflated by `inf`: one thread feeds the GPU round by round while the calling thread walks the record
+ * lengths behind the chunks that have landed (with n_threads = 1 there is no second thread: the round is inflated first and walked afterwards); n_threads parse, group
+ * and sort as before.  A block the GPU rejects is inflated again by the host engine, whose
+ * verdict stands: errors and their texts are those of the host path. */
+int  hlala_bam_extract_seeds_gpu(hlala_inflater* inf, const char* bam_path, int32_t n_intervals, const hlala_bam_interval* intervals,
+                                 int32_t long_read_mode, int32_t n_threads, int32_t flags, hlala_seed_batch** out);
+/* counts[3]: blocks inflated on the GPU, blocks the GPU rejected and the host engine ran again, blocks inflated on the host only */
+int  hlala_seed_batch_inflate_counts(const hlala_seed_batch* s, int64_t* counts);
+
 /* Page-locked host memory for the buffers a caller hands to hlala_batch_create / hlala_batch_get_pairs_packed / the getters: transfers from and
  * to such buffers are true DMA (asynchronous, full PCIe rate); pageable buffers work everywhere, at about a third of the rate.  hlala_host_register
  * pins an existing allocation in place (e.g. the arrays of a seed batch: hlala_seed_batch_pin), hlala_host_unregister undoes it.  */
@@ -758,10 +804,11 @@ int  hlala_abi_sizeof(const char* struct_name);
  * hlala_abi_sizeof cannot see) or a struct grows: 2 = hlala_batch_in carries 64-bit window offsets and an absolute read_primary (round 3);
  * 3 = hlala_batch_stats ends with n_dp_jump_free / ms_dp_jump_free, hlala_batch_in with read_bases_packed / first_read (round 4);
  * 4 = hlala_batch_stats ends with n_dp_band / n_dp_band_failed / n_dp_jump_free_failed / ms_dp_band (round 5);
- * 5 = ... with n_dp_band2 / n_dp_band2_failed / ms_dp_band2, hlala_set_tail_pool / hlala_flush / hlala_comm_* exist (round 6).  A caller compares
+ * 5 = ... with n_dp_band2 / n_dp_band2_failed / ms_dp_band2, hlala_set_tail_pool / hlala_flush / hlala_comm_* exist (round 6);
+ * 6 = hlala_inflater_* / hlala_bgzf_inflate / hlala_bam_extract_seeds_gpu / hlala_seed_batch_inflate_counts exist (additive).  A caller compares
  * hlala_abi_version() with the HLALA_ABI_VERSION it was compiled against and refuses to run on a mismatch (hla-la_amd/__init__.py and
  * hla-la_amd/host/hlala_host.hpp do). */
-#define HLALA_ABI_VERSION 5
+#define HLALA_ABI_VERSION 6
 int  hlala_abi_version(void);
 /* ---- debug / diagnostics section (tests and tools only; not part of the path the reference calls).  Layouts may change between rounds: the constants below are
  * checked against the library's own at compile time (hlala_api.hip). */

@@ -1,0 +1,117 @@
+#!/usr/bin/env python3
+"""BGZF inflate: the host engine against the GPU kernel on one BAM (its output is meant for profiles/inflate_gpu.txt, which is yet to be produced).
+
+A sample is drawn with the generators of bench.py's end-to-end leg (tools/synth.py: make_world_m, make_batch_m, BamWriter on tools/graphm/bamwriter.cpp;
+reference names of tools/graphm_dir.py) and written coordinate-sorted at level 1, at least --min-inflated-gb of records.  hlala_bam_extract_seeds_opt and
+hlala_bam_extract_seeds_gpu then decode it alternately: one warm-up each, --runs timed runs each, the same thread count.  Printed per run: the six phase times
+of hlala_seed_batch_timing; for the GPU path also the blocks by who inflated them; and once, hlala_bgzf_inflate on all blocks of the file (hlala_inflate_stats:
+upload, kernel, download, wall; blocks/s and inflated GB/s).  There is no threshold: the yardstick is the host engine's inflate phase on the same file and box."""
+import argparse
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def bgzf_blocks(path):
+    """[(payload offset, payload bytes, isize)] of the non-empty blocks, and the file's bytes (memory-mapped)"""
+    raw = np.memmap(path, np.uint8, "r"); o = 0; out = []
+    n = raw.size
+    while o < n:
+        xlen = int(raw[o + 10]) | (int(raw[o + 11]) << 8)
+        bsize = (int(raw[o + 16]) | (int(raw[o + 17]) << 8)) + 1          # (the BC subfield is the first one in every block this repository writes)
+        isize = int.from_bytes(raw[o + bsize - 4:o + bsize].tobytes(), "little")
+        if isize:
+            out.append((o + 12 + xlen, bsize - 12 - xlen - 8, isize))
+        o += bsize
+    return raw, out
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--pairs", type=int, default=1 << 20, help="pairs per generated chunk of the sample")
+    ap.add_argument("--levels", type=int, default=5_000_000, help="levels of the Graph M world (bench.py --levels)")
+    ap.add_argument("--min-inflated-gb", type=float, default=1.0, help="chunks are added until the BAM holds this much inflated")
+    ap.add_argument("--threads", type=int, default=0, help="decoder threads of both paths (0 = the decoder's default)")
+    ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--chunk-mb", type=int, default=0, help="compressed MiB staged per launch (0 = the library's default)")
+    ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--bam", default="", help="use this BAM (reference names PRG_<n>) instead of generating one; needs --levels of the world it was made from")
+    ap.add_argument("--no-gpu", action="store_true", help="host engine only (a box without a GPU: checks the generator and the host figures)")
+    args = ap.parse_args()
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("hla_la_amd", os.path.join(ROOT, "hla-la_amd", "__init__.py"), submodule_search_locations=[os.path.join(ROOT, "hla-la_amd")])
+    P = importlib.util.module_from_spec(spec); sys.modules["hla_la_amd"] = P; spec.loader.exec_module(P)
+    from tools import graphm_dir, synth
+    lib = P.load_library()
+    lib.hlala_bam_inflate_engine.restype = __import__("ctypes").c_char_p
+    t0 = time.time()
+    w = synth.make_world_m(seed=2, n_levels=args.levels)
+    clen = np.diff(w["contigs"]["contig_off"]); names = graphm_dir.ref_names(w)
+    intervals = [(nm, 0, int(clen[i]) - 1, i) for i, nm in enumerate(names)]
+    tmp = None
+    bam = args.bam
+    if not bam:
+        tmp = tempfile.mkdtemp(prefix="hlala_inflate_rate_"); bam = os.path.join(tmp, "sample.bam")
+        bw = synth.BamWriter(bam, [(nm, int(clen[i])) for i, nm in enumerate(names)], threads=0, level=1)
+        k = 0; inflated = 0
+        while inflated < args.min_inflated_gb * 1e9:
+            bk = synth.make_batch_m(w, args.pairs, seed=3000 + k, frac_gene=0.04); nm, _ = synth.scrambled_names(k, args.pairs)
+            bw.append_batch(bk, nm, order="coordinate")
+            # (bytes of the records just written: 36 fixed + name + NUL + the AS tag per alignment, the CIGARs, bases and qualities of the primaries)
+            inflated += bk["n_chains"] * (36 + nm.shape[1] + 1 + 7) + 4 * len(bk["cigar"]) + int(1.5 * len(bk["read_bases"]))
+            del bk
+            k += 1
+        bw.close()
+    raw, blocks = bgzf_blocks(bam)
+    n_inflated = sum(b[2] for b in blocks); n_comp = sum(b[1] for b in blocks)
+    print("sample: %s, %.3f GB of BAM, %d BGZF blocks, %.3f GB inflated (ratio %.2f); world and sample made in %.1f s" % (
+        "generated" if tmp else bam, raw.size / 1e9, len(blocks), n_inflated / 1e9, n_inflated / max(1, n_comp), time.time() - t0))
+    if n_inflated < args.min_inflated_gb * 1e9:
+        print("WARNING: the file holds %.3f GB inflated, less than the %.3f GB asked for (--min-inflated-gb)" % (n_inflated / 1e9, args.min_inflated_gb))
+    print("host engine: %s; decoder threads: %s" % (lib.hlala_bam_inflate_engine().decode(), args.threads or "default"))
+    inf = None if args.no_gpu else P.Inflater(lib, device=args.device, chunk_bytes=args.chunk_mb << 20)
+    keys = ("index", "inflate", "parse", "group", "name_sort", "layout")
+
+    def run(label, opener, timed):
+        t = time.time(); S = opener(); wall = time.time() - t
+        tm = S.timing(); cnt = S.inflate_counts(); units = S.n_units; S.close()
+        if timed:
+            print("%-5s wall %.3f s  %s  threads %d  units %d  blocks gpu/retried/host %d/%d/%d" % (
+                label, wall, "  ".join("%s %.3f" % (k, tm[k]) for k in keys), tm["threads"], units, cnt[0], cnt[1], cnt[2]))
+        return tm["inflate"]
+    host = lambda: P.bam_open_seeds(lib, bam, intervals, threads=args.threads, flags=P.SEEDS_PACKED)                 # noqa: E731
+    gpu = (lambda: inf.bam_open_seeds(bam, intervals, threads=args.threads, flags=P.SEEDS_PACKED)) if inf else None      # noqa: E731
+    res = {"host": [], "gpu": []}
+    for i in range(args.runs + 1):
+        res["host"].append(run("host", host, i > 0))
+        if gpu:
+            res["gpu"].append(run("gpu", gpu, i > 0))
+    for k in ("host", "gpu"):
+        if len(res[k]) > 1:
+            v = res[k][1:]
+            print("inflate phase, %s: median %.3f s (%.2f GB/s inflated) of %s" % (k, float(np.median(v)), n_inflated / 1e9 / float(np.median(v)), ["%.3f" % x for x in v]))
+    if inf:
+        # the kernel and its copies alone: every block of the file in one call, into one pageable buffer
+        out = np.empty(n_inflated, np.uint8); desc = []; u = 0
+        for off, clen_, isize in blocks:
+            desc.append((off, clen_, isize, u)); u += isize
+        for i in range(2):
+            status, st = inf.inflate(raw, desc, out)
+        assert int((status != 0).sum()) == 0 and st.n_rejected == 0, "the GPU rejected blocks of a valid file"
+        print("hlala_bgzf_inflate, all blocks in one call (second call): upload %.1f ms, kernel %.1f ms, download %.1f ms (device times summed over the chunks; they overlap), "
+              "wall %.1f ms: %.0f blocks/s, %.2f GB/s inflated" % (st.ms_h2d, st.ms_kernel, st.ms_d2h, st.ms_wall, st.n_blocks / (st.ms_wall / 1e3), n_inflated / 1e9 / (st.ms_wall / 1e3)))
+        print("kernel alone: %.2f GB/s inflated; download alone: %.2f GB/s" % (n_inflated / 1e9 / (st.ms_kernel / 1e3), n_inflated / 1e9 / max(1e-9, st.ms_d2h / 1e3)))
+        inf.close()
+    if tmp:
+        import shutil
+        shutil.rmtree(tmp, ignore_errors=True)
+
+
+if __name__ == "__main__":
+    main()
