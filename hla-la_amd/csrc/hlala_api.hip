@@ -1912,20 +1912,20 @@ extern "C" int hlala_kat_phred(hlala_ctx* c, int n, const double* p_correct, uin
 static int call_locus_impl(hlala_ctx* c, int32_t C, const double* pairLL, const double* misAvg, const double* misMin, const double* dLLin, const double* dMAin, const double* dMMin,
                           int32_t* order, double* p_normalized, double* cluster_marginal, hlala_call_out* out)
 {
-    if(!c || C < 1 || (!dLLin && (!pairLL || !misAvg || !misMin)) || !out) return HLALA_E_ARG;
+    if(!c || C < 1 || !pairLL || !misAvg || (!dLLin && !misMin) || !out) return HLALA_E_ARG;
     if(C > 46000) { c->err = "hlala_call_locus: more than 46000 clusters (pair index exceeds 31 bits)"; return HLALA_E_CAPACITY; }
     const long long nP = (long long)C * (C + 1) / 2, n2 = 2 * nP;
     std::vector<void*> tmp;
     auto done = [&](int r_) { for(void* p : tmp) pool_release(c, p); return r_; };       // scratch is parked for the next locus
     int rc = 0;
     double *dLL = nullptr, *dMA = nullptr, *dMM = nullptr, *dP = nullptr, *dPart = nullptr, *dScal = nullptr, *dVal = nullptr, *dVal2 = nullptr, *dMarg = nullptr;
-    u64 *dK1 = nullptr, *dK2 = nullptr, *dCK = nullptr, *dCK2 = nullptr; int *dI1 = nullptr, *dI2 = nullptr, *dC1 = nullptr, *dC2 = nullptr, *dTies = nullptr;
+    u64 *dCK = nullptr, *dCK2 = nullptr; int *dI1 = nullptr, *dC1 = nullptr, *dC2 = nullptr, *dTies = nullptr;
     long long* dPidx = nullptr; hlala_call_out* dOut = nullptr;
     const int NB = 1024;
     if(dLLin) { dLL = const_cast<double*>(dLLin); dMA = const_cast<double*>(dMAin); dMM = const_cast<double*>(dMMin); }
     else if((rc = dev_upload(c, tmp, pairLL, (size_t)nP, &dLL)) || (rc = dev_upload(c, tmp, misAvg, (size_t)nP, &dMA)) || (rc = dev_upload(c, tmp, misMin, (size_t)nP, &dMM))) return done(rc);
     if((rc = dev_alloc(c, tmp, (size_t)nP, &dP)) || (rc = dev_alloc(c, tmp, (size_t)NB, &dPart)) || (rc = dev_alloc(c, tmp, (size_t)NB, &dPidx)) || (rc = dev_alloc(c, tmp, 4, &dScal)) ||
-       (rc = dev_alloc(c, tmp, (size_t)nP, &dK1)) || (rc = dev_alloc(c, tmp, (size_t)nP, &dK2)) || (rc = dev_alloc(c, tmp, (size_t)nP, &dI1)) || (rc = dev_alloc(c, tmp, (size_t)nP, &dI2)) ||
+       (rc = dev_alloc(c, tmp, (size_t)nP, &dI1)) ||
        (rc = dev_alloc(c, tmp, (size_t)nP, &dC1)) || (rc = dev_alloc(c, tmp, (size_t)nP, &dC2)) || (rc = dev_alloc(c, tmp, (size_t)n2, &dCK)) || (rc = dev_alloc(c, tmp, (size_t)n2, &dCK2)) ||
        (rc = dev_alloc(c, tmp, (size_t)n2, &dVal)) || (rc = dev_alloc(c, tmp, (size_t)n2, &dVal2)) || (rc = dev_alloc(c, tmp, (size_t)C, &dMarg)) || (rc = dev_alloc(c, tmp, 1, &dTies, true)) ||
        (rc = dev_alloc(c, tmp, 1, &dOut))) return done(rc);
@@ -1937,16 +1937,30 @@ static int call_locus_impl(hlala_ctx* c, int32_t C, const double* pairLL, const 
     hipLaunchKernelGGL(k_call_p, dim3(NB), dim3(T), 0, st, dLL, nP, dScal, dP, dPart);
     hipLaunchKernelGGL(k_call_psum_final, dim3(1), dim3(1), 0, st, dPart, NB, dScal + 1);
     hipLaunchKernelGGL(k_call_normalize, dim3(gP), dim3(T), 0, st, dP, nP, dScal + 1);
-    // order: stable sort by Mism_avg ascending, then stable sort by LL descending
-    hipLaunchKernelGGL(k_call_keys_mism, dim3(gP), dim3(T), 0, st, dMA, nP, dK1, dI1);
-    size_t cubBytes = 0, cubBytes2 = 0;
-    HIP_TRY_F(c, hipcub::DeviceRadixSort::SortPairs(nullptr, cubBytes, dK1, dK2, dI1, dI2, (int)nP, 0, 64, st), done);
-    HIP_TRY_F(c, hipcub::DeviceRadixSort::SortPairs(nullptr, cubBytes2, dCK, dCK2, dVal, dVal2, (int)n2, 0, 64, st), done);
-    if(cubBytes2 > cubBytes) cubBytes = cubBytes2;
+    // order: the reference's own two library calls -- std::sort with its comparator, then std::reverse (hla/HLATyper.cpp:2381-2403) -- on the HOST.  Pairs equal in both
+    // keys come out in the order libstdc++'s std::sort leaves them in, which depends on every comparison it makes on the way over the whole sequence: only the same routine
+    // over the same sequence reproduces it, and R1_PP_<locus>_pairs.txt prints that order (through the accumulation order of the marginals below, the call on exactly tied
+    // marginals depends on it too).  A stable device sort agrees with the reference everywhere except inside such groups, which is where the reference pin of the typer found
+    // it (tests/test_gpu_reference_pin_typer.py).  The tables the sort reads are the caller's (hlala_call_locus: it then runs beside the kernels queued above) or the host
+    // copies hlala_type_locus has queued; those have to have arrived, so that path drains the stream first and nothing overlaps.  One thread, nP log nP comparisons
+    // (DESIGN.md section D-H has the measured time).  The elements carry their keys: std::sort's sequence of comparisons and moves does not depend on the element type, so
+    // the permutation is the one the reference's sort of bare indices produces, at half the time of looking the keys up through the index; 24 bytes per pair of host memory.
+    if(dLLin) HIP_TRY_F(c, hipStreamSynchronize(st), done);
+    struct Keyed { double ll, ma; int32_t i; };
+    std::vector<Keyed> keyed; std::vector<int32_t> hOrder;
+    try { keyed.resize((size_t)nP); hOrder.resize((size_t)nP); } catch(const std::exception&) { c->err = "hlala_call_locus: no host memory for the order of the pair table"; return done(HLALA_E_CAPACITY); }
+    for(long long i = 0; i < nP; i++) keyed[(size_t)i] = Keyed{pairLL[i], misAvg[i], (int32_t)i};
+    std::sort(keyed.begin(), keyed.end(), [](const Keyed& a, const Keyed& b) {
+        if(a.ll == b.ll) return (b.ma < a.ma);
+        else return (a.ll < b.ll);
+    });
+    std::reverse(keyed.begin(), keyed.end());
+    for(long long i = 0; i < nP; i++) hOrder[(size_t)i] = keyed[(size_t)i].i;
+    HIP_TRY_F(c, hipMemcpyAsync(dI1, hOrder.data(), (size_t)nP * sizeof(int32_t), hipMemcpyHostToDevice, st), done);
+    HIP_TRY_F(c, hipStreamSynchronize(st), done);                                                                            // (hOrder is a local)
+    size_t cubBytes = 0;
+    HIP_TRY_F(c, hipcub::DeviceRadixSort::SortPairs(nullptr, cubBytes, dCK, dCK2, dVal, dVal2, (int)n2, 0, 64, st), done);
     char* dCub = nullptr; if((rc = dev_alloc(c, tmp, cubBytes ? cubBytes : 1, &dCub))) return done(rc);
-    HIP_TRY_F(c, hipcub::DeviceRadixSort::SortPairs(dCub, cubBytes, dK1, dK2, dI1, dI2, (int)nP, 0, 64, st), done);
-    hipLaunchKernelGGL(k_call_keys_ll, dim3(gP), dim3(T), 0, st, dLL, dI2, nP, dK1);
-    HIP_TRY_F(c, hipcub::DeviceRadixSort::SortPairs(dCub, cubBytes, dK1, dK2, dI2, dI1, (int)nP, 0, 64, st), done);       // dI1 = order
     // marginals in the reference's accumulation order
     hipLaunchKernelGGL(k_call_clusters, dim3((unsigned)C), dim3(128), 0, st, (int)C, dC1, dC2);
     hipLaunchKernelGGL(k_call_contrib, dim3(gP), dim3(T), 0, st, dI1, dC1, dC2, dP, nP, dCK, dVal, dTies, dLL, dMA);
@@ -1987,7 +2001,7 @@ extern "C" int hlala_type_locus(hlala_ctx* c, const hlala_exon_in* in, double* L
         if((rc = dev_alloc(c, keep, 1, &dLL)) || (rc = dev_alloc(c, keep, 1, &dM))) return done(rc);
     }
     if((rc = pair_loglik_impl(c, nullptr, nullptr, dLL, dM, C, R, pairLL, misAvg, misMin, &keep, &dP, &dA, &dMn))) return done(rc);
-    rc = call_locus_impl(c, C, nullptr, nullptr, nullptr, dP, dA, dMn, order, p_normalized, cluster_marginal, out);       // (ends synchronised)
+    rc = call_locus_impl(c, C, pairLL, misAvg, misMin, dP, dA, dMn, order, p_normalized, cluster_marginal, out);          // (host copies for the sort of the order; ends synchronised)
     return done(rc);
 }
 

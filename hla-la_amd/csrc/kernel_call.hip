@@ -1,7 +1,7 @@
 // kernel_call.hip -- the call of one locus from the all-pairs table (hla/HLATyper.cpp:2366-2541) on gfx950.
 //
-//   order        : pair indices by LL descending, Mism_avg ascending = two stable LSD radix sorts (hipCUB's device radix sort:
-//                  a plain library sort; keys are the order-preserving integer images of the doubles)
+//   order        : pair indices by LL descending, Mism_avg ascending: NOT here.  The reference's order among pairs equal in both keys is what std::sort + std::reverse
+//                  leave behind, and only that routine reproduces it: the host runs it (hlala_api.hip: call_locus_impl) and uploads the order
 //   P            : exp(LL - max) / sum; the sum is a fixed-shape tree over blocks (deterministic, not the reference's serial order:
 //                  P agrees to ~1e-13 relative, the integer decisions below do not depend on it beyond that)
 //   marginals    : the reference accumulates clusterI_overAllPairs while walking `order`; here every (cluster, rank, P) contribution is
@@ -14,13 +14,6 @@
 #include "../../include/hlala_gpu.h"
 
 namespace hlala {
-
-// order-preserving map double -> u64 (ascending)
-__device__ __forceinline__ u64 dbl_key(double d)
-{
-    u64 b = (u64)__double_as_longlong(d);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
 
 __device__ __forceinline__ long long tri_index(int c1, int c2, int C) { return (long long)c1 * C - (long long)c1 * (c1 - 1) / 2 + (c2 - c1); }
 
@@ -49,18 +42,6 @@ __global__ void k_call_max_final(const double* __restrict__ pmax, const long lon
     double m = -INFINITY; long long mi = 0x7FFFFFFFFFFFFFFFll;
     for(int i = 0; i < nb; i++) if(pmax[i] > m || (pmax[i] == m && pidx[i] < mi)) { m = pmax[i]; mi = pidx[i]; }
     *outMax = m; *outIdx = mi;
-}
-
-__global__ void k_call_keys_mism(const double* __restrict__ MA, long long n, u64* __restrict__ key, int* __restrict__ idx)
-{
-    long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if(i < n) { key[i] = dbl_key(MA[i]); idx[i] = (int)i; }
-}
-// second pass: descending LL of the already mism-sorted indices
-__global__ void k_call_keys_ll(const double* __restrict__ LL, const int* __restrict__ idx, long long n, u64* __restrict__ key)
-{
-    long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if(i < n) key[i] = ~dbl_key(LL[idx[i]]);
 }
 
 // P = exp(LL - max); per-block sums in a fixed tree

@@ -623,8 +623,10 @@ int  hlala_filter_positions(const hlala_exon_positions_out* pos, const hlala_fil
                             uint8_t* read_ignored /* [n_reads] or NULL */, hlala_filter_stats* stats /* or NULL */);
 
 /* The call of one locus from the all-pairs table (hla/HLATyper.cpp:2366-2541).  Pair (c1 <= c2) sits at the index
- * hlala_pair_loglik uses.  order = pair indices sorted by LL descending, Mism_avg ascending (std::sort + std::reverse, :2381-2403;
- * the order among pairs equal in both keys is unspecified in the reference too -- n_sort_ties counts adjacent equal keys);
+ * hlala_pair_loglik uses.  order = pair indices sorted by LL descending, Mism_avg ascending (std::sort + std::reverse, :2381-2403).
+ * Among pairs equal in both keys the C++ standard leaves the order open, but the reference's files print the one its library produces:
+ * the same two library calls run on the host over the same sequence, so that `order` is the reference's there too (n_sort_ties counts
+ * adjacent equal keys);
  * p_normalized = exp(LL - max) / sum (:2411-2448); cluster_marginal = clusterI_overAllPairs, accumulated in `order` (:2459-2486);
  * first = first maximum of the marginals in cluster order (findIntMapMax, Utilities.cpp:257-272, :2490); second = among the pairs that
  * contain `first` the maximum P, ties resolved by the smallest Mism_min, then the smallest cluster (:2498-2533). */

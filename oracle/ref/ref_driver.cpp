@@ -5,7 +5,9 @@
  * it and copies its outputs.  Three short passages of processBAM.cpp that sit inside non-static members are followed line by
  * line, each line citing the one it follows: the gap filling at the head of PRGContigAlignment2Seed (only for the optional
  * intermediate stages of ref_project_chains), the pairing double loop and the selection of alignOneReadPair (ref_pair_chains).
- * Everything they call is the reference's.
+ * Everything they call is the reference's.  The typer (hla::HLATyper) is reached the same way: ref_typer_infer calls HLATypeInference
+ * itself, ref_typer_exon_positions follows the two read loops at its head (hla/HLATyper.cpp:1386-1495) line by line around the
+ * reference's protected members, ref_typer_include is its intervalOverlapsWithGenes.
  *
  * Order is pointer order in the reference (std::set<Node*>, std::set<Edge*>, std::map<Node*, ...>): all nodes live in
  * one array and all edges in one array, in the order of the graph description, so that pointer order is index order
@@ -19,8 +21,13 @@
 #include "Graph/Graph.h"
 #include "Graph/Node.h"
 #include "Graph/Edge.h"
+#include "hla/HLATyper.h"
+#include "hla/oneExonPosition.h"
 
 #include "hlala_gpu.h"
+
+#include <omp.h>
+#include <unistd.h>
 
 #include <algorithm>
 #include <cmath>
@@ -29,6 +36,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
+#include <map>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -582,5 +590,242 @@ int ref_mapq_unpaired(ref_handle* h, const hlala_seeds_in* in, const double* ll,
         if(c != in->n_chains) throw std::runtime_error("chains are not grouped by read");
         return 0;
     });
+}
+
+/* ------------------------------------------------------------------ the typer: hla::HLATyper (hla/HLATyper.cpp)
+ *
+ * Alignments are handed over as a hlala_seeds_in whose "chains" are the selected alignments: row 2u + m for mate m of unit u of a paired
+ * batch, row u for read u of an unpaired one; chain_read[c] = c, chain_reverse[c] the strand of the selected alignment, the reads as a
+ * batch carries them (the bases of the primary alignment in alignment orientation).  Beside it: mapQ_perPosition packed like the columns,
+ * verboseSeedChain::mapQ per row, verboseSeedChainPair::mapQ per unit, the strand of the primary alignment per row (the raw read is
+ * inverted when it is reverse, mapper/processBAM.cpp:2138-2158, :2314-2325, :2452-2475) and the read names. */
+typedef struct {
+    int32_t n_units, paired;
+    const hlala_seeds_in* rows;
+    const uint8_t* col_mapq;          /* [col_off[n_rows]] */
+    const double*  row_mapq;          /* [n_rows] */
+    const double*  unit_mapq;         /* [n_units], paired only */
+    const uint8_t* primary_reverse;   /* [n_rows] */
+    const int32_t* name_off;          /* [n_rows + 1] into names */
+    const char*    names;
+} ref_typer_reads;
+
+namespace {
+struct TyperAccess : hla::HLATyper {
+    using hla::HLATyper::HLATyper;
+    using hla::HLATyper::oneReadAlignment_2_exonPositions_paired;
+    using hla::HLATyper::oneReadAlignment_2_exonPositions_unpaired;
+    using hla::HLATyper::alignmentFractionOK;
+    using hla::HLATyper::alignmentWeightedOKFraction;
+    using hla::HLATyper::removeDoublePositionsFromRead;
+};
+struct TyperReads {
+    std::vector<mapper::reads::oneReadPair> rawPaired; std::vector<mapper::reads::verboseSeedChainPair> alignedPaired;
+    std::vector<mapper::reads::oneRead> rawUnpaired; std::vector<mapper::reads::verboseSeedChain> alignedUnpaired;
+};
+mapper::reads::oneRead typer_raw_read(const ref_typer_reads* in, int row)
+{
+    const hlala_seeds_in* s = in->rows;
+    std::string name(in->names + in->name_off[row], (size_t)(in->name_off[row + 1] - in->name_off[row]));
+    std::string seq((const char*)s->read_bases + s->read_off[row], (size_t)(s->read_off[row + 1] - s->read_off[row]));
+    std::string qual((const char*)s->read_quals + s->read_off[row], (size_t)(s->read_off[row + 1] - s->read_off[row]));
+    mapper::reads::oneRead r(name, seq, qual);
+    if(in->primary_reverse[row]) r.invert();
+    return r;
+}
+mapper::reads::verboseSeedChain typer_alignment(const ref_handle* h, const ref_typer_reads* in, int row, bool fromFirstRead)
+{
+    const hlala_seeds_in* s = in->rows;
+    if(s->chain_read[row] != row) throw std::runtime_error("typer rows: chain_read[c] != c");
+    mapper::reads::verboseSeedChain c = chain_from_columns(h, s, row);
+    c.fromFirstRead = fromFirstRead;
+    c.mapQ = in->row_mapq[row];
+    c.mapQ_perPosition.assign((const char*)in->col_mapq + s->col_off[row], (size_t)(s->col_off[row + 1] - s->col_off[row]));
+    c.readID = std::string(in->names + in->name_off[row], (size_t)(in->name_off[row + 1] - in->name_off[row]));
+    return c;
+}
+void typer_build_reads(const ref_handle* h, const ref_typer_reads* in, TyperReads& R)
+{
+    const int n_rows = in->paired ? 2 * in->n_units : in->n_units;
+    if(in->rows->n_chains != n_rows || in->rows->n_reads != n_rows) throw std::runtime_error("typer rows: one row per mate expected");
+    for(int u = 0; u < in->n_units; u++) {
+        if(in->paired) {
+            mapper::reads::verboseSeedChainPair P;
+            P.chains.first = typer_alignment(h, in, 2 * u, true); P.chains.second = typer_alignment(h, in, 2 * u + 1, false);     /* processBAM.cpp:3545-3546 */
+            P.mapQ = in->unit_mapq[u]; P.readID = P.chains.first.readID;
+            R.alignedPaired.push_back(P);
+            R.rawPaired.push_back(mapper::reads::oneReadPair(typer_raw_read(in, 2 * u), typer_raw_read(in, 2 * u + 1), 0));
+        } else {
+            R.alignedUnpaired.push_back(typer_alignment(h, in, u, true));                                                         /* processBAM.cpp:3774 */
+            R.rawUnpaired.push_back(typer_raw_read(in, u));
+        }
+    }
+}
+}  // namespace
+
+/* HLATyper.cpp:28, :30: the thresholds of the pair test are globals of the reference */
+extern double min_bothReads_weightedCharactersOK;
+extern double minimumMappingQuality;
+
+struct ref_typer { ref_handle* h = nullptr; TyperAccess* T = nullptr; };
+
+/* HLATyper(Graph*, graphDir, ""): reads graph_dir/PRG/segments.txt and the segment files; with an empty quality-matrix name no read simulator is built */
+ref_typer* ref_typer_create(ref_handle* h, const char* graph_dir)
+{
+    ref_typer* t = new ref_typer(); t->h = h;
+    int rc = guarded([&]() -> int { t->T = new TyperAccess(h->g, std::string(graph_dir), std::string("")); return 0; });
+    if(rc != 0) { delete t; return nullptr; }
+    return t;
+}
+
+void ref_typer_destroy(ref_typer* t)
+{
+    if(!t) return;
+    delete t->T; delete t;
+}
+
+/* HLATyper::intervalOverlapsWithGenes for n (first, last) level pairs: one call of the includeInHLA decision (processBAM.cpp:2114-2133, :2298-2312, :2428-2448) */
+int ref_typer_include(ref_typer* t, int n, const int32_t* first, const int32_t* last, uint8_t* overlaps)
+{
+    return guarded([&]() -> int {
+        for(int i = 0; i < n; i++) overlaps[i] = t->T->intervalOverlapsWithGenes(first[i], last[i]) ? 1 : 0;
+        return 0;
+    });
+}
+
+/* The two read loops at the head of the per-locus part of HLATypeInference (:1386-1464 paired, :1467-1495 unpaired) around the reference's
+ * oneReadAlignment_2_exonPositions_paired / _unpaired, alignmentWeightedOKFraction, alignedReadPair_strandsValid / _pairsDistanceInGraphLevels and
+ * removeDoublePositionsFromRead.  `locus` gives combined_exon_sequences_graphLevels_min / _max and graphLevel_2_exonPosition (level_to_exon), the
+ * insert size and, for unpaired batches, minAlignmentLength_unpaired (a local constant of the reference, :1032); the two thresholds of the pair
+ * test are the reference's globals.  Output in the layout of hlala_exon_positions: one entry per element of exonPositions_fromReads.  The
+ * per-mate arrays are filled from the oneExonPosition fields of the entry's positions (thisRead_* of the position's own mate, pairedRead_* of the
+ * other); a field no position of the entry witnesses stays at -1 (read_reverse: 255), and two positions of an entry that disagree about a
+ * per-mate field fail the call.  pos_mapq_p (may be NULL) takes oneExonPosition::mapQ_position. */
+int ref_typer_exon_positions(ref_typer* t, const ref_typer_reads* in, const hlala_locus_desc* locus, hlala_exon_positions_out* o, double* pos_mapq_p)
+{
+    return guarded([&]() -> int {
+        using hla::oneExonPosition;
+        TyperReads R; typer_build_reads(t->h, in, R);
+        const std::vector<mapper::reads::verboseSeedChainPair>& alignments_paired = R.alignedPaired;
+        const std::vector<mapper::reads::verboseSeedChain>& alignments_unpaired = R.alignedUnpaired;
+        const std::vector<mapper::reads::oneReadPair>& alignments_originalReads_paired = R.rawPaired;
+        const std::vector<mapper::reads::oneRead>& alignments_originalReads_unpaired = R.rawUnpaired;
+        const double insertSize_mean = locus->insert_mean, insertSize_sd = locus->insert_sd;
+        const int minAlignmentLength_unpaired = locus->min_alignment_columns;
+        int combined_exon_sequences_graphLevels_min = locus->level_min, combined_exon_sequences_graphLevels_max = locus->level_max;
+        std::map<int, unsigned int> graphLevel_2_exonPosition;
+        for(int l = locus->level_min; l <= locus->level_max; l++) if(locus->level_to_exon[l - locus->level_min] >= 0) graphLevel_2_exonPosition[l] = (unsigned int)locus->level_to_exon[l - locus->level_min];
+
+        std::vector<std::vector<oneExonPosition>> exonPositions_fromReads; std::vector<int> entry_unit;
+        unsigned int readPairs_OK = 0, readPairs_broken = 0;
+        for(unsigned int readPairI = 0; readPairI < alignments_paired.size(); readPairI++)                                     /* :1386 */
+        {
+            const mapper::reads::oneReadPair& originalReadPair = alignments_originalReads_paired.at(readPairI);
+            const mapper::reads::verboseSeedChainPair& alignedReadPair = alignments_paired.at(readPairI);
+            std::vector<oneExonPosition> read1_exonPositions, read2_exonPositions;
+            t->T->oneReadAlignment_2_exonPositions_paired(alignedReadPair.chains.first, originalReadPair.reads.first, read1_exonPositions, alignedReadPair.chains.second, originalReadPair.reads.second, 1, combined_exon_sequences_graphLevels_min, combined_exon_sequences_graphLevels_max, graphLevel_2_exonPosition);   /* :1394 */
+            t->T->oneReadAlignment_2_exonPositions_paired(alignedReadPair.chains.second, originalReadPair.reads.second, read2_exonPositions, alignedReadPair.chains.first, originalReadPair.reads.first, 2, combined_exon_sequences_graphLevels_min, combined_exon_sequences_graphLevels_max, graphLevel_2_exonPosition);   /* :1395 */
+            if(!((alignedReadPair.chains.first.mapQ >= 0) && (alignedReadPair.chains.first.mapQ <= 1))) throw std::runtime_error("chains.first.mapQ outside [0, 1]");   /* :1403 */
+            double mapQ_thisAlignment = alignedReadPair.chains.first.mapQ;                                                     /* :1404 */
+            if(mapper::aligner::alignerBase::alignedReadPair_strandsValid(alignedReadPair) &&
+               (abs(mapper::aligner::alignerBase::alignedReadPair_pairsDistanceInGraphLevels(alignedReadPair) - insertSize_mean) <= (5 * insertSize_sd)) &&
+               (mapQ_thisAlignment >= minimumMappingQuality) &&
+               ((TyperAccess::alignmentWeightedOKFraction(originalReadPair.reads.first, alignedReadPair.chains.first) >= min_bothReads_weightedCharactersOK) && (TyperAccess::alignmentWeightedOKFraction(originalReadPair.reads.second, alignedReadPair.chains.second) >= min_bothReads_weightedCharactersOK)))   /* :1405-1410 */
+            {
+                std::vector<oneExonPosition> thisRead_exonPositions = read1_exonPositions;                                     /* :1415 */
+                thisRead_exonPositions.insert(thisRead_exonPositions.end(), read2_exonPositions.begin(), read2_exonPositions.end());   /* :1416 */
+                if(thisRead_exonPositions.size() > 0)                                                                          /* :1418 */
+                {
+                    thisRead_exonPositions = TyperAccess::removeDoublePositionsFromRead(thisRead_exonPositions);               /* :1420 */
+                    exonPositions_fromReads.push_back(thisRead_exonPositions); entry_unit.push_back((int)readPairI);           /* :1421 */
+                }
+                readPairs_OK++;                                                                                                /* :1424 */
+            }
+            else
+                readPairs_broken++;                                                                                            /* :1462 */
+        }
+        for(unsigned int readI = 0; readI < alignments_unpaired.size(); readI++)                                               /* :1467 */
+        {
+            const mapper::reads::oneRead& originalRead = alignments_originalReads_unpaired.at(readI);
+            const mapper::reads::verboseSeedChain& alignedRead = alignments_unpaired.at(readI);
+            std::vector<oneExonPosition> read_exonPositions;
+            t->T->oneReadAlignment_2_exonPositions_unpaired(alignedRead, originalRead, read_exonPositions, combined_exon_sequences_graphLevels_min, combined_exon_sequences_graphLevels_max, graphLevel_2_exonPosition);   /* :1473 */
+            double mapQ_thisAlignment = alignedRead.mapQ;                                                                      /* :1475 */
+            if((mapQ_thisAlignment >= minimumMappingQuality) && ((int)alignedRead.graph_aligned.size() >= minAlignmentLength_unpaired))   /* :1476 */
+            {
+                if(read_exonPositions.size() > 0) { exonPositions_fromReads.push_back(read_exonPositions); entry_unit.push_back((int)readI); }   /* :1481-1485 */
+                readPairs_OK++;                                                                                                /* :1486 */
+            }
+            else
+                readPairs_broken++;                                                                                            /* :1493 */
+        }
+
+        /* ---- copy out */
+        o->n_pairs_ok = (int)readPairs_OK; o->n_pairs_broken = (int)readPairs_broken;
+        size_t nPos = 0, nChars = 0;
+        for(const auto& e : exonPositions_fromReads) { nPos += e.size(); for(const auto& p : e) nChars += p.genotype.size(); }
+        o->n_reads = (int)exonPositions_fromReads.size(); o->n_pos = (int)nPos; o->n_chars = (int)nChars;
+        if(o->n_reads > o->cap_reads || o->n_pos > o->cap_pos || o->n_chars > o->cap_chars) throw std::runtime_error("exon positions: output capacity too small");
+        auto witness = [](double& slot, double v, const char* what) {
+            if(slot == -1) slot = v;
+            else if(!(slot == v)) throw std::runtime_error(std::string("positions of one entry disagree about ") + what);
+        };
+        int q = 0, ch = 0;
+        for(size_t i = 0; i < exonPositions_fromReads.size(); i++) {
+            o->read_pair[i] = entry_unit[i]; o->pos_off[i] = q;
+            double wok[2] = {-1, -1}, fok[2] = {-1, -1}, mq[2] = {-1, -1}, rev[2] = {-1, -1}, cng[2] = {-1, -1}, dist = -1;
+            bool have_dist = false;
+            for(const oneExonPosition& p : exonPositions_fromReads[i]) {
+                const int m = p.fromFirstRead ? 0 : 1;
+                if(!in->paired && m != 0) throw std::runtime_error("an unpaired position that is not fromFirstRead");
+                witness(wok[m], p.thisRead_WeightedCharactersOK, "thisRead_WeightedCharactersOK"); witness(fok[m], p.thisRead_fractionOK, "thisRead_fractionOK");
+                if(in->paired) { witness(wok[1 - m], p.pairedRead_WeightedCharactersOK, "pairedRead_WeightedCharactersOK"); witness(fok[1 - m], p.pairedRead_fractionOK, "pairedRead_fractionOK"); }
+                else if(!(p.pairedRead_WeightedCharactersOK == -1 && p.pairedRead_fractionOK == -1)) throw std::runtime_error("pairedRead_* of an unpaired position is not -1");
+                if(!(p.mapQ == p.mapQ_genomic)) throw std::runtime_error("mapQ != mapQ_genomic");
+                witness(mq[m], p.mapQ, "mapQ"); witness(rev[m], p.reverse ? 1 : 0, "reverse"); witness(cng[m], p.alignmentColumnsWithAtLeastOneNonGap, "alignmentColumnsWithAtLeastOneNonGap");
+                if(have_dist && !(dist == p.pairs_strands_distance)) throw std::runtime_error("positions of one entry disagree about pairs_strands_distance");
+                dist = p.pairs_strands_distance; have_dist = true;
+                if(in->paired && !p.pairs_strands_OK) throw std::runtime_error("a position of a pair whose strands are not valid");
+                o->pos_exon[q] = (int32_t)p.positionInExon; o->pos_level[q] = p.graphLevel; o->pos_mate[q] = (uint8_t)(m + 1);
+                o->pos_novel_gap[q] = p.runningNovelGapEitherDirection;
+                if(pos_mapq_p) pos_mapq_p[q] = p.mapQ_position;
+                o->pos_mapq[q] = 0;                                /* the Phred character is an input of the caller; the reference keeps its translation (pos_mapq_p) */
+                o->geno_off[q] = ch;
+                if(!(p.genotype == "_" ? p.qualities.size() == 0 : p.qualities.size() == p.genotype.size())) throw std::runtime_error("genotype and qualities of unequal length");
+                for(size_t k = 0; k < p.genotype.size(); k++) { o->geno_chars[ch] = (uint8_t)p.genotype[k]; o->qual_chars[ch] = k < p.qualities.size() ? (uint8_t)p.qualities[k] : 0; ch++; }
+                q++;
+            }
+            if(dist != (double)(int32_t)dist) throw std::runtime_error("pairs_strands_distance is not an integer");
+            for(int m = 0; m < 2; m++) {
+                o->read_weighted_ok[2 * i + m] = wok[m]; o->read_fraction_ok[2 * i + m] = fok[m]; o->read_cols_nongap[2 * i + m] = (int32_t)cng[m];
+                if(o->read_mapq) o->read_mapq[2 * i + m] = mq[m];
+                if(o->read_reverse) o->read_reverse[2 * i + m] = rev[m] < 0 ? 255 : (uint8_t)rev[m];
+            }
+            o->read_distance[i] = (int32_t)dist;
+        }
+        o->pos_off[exonPositions_fromReads.size()] = q; o->geno_off[q] = ch;
+        return 0;
+    });
+}
+
+/* HLATyper::HLATypeInference on the alignments of `in`, writing its files into out_dir.  read_G_alleles opens "hla_nom_g.txt" in the
+ * current directory: the call runs with g_dir (a directory that holds that file) as the working directory and restores the old one.
+ * The all-pairs loop appends per-thread results inside a critical section, so with more than one OpenMP thread the order of
+ * LLs_completeReads -- which findVectorMax, the sort on ties and findIntMapMax see -- depends on thread timing: the call runs with one. */
+int ref_typer_infer(ref_typer* t, const ref_typer_reads* in, double insert_mean, double insert_sd, const char* out_dir, const char* long_reads_mode, const char* g_dir)
+{
+    char cwd[4096];
+    if(!getcwd(cwd, sizeof(cwd))) { g_err = "getcwd failed"; return -1; }
+    if(chdir(g_dir) != 0) { g_err = std::string("cannot change into ") + g_dir; return -1; }
+    const int threads = omp_get_max_threads();
+    omp_set_num_threads(1);
+    int rc = guarded([&]() -> int {
+        TyperReads R; typer_build_reads(t->h, in, R);
+        t->T->HLATypeInference(R.rawPaired, R.alignedPaired, R.rawUnpaired, R.alignedUnpaired, insert_mean, insert_sd, std::string(out_dir), std::string(long_reads_mode));
+        return 0;
+    });
+    omp_set_num_threads(threads);
+    if(chdir(cwd) != 0 && rc == 0) { g_err = std::string("cannot change back into ") + cwd; rc = -1; }
+    return rc;
 }
 }  // extern "C"

@@ -64,6 +64,12 @@ def lib():
         _lib.ref_project_chains.argtypes = [vp, C.POINTER(P.ContigsDesc), C.POINTER(P.BatchIn), C.c_int, P.c_u8p, P.c_u8p, C.c_int, C.POINTER(P.ChainsOut), C.POINTER(P.ChainsOut)]
         _lib.ref_pair_chains.argtypes = [vp, C.POINTER(P.ContigsDesc), C.POINTER(P.Params), C.POINTER(P.SeedsIn), P.c_i32p, C.c_int, C.POINTER(P.ChainsOut), C.POINTER(P.PairsOut), P.c_u8p]
         _lib.ref_mapq_unpaired.argtypes = [vp, C.POINTER(P.SeedsIn), P.c_f64p, C.c_int, C.c_int, C.POINTER(P.PairsOut)]
+        _lib.ref_typer_create.argtypes = [vp, C.c_char_p]
+        _lib.ref_typer_create.restype = vp
+        _lib.ref_typer_destroy.argtypes = [vp]
+        _lib.ref_typer_include.argtypes = [vp, C.c_int, P.c_i32p, P.c_i32p, P.c_u8p]
+        _lib.ref_typer_exon_positions.argtypes = [vp, C.POINTER(TyperReads), C.POINTER(P.LocusDesc), C.POINTER(P.ExonPositionsOut), P.c_f64p]
+        _lib.ref_typer_infer.argtypes = [vp, C.POINTER(TyperReads), C.c_double, C.c_double, C.c_char_p, C.c_char_p, C.c_char_p]
     return _lib
 
 
@@ -146,6 +152,75 @@ class Reference:
     def close(self):
         if self.h:
             lib().ref_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class TyperReads(C.Structure):
+    """ref_typer_reads of oracle/ref/ref_driver.cpp"""
+    _fields_ = [("n_units", C.c_int32), ("paired", C.c_int32), ("rows", C.POINTER(P.SeedsIn)), ("col_mapq", P.c_u8p), ("row_mapq", P.c_f64p), ("unit_mapq", P.c_f64p),
+                ("primary_reverse", P.c_u8p), ("name_off", P.c_i32p), ("names", C.c_char_p)]
+
+
+def _typer_reads(rows):
+    """TyperReads from the dict tests/ref_typer.py: typer_rows builds; returns (struct, keepalive)."""
+    s, ks = P.fill_struct(P.SeedsIn, rows["seeds"])
+    enc = [n.encode() for n in rows["names"]]
+    a = dict(col_mapq=np.ascontiguousarray(rows["col_mapq"], np.uint8), row_mapq=np.ascontiguousarray(rows["row_mapq"], np.float64),
+             unit_mapq=np.ascontiguousarray(rows["unit_mapq"], np.float64), primary_reverse=np.ascontiguousarray(rows["primary_reverse"], np.uint8),
+             name_off=np.concatenate([[0], np.cumsum([len(x) for x in enc])]).astype(np.int32))
+    t = TyperReads(); t.n_units = int(rows["n_units"]); t.paired = int(rows["paired"]); t.rows = C.pointer(s); t.names = b"".join(enc)
+    for k, v in a.items():
+        setattr(t, k, v.ctypes.data_as(dict(TyperReads._fields_)[k]))
+    return t, (s, ks, a, enc)
+
+
+class ReferenceTyper:
+    """hla::HLATyper of the reference over the graph of a Reference and a graph directory (PRG/segments.txt and the segment files)."""
+
+    def __init__(self, ref, graph_dir):
+        self.ref = ref
+        self.h = lib().ref_typer_create(ref.h, str(graph_dir).encode())
+        if not self.h:
+            raise ReferenceError_(lib().ref_last_error().decode())
+
+    def _check(self, rc):
+        if rc != 0:
+            raise ReferenceError_(lib().ref_last_error().decode())
+
+    def include(self, first, last):
+        """intervalOverlapsWithGenes per (first, last) level pair"""
+        f = np.ascontiguousarray(first, np.int32); l = np.ascontiguousarray(last, np.int32); o = np.zeros(max(1, len(f)), np.uint8)
+        self._check(lib().ref_typer_include(self.h, len(f), f.ctypes.data_as(P.c_i32p), l.ctypes.data_as(P.c_i32p), o.ctypes.data_as(P.c_u8p)))
+        return o[:len(f)]
+
+    def exon_positions(self, rows, level_min, level_to_exon, insert_mean, insert_sd, min_alignment_columns=1000):
+        """The read loops of HLATypeInference for one locus around the reference's oneReadAlignment_2_exonPositions_*, alignmentWeightedOKFraction and
+        removeDoublePositionsFromRead, in the layout of hlala_exon_positions (read_pair indexes the units of `rows`) plus pos_mapq_p = mapQ_position.
+        Per-mate fields no position of an entry witnesses are -1 (read_reverse: 255); pos_mapq is not written."""
+        t, keep = _typer_reads(rows)
+        L, kl = P.make_locus_desc(level_min, level_to_exon, insert_mean, insert_sd, 0.0, 0.0, None, min_alignment_columns)
+        n = int(rows["n_units"]); ncol = int(rows["seeds"]["col_off"][-1])
+        o, d = P.alloc_exon_positions_out(n, ncol + 1, 2 * ncol + 1)
+        mp = np.zeros(ncol + 1, np.float64)
+        self._check(lib().ref_typer_exon_positions(self.h, C.byref(t), C.byref(L), C.byref(o), mp.ctypes.data_as(P.c_f64p)))
+        e = P.trim_exon_positions(o, d)
+        e["pos_mapq_p"] = mp[:e["n_pos"]].copy()
+        return e
+
+    def infer(self, rows, insert_mean, insert_sd, out_dir, long_reads_mode, g_dir):
+        """HLATypeInference into out_dir, with one OpenMP thread and g_dir (holding hla_nom_g.txt) as the working directory during the call."""
+        t, keep = _typer_reads(rows)
+        self._check(lib().ref_typer_infer(self.h, C.byref(t), insert_mean, insert_sd, str(out_dir).encode(), long_reads_mode.encode(), str(g_dir).encode()))
+
+    def close(self):
+        if self.h:
+            lib().ref_typer_destroy(self.h)
             self.h = None
 
     def __del__(self):
