@@ -4,77 +4,77 @@
 
 namespace hlala {
 
-struct DevBatch {
+template <template <class> class Ptr> struct DevBatchT {
     int n_pairs, n_reads, n_chains, stride;
     int from_seeds;                 // 1: seed chains were uploaded directly (no stage A / C inputs)
     int unpaired;                   // 1: one read per unit (long-read / unpaired mode): n_reads == n_pairs, no extension DP
     // ---- inputs
-    const int* read_off;            // [n_reads+1]
-    const uint8_t* read_bases;      // alignment orientation of the primary
-    const uint8_t* read_quals;
-    const int* chain_off;           // [n_reads+1]
-    const int* read_primary;        // [n_reads]
-    const int* chain_read;          // [n_chains]
-    const int* chain_contig;
-    const int* chain_pos;
-    const int* chain_offset;
-    const int* chain_as;
-    const uint8_t* chain_reverse;
-    const int* cigar_off;
-    const u32* cigar;
+    Ptr<const int> read_off;            // [n_reads+1]
+    Ptr<const uint8_t> read_bases;      // alignment orientation of the primary
+    Ptr<const uint8_t> read_quals;
+    Ptr<const int> chain_off;           // [n_reads+1]
+    Ptr<const int> read_primary;        // [n_reads]
+    Ptr<const int> chain_read;          // [n_chains]
+    Ptr<const int> chain_contig;
+    Ptr<const int> chain_pos;
+    Ptr<const int> chain_offset;
+    Ptr<const int> chain_as;
+    Ptr<const uint8_t> chain_reverse;
+    Ptr<const int> cigar_off;
+    Ptr<const u32> cigar;
     // ---- stage A: seed chains (verboseSeedChain after alignment2Chain)
-    int* seed_status;               // [n_chains] HLALA_CHAIN_*
-    int* seed_ncols;
-    int* seed_begin;
-    int* seed_end;
-    int* seed_removed;
-    int* seed_level;                // [n_rows*stride]: the column rows of a chain start at row_base(B, chain)
-    int* seed_edge;
-    uint8_t* seed_g;
-    uint8_t* seed_s;
+    Ptr<int> seed_status;               // [n_chains] HLALA_CHAIN_*
+    Ptr<int> seed_ncols;
+    Ptr<int> seed_begin;
+    Ptr<int> seed_end;
+    Ptr<int> seed_removed;
+    Ptr<int> seed_level;                // [n_rows*stride]: the column rows of a chain start at row_base(B, chain)
+    Ptr<int> seed_edge;
+    Ptr<uint8_t> seed_g;
+    Ptr<uint8_t> seed_s;
     // ---- stage B: extended chains
-    int* ext_status;
-    int* ext_ncols;
-    int* ext_begin;
-    int* ext_end;
-    double* ext_ll;
-    int* dp_iters;                  // [2*n_chains]
-    int* dp_score;                  // [2*n_chains]
-    int* dp_ncols;                  // [2*n_chains] extension columns of the DP (-1: no extension)
-    int* dp_sb;                     // [2*n_chains] read interval covered by the extension
-    int* dp_se;
-    int* dp_err;                    // [2*n_chains] 0, kernel line of a capacity failure, or -1000000 - columns
-    int* dp_alias_head;             // [2*n_chains] items whose DP starts from the same cell of the same read as this item's: head of the list (-1: none)
-    int* dp_alias_next;             // [2*n_chains] ... next entry of the list an item is on
-    int* ext_level;                 // [n_rows*stride]
-    int* ext_edge;
-    uint8_t* ext_g;
-    uint8_t* ext_s;
-    uint8_t* ext_fromseed;
-    int* ext_firstlast;             // [n_chains*4]: first level, second level, last level, second-last level (-1 = none)
+    Ptr<int> ext_status;
+    Ptr<int> ext_ncols;
+    Ptr<int> ext_begin;
+    Ptr<int> ext_end;
+    Ptr<double> ext_ll;
+    Ptr<int> dp_iters;                  // [2*n_chains]
+    Ptr<int> dp_score;                  // [2*n_chains]
+    Ptr<int> dp_ncols;                  // [2*n_chains] extension columns of the DP (-1: no extension)
+    Ptr<int> dp_sb;                     // [2*n_chains] read interval covered by the extension
+    Ptr<int> dp_se;
+    Ptr<int> dp_err;                    // [2*n_chains] 0, kernel line of a capacity failure, or -1000000 - columns
+    Ptr<int> dp_alias_head;             // [2*n_chains] items whose DP starts from the same cell of the same read as this item's: head of the list (-1: none)
+    Ptr<int> dp_alias_next;             // [2*n_chains] ... next entry of the list an item is on
+    Ptr<int> ext_level;                 // [n_rows*stride]
+    Ptr<int> ext_edge;
+    Ptr<uint8_t> ext_g;
+    Ptr<uint8_t> ext_s;
+    Ptr<uint8_t> ext_fromseed;
+    Ptr<int> ext_firstlast;             // [n_chains*4]: first level, second level, last level, second-last level (-1 = none)
     // ---- stage C: selected pair
-    int* pair_status;               // [n_pairs]
-    int* best_chain;                // [n_reads]
-    int* n_comb;                    // [n_pairs]
-    double* pair_ll;
-    double* pair_mapq;
-    double* mate_mapq;              // [n_reads]
-    uint8_t* strands_valid;
-    uint8_t* sel_mapq;              // [n_reads*stride] mapQ_perPosition of the selected chain
+    Ptr<int> pair_status;               // [n_pairs]
+    Ptr<int> best_chain;                // [n_reads]
+    Ptr<int> n_comb;                    // [n_pairs]
+    Ptr<double> pair_ll;
+    Ptr<double> pair_mapq;
+    Ptr<double> mate_mapq;              // [n_reads]
+    Ptr<uint8_t> strands_valid;
+    Ptr<uint8_t> sel_mapq;              // [n_reads*stride] mapQ_perPosition of the selected chain
     // ---- counters (device): see hlala_batch_stats
-    u64* counters;                  // [32]
-    int* work_counter;              // [WC_N] dynamic work distribution: [0] stage A, [2] stage C, [7] chains stitched, [8]/[9] left / right DP items,
+    Ptr<u64> counters;                  // [32]
+    Ptr<int> work_counter;              // [WC_N] dynamic work distribution: [0] stage A, [2] stage C, [7] chains stitched, [8]/[9] left / right DP items,
                                     //      [1]/[10] left / right items fetched, [12..35] retry lists (count, fetched) per tier 1..6 and direction
-    int* retry_list;                // [16*n_chains] DP items that outgrew a capacity class: (tier 1..6) x (left, right) x n_chains; rows 14 / 15: the fail-over lists of the band kernels and the
+    Ptr<int> retry_list;                // [16*n_chains] DP items that outgrew a capacity class: (tier 1..6) x (left, right) x n_chains; rows 14 / 15: the fail-over lists of the band kernels and the
                                     //      jump-free instantiation (WC_FO_COUNT)
-    int* pair_multi;                // [2 passes][2 classes][n_pairs] pairs with several combinations, listed by k_pair_chains for k_pair_multi (kernel_pair.hip; counts in work_counter[WC_PAIR_MULTI ...])
-    uint8_t* pair_deferred;         // [n_pairs] 1: a DP call of the pair went to the in-memory class; with the fused entry point its chains are stitched and
+    Ptr<int> pair_multi;                // [2 passes][2 classes][n_pairs] pairs with several combinations, listed by k_pair_chains for k_pair_multi (kernel_pair.hip; counts in work_counter[WC_PAIR_MULTI ...])
+    Ptr<uint8_t> pair_deferred;         // [n_pairs] 1: a DP call of the pair went to the in-memory class; with the fused entry point its chains are stitched and
                                     //           the pair is scored in a second pass, after that class (which runs on a side stream next to the first pass)
     // ---- position order of the chains (kernel_order.hip): the kernels that walk the graph take their chains in this order, so that the work in flight at
     //      one time sits on neighbouring levels and its share of the graph arrays stays in the L2 (input order = read-name order = random positions)
-    int* chain_order;               // [n_chains] chain numbers sorted by position bucket; null: input order
-    int* chain_bucket;              // [n_chains] position bucket = first level >> order_shift (the last bucket: chains filtered out)
-    int* order_hist;                // [order_nb + 1] bucket counts -> bucket starts -> scatter cursors
+    Ptr<int> chain_order;               // [n_chains] chain numbers sorted by position bucket; null: input order
+    Ptr<int> chain_bucket;              // [n_chains] position bucket = first level >> order_shift (the last bucket: chains filtered out)
+    Ptr<int> order_hist;                // [order_nb + 1] bucket counts -> bucket starts -> scatter cursors
     int order_shift, order_nb;
     int long_chunk_nodes, long_max_segs;      // long-read layout, level-by-level form of the re-threading DP (kernel_project.hip): nodes a chunk of levels may hold (<= RT_SN) and long segments a read may
                                     // have beside its short ones (<= PROJL_LONGSEG); HLALA_LONG_CHUNK_NODES / HLALA_LONG_MAXSEGS shrink them so that small tests walk every branch
@@ -84,24 +84,39 @@ struct DevBatch {
     //      processBAM.cpp:3200-3240) and never hold a column.  The filter and the position order run when the batch is CREATED (they read inputs only), the count of the
     //      ordered chains comes back with the upload's synchronisation, and the column arrays (seed_* / ext_*: 20 bytes per column slot) are sized by it: row k belongs to
     //      chain_order[k] -- rows are in position order -- and chain_row is the inverse (-1: no row).  null: row = chain number (batches made from seeds, no position order).
-    int* chain_row;                 // [n_chains]
+    Ptr<int> chain_row;                 // [n_chains]
     int n_rows;
-    int* dp_blk;                    // [DPL_N * dp_nblk + 1] items per block of k_dp_items and list (band left / right, jump-free left / right, general left / right); after the scan: where they start
-    int* dp_list;                   // [2*n_chains] the ten dense lists of the first DP classes: slots of dp_items in position order (k_dp_lists)
+    Ptr<int> dp_blk;                    // [DPL_N * dp_nblk + 1] items per block of k_dp_items and list (band left / right, jump-free left / right, general left / right); after the scan: where they start
+    Ptr<int> dp_list;                   // [2*n_chains] the ten dense lists of the first DP classes: slots of dp_items in position order (k_dp_lists)
     int dp_nblk;                    // blocks of k_dp_items
     int dp_band;                    // > 0: calls whose reach (read bases left + dp_band - 1 levels) stays inside a linear run of the graph go to the band kernel's lists (kernel_dp_band.hip); 0: HLALA_DP_BAND=0
     int dp_band_risky;              // tests (HLALA_DP_BAND_RISKY=1): a call is listed for the band kernel as soon as the linear run covers its read bases -- many then walk past it and exercise the fail-over
     int dp_jf;                      // > 0: calls that meet no gap-path jump go to the lists of the jump-free instantiations, reach = read bases left + dp_jf - 1 levels (HLALA_DP_JF_MARGIN + 1)
-    void* dp_items;                 // [2*n_chains] DpItem (kernel_dp.hip)
-    int* dbg;                       // non-null with HLALA_DEBUG=1: kernels add phase clocks to counters[16..31]
+    Ptr<void> dp_items;                 // [2*n_chains] DpItem (kernel_dp.hip)
+    Ptr<int> dbg;                       // non-null with HLALA_DEBUG=1: kernels add phase clocks to counters[16..31]
 };
+typedef DevBatchT<HostP> DevBatch;       // the host's form and the kernels' by-value form
+typedef DevBatchT<GlobP> DevBatchG;      // the device view of a descriptor in device memory (device_common.h)
+static_assert(sizeof(DevBatch) == sizeof(DevBatchG), "one layout");
+__device__ __forceinline__ const DevBatchG& dev_view(const DevBatch* p) { return *(const DevBatchG*)p; }
+// How a kernel gets a descriptor is chosen per kernel, and per instantiation of a kernel template, by what the compiler's report and the kernel trace say
+// (profiles/flat_to_global.txt): by value, through the view of the device copy, or -- the form every kernel had before -- through the plain device copy, whose
+// pointers are generic.  A template that mixes forms (k_project_chains, k_pair_multi: their names are what the profile tools match on) takes both arguments and picks one; the one an
+// instantiation does not read costs its 0.4-0.6 KB of the kernel-argument segment per launch and no instruction.
+enum { DESC_VALUE = 0, DESC_VIEW = 1, DESC_GENERIC = 2 };
+template <int FORM, class D> __device__ __forceinline__ decltype(auto) desc_of(const D& byValue, const D* inMemory)
+{
+    if constexpr (FORM == DESC_VIEW) return dev_view(inMemory);
+    else if constexpr (FORM == DESC_GENERIC) return (*inMemory);
+    else return (byValue);
+}
 
 // number of entries of B.chain_order: the chains that passed the filters (k_filter_chains); without a position order every chain is listed.
 // (order_hist[order_nb - 1] is the start of a bucket nothing is put into = the end of the last real bucket, before and after the scatter)
-__device__ __forceinline__ int ordered_chains(const DevBatch& B) { return B.chain_order ? __builtin_amdgcn_readfirstlane(B.order_hist[B.order_nb - 1]) : B.n_chains; }
+template <class BT> __device__ __forceinline__ int ordered_chains(const BT& B) { return B.chain_order ? __builtin_amdgcn_readfirstlane(B.order_hist[B.order_nb - 1]) : B.n_chains; }
 
 // first column slot of a chain's rows in seed_* / ext_* (only chains that passed the filters have rows: callers look at the chain's status first)
-__device__ __forceinline__ size_t row_base(const DevBatch& B, int c) { return (size_t)(B.chain_row ? B.chain_row[c] : c) * (size_t)B.stride; }
+template <class BT> __device__ __forceinline__ size_t row_base(const BT& B, int c) { return (size_t)(B.chain_row ? B.chain_row[c] : c) * (size_t)B.stride; }
 
 // ---- the first DP classes' dense item lists (k_dp_items / k_dp_lists): list k occupies dp_list[dp_blk[k * dp_nblk] .. dp_blk[(k + 1) * dp_nblk]); k + 1: the right extensions
 enum { DPL_BAND16 = 0, DPL_BAND32 = 2, DPL_BAND64 = 4, DPL_JF = 6, DPL_GEN = 8, DPL_N = 10 };

@@ -8,40 +8,56 @@ namespace hlala {
 typedef unsigned long long u64;
 typedef unsigned int u32;
 
+// The descriptors below exist in two forms with ONE layout.  The host builds them with plain pointers (DevGraph, DevBatch) and hands them to a kernel either by
+// value -- the words then sit in SGPRs from the kernel's entry and the compiler knows that the pointers are global -- or as a device copy.  A kernel that keeps
+// the device copy (its descriptor words would not fit the SGPRs beside its state) can read it through the device view (DevGraphG, DevBatchG, dev_view()): the
+// same words, the pointer members typed as address-space-1 pointers.  A pointer loaded from memory is otherwise 'generic' to the compiler, and every access
+// through it a FLAT instruction (see GPtr below).  Which kernel takes which form: batch.h (desc_of) and profiles/flat_to_global.txt.
+#define HLALA_AS_GLOBAL __attribute__((address_space(1)))
+template <class T> using HostP = T*;
+#if defined(__HIP_DEVICE_COMPILE__)
+template <class T> using GlobP = HLALA_AS_GLOBAL T*;
+#else
+template <class T> using GlobP = T*;       // the host pass only parses the kernels; its target knows no conversion from address space 1 to a plain pointer
+#endif
+
 // Flattened PRG resident in HBM (see flat_graph.hpp for the meaning of each array).
-struct DevGraph {
+template <template <class> class Ptr> struct DevGraphT {
     int L, N, E, P;
-    const int* level_off;      // [L+1]
-    const int* node_level;     // [N]
-    const int* node_orig;      // [N]
-    const int* out_off;        // [N+1]
-    const int* out_to;         // [E]
-    const uint8_t* out_label;  // [E]
-    const int* out_eid;        // [E]
-    const int* in_off;
-    const int* in_from;
-    const uint8_t* in_label;
-    const int* in_eid;
-    const unsigned int* in_rec; // [E] packed in-edge records of the projection's re-threading DP (flat_graph.hpp)
-    const uint8_t* level_fast;  // [L] the level can be solved edge-parallel (flat_graph.hpp)
-    const int* edge_from_new;  // [E] by creation index
-    const int* edge_to_new;    // [E]
-    const uint8_t* edge_label; // [E] by creation index
-    const int* jf_off; const int* jf_node; const int* jf_path; const int* jf_lvl;
-    const int* jb_off; const int* jb_node; const int* jb_path; const int* jb_lvl;
-    const uint8_t* out_prank; const uint8_t* in_prank; const uint8_t* jf_prank; const uint8_t* jb_prank;   // rank among the node's earlier entries to the same target (flat_graph.hpp)
-    const uint8_t* jfree_out; const uint8_t* jfree_in;   // [L] levels without a gap-path jump from this level on, in either direction (flat_graph.hpp)
-    const u32* lin_label; const uint8_t* lin_out; const uint8_t* lin_in; const int* lin_eid;   // [L] linear steps and their run lengths (flat_graph.hpp; kernel_dp_band.hip)
-    const int4* nrec_out;      // [2*N] 32-byte node records of the extension DP (flat_graph.hpp)
-    const int4* nrec_in;
-    const int* path_len;       // [P]
-    const long long* path_off; // [P+1]
-    const int* path_edges;
-    const uint8_t* gap_stretch;// [L-1]
-    const long long* lp_off;   // [L+1]
-    const int* lp_seqid;
-    const int* lp_pos;
+    Ptr<const int> level_off;      // [L+1]
+    Ptr<const int> node_level;     // [N]
+    Ptr<const int> node_orig;      // [N]
+    Ptr<const int> out_off;        // [N+1]
+    Ptr<const int> out_to;         // [E]
+    Ptr<const uint8_t> out_label;  // [E]
+    Ptr<const int> out_eid;        // [E]
+    Ptr<const int> in_off;
+    Ptr<const int> in_from;
+    Ptr<const uint8_t> in_label;
+    Ptr<const int> in_eid;
+    Ptr<const unsigned int> in_rec; // [E] packed in-edge records of the projection's re-threading DP (flat_graph.hpp)
+    Ptr<const uint8_t> level_fast;  // [L] the level can be solved edge-parallel (flat_graph.hpp)
+    Ptr<const int> edge_from_new;  // [E] by creation index
+    Ptr<const int> edge_to_new;    // [E]
+    Ptr<const uint8_t> edge_label; // [E] by creation index
+    Ptr<const int> jf_off; Ptr<const int> jf_node; Ptr<const int> jf_path; Ptr<const int> jf_lvl;
+    Ptr<const int> jb_off; Ptr<const int> jb_node; Ptr<const int> jb_path; Ptr<const int> jb_lvl;
+    Ptr<const uint8_t> out_prank; Ptr<const uint8_t> in_prank; Ptr<const uint8_t> jf_prank; Ptr<const uint8_t> jb_prank;   // rank among the node's earlier entries to the same target (flat_graph.hpp)
+    Ptr<const uint8_t> jfree_out; Ptr<const uint8_t> jfree_in;   // [L] levels without a gap-path jump from this level on, in either direction (flat_graph.hpp)
+    Ptr<const u32> lin_label; Ptr<const uint8_t> lin_out; Ptr<const uint8_t> lin_in; Ptr<const int> lin_eid;   // [L] linear steps and their run lengths (flat_graph.hpp; kernel_dp_band.hip)
+    Ptr<const int4> nrec_out;      // [2*N] 32-byte node records of the extension DP (flat_graph.hpp)
+    Ptr<const int4> nrec_in;
+    Ptr<const int> path_len;       // [P]
+    Ptr<const long long> path_off; // [P+1]
+    Ptr<const int> path_edges;
+    Ptr<const uint8_t> gap_stretch;// [L-1]
+    Ptr<const long long> lp_off;   // [L+1]
+    Ptr<const int> lp_seqid;
+    Ptr<const int> lp_pos;
 };
+typedef DevGraphT<HostP> DevGraph;
+typedef DevGraphT<GlobP> DevGraphG;
+static_assert(sizeof(DevGraph) == sizeof(DevGraphG), "one layout");
 
 // Constant tables computed once on the host with the host libm so that device results are
 // bit-identical to a CPU evaluation of the reference formulas.
@@ -76,7 +92,6 @@ __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 // 'generic': every access through it is a FLAT instruction, which goes to the LDS queue as well as to the vector-memory path, counts in both wait counters and can
 // only be waited for with 'everything outstanding' (round 6: 286 of the 310 loads of the long-read projection were flat_load).  glob() casts to the global address
 // space (the result is a pointer TYPE of that address space: `auto`, not `T*`, receives it); GPtr<T> is a pointer member whose accesses are global.
-#define HLALA_AS_GLOBAL __attribute__((address_space(1)))
 template <class T> struct GPtr {
     typedef HLALA_AS_GLOBAL T GT;
     T* p;
@@ -89,6 +104,8 @@ template <class T> struct GPtr {
     __device__ __forceinline__ operator GT*() const { return g(); }
 };
 template <class T> __device__ __forceinline__ HLALA_AS_GLOBAL T* glob(T* p) { return (HLALA_AS_GLOBAL T*)p; }
+// the device view of a descriptor in device memory
+__device__ __forceinline__ const DevGraphG& dev_view(const DevGraph* p) { return *(const DevGraphG*)p; }
 // All kernels run ONE wavefront per block, so a block barrier is only a memory-ordering point between lanes of the
 // same wave.  __syncthreads() is not used: hipcc (ROCm 7.2) miscompiled persistent work loops that `continue` / `break`
 // around it (kernels never terminated); a wavefront-scope fence + scheduling barrier gives the ordering without the

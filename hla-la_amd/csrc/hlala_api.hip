@@ -927,14 +927,14 @@ int hlala_project_chains(hlala_ctx* c, hlala_batch* b)
         }
         int grid = B.n_chains < c->proj_grid ? B.n_chains : c->proj_grid;
         if(c->proj_long_slabs)
-            hipLaunchKernelGGL((k_project_chains<ProjLdsLong>), dim3(grid), dim3(64), 0, c->active, c->dG, b->dB, c->d_contig_off, c->d_contig_seq, c->d_contig_level,
+            hipLaunchKernelGGL((k_project_chains<ProjLdsLong>), dim3(grid), dim3(64), 0, c->active, c->G, b->B, c->dG, b->dB, c->d_contig_off, c->d_contig_seq, c->d_contig_level,
                                c->proj_slabs, c->proj_slab_bytes, c->proj_long_slabs, c->proj_long_slab_bytes, 0);
         else
             if(c->params.max_columns <= PROJ_CAP_SHORT)
-                hipLaunchKernelGGL((k_project_chains<ProjLdsShort>), dim3(grid), dim3(64), 0, c->active, c->dG, b->dB, c->d_contig_off, c->d_contig_seq, c->d_contig_level,
+                hipLaunchKernelGGL((k_project_chains<ProjLdsShort>), dim3(grid), dim3(64), 0, c->active, c->G, b->B, c->dG, b->dB, c->d_contig_off, c->d_contig_seq, c->d_contig_level,
                                    c->proj_slabs, c->proj_slab_bytes, (char*)nullptr, (size_t)0, c->rethread_slabs ? 1 : 0);
             else
-                hipLaunchKernelGGL((k_project_chains<ProjLds>), dim3(grid), dim3(64), 0, c->active, c->dG, b->dB, c->d_contig_off, c->d_contig_seq, c->d_contig_level,
+                hipLaunchKernelGGL((k_project_chains<ProjLds>), dim3(grid), dim3(64), 0, c->active, c->G, b->B, c->dG, b->dB, c->d_contig_off, c->d_contig_seq, c->d_contig_level,
                                c->proj_slabs, c->proj_slab_bytes, (char*)nullptr, (size_t)0, c->rethread_slabs ? 1 : 0);
         int rc = check_launch(c, "k_project_chains"); if(rc) return rc;
         if(c->rethread_slabs) {
@@ -989,10 +989,10 @@ static int extend_impl(hlala_ctx* c, hlala_batch* b, bool fused, int phase)
         HIP_TRY(c, hipMemsetAsync(B.dp_alias_next, 0xFF, (size_t)2 * B.n_chains * sizeof(int), c->active));
         // items, then the ten dense lists of the first classes (three band lists, jump-free, general; left / right each) in position order: counts per block, their scan, the slots
         HIP_TRY(c, hipMemsetAsync(B.dp_blk, 0, ((size_t)DPL_N * B.dp_nblk + 1) * sizeof(int), c->active));
-        hipLaunchKernelGGL(k_dp_items, dim3(B.dp_nblk), dim3(256), 0, c->active, c->dG, b->dB, items);
+        hipLaunchKernelGGL(k_dp_items, dim3(B.dp_nblk), dim3(256), 0, c->active, c->G, b->B, items);
         rc = check_launch(c, "k_dp_items"); if(rc) return rc;
         hipLaunchKernelGGL(k_order_scan, dim3(1), dim3(ORDER_SCAN_THREADS), 0, c->active, B.dp_blk, DPL_N * B.dp_nblk + 1);
-        hipLaunchKernelGGL(k_dp_lists, dim3(B.dp_nblk), dim3(256), 0, c->active, b->dB, (const DpItem*)items);
+        hipLaunchKernelGGL(k_dp_lists, dim3(B.dp_nblk), dim3(256), 0, c->active, b->B, (const DpItem*)items);
         rc = check_launch(c, "k_dp_lists"); if(rc) return rc;
         }
         // every DP item first runs in the 16-lane class; the item count lives on the device, idle groups leave at once.
@@ -1037,9 +1037,9 @@ static int extend_impl(hlala_ctx* c, hlala_batch* b, bool fused, int phase)
         b->band_used = c->band_grid > 0;
         if(b->band_used) {
             HIP_TRY(c, hipEventRecord(b->evBand[0], c->active));
-            hipLaunchKernelGGL((k_dp_band<16>), dim3(c->band_grid), dim3(64), 0, c->active, c->dG, b->dB, (const DpItem*)items, seed, (const uint8_t*)B.read_bases, c->G.lin_label, c->G.lin_eid);
-            hipLaunchKernelGGL((k_dp_band<32>), dim3(c->band_grid), dim3(64), 0, c->active, c->dG, b->dB, (const DpItem*)items, seed, (const uint8_t*)B.read_bases, c->G.lin_label, c->G.lin_eid);
-            hipLaunchKernelGGL((k_dp_band<64>), dim3(c->band_grid), dim3(64), 0, c->active, c->dG, b->dB, (const DpItem*)items, seed, (const uint8_t*)B.read_bases, c->G.lin_label, c->G.lin_eid);
+            hipLaunchKernelGGL((k_dp_band<16>), dim3(c->band_grid), dim3(64), 0, c->active, c->G, b->B, (const DpItem*)items, seed, (const uint8_t*)B.read_bases, c->G.lin_label, c->G.lin_eid);
+            hipLaunchKernelGGL((k_dp_band<32>), dim3(c->band_grid), dim3(64), 0, c->active, c->G, b->B, (const DpItem*)items, seed, (const uint8_t*)B.read_bases, c->G.lin_label, c->G.lin_eid);
+            hipLaunchKernelGGL((k_dp_band<64>), dim3(c->band_grid), dim3(64), 0, c->active, c->G, b->B, (const DpItem*)items, seed, (const uint8_t*)B.read_bases, c->G.lin_label, c->G.lin_eid);
             rc = check_launch(c, "k_dp_band"); if(rc) return rc;
             HIP_TRY(c, hipEventRecord(b->evBand[1], c->active));
         }
@@ -1062,14 +1062,14 @@ static int extend_impl(hlala_ctx* c, hlala_batch* b, bool fused, int phase)
         if(fused && phase != 1 && phase != 3) {
             // second pass (side): the chains of the deferred pairs, work counter 36; first pass (main): all the others, work counter 7
             { const int pgrid = (B.n_pairs + 63) / 64, cap = c->stitch_grid / 20;       // the second pass sweeps the pairs' flags, 64 per wave and round: one wave per CU finds room beside the next batch's persistent kernels
-              hipLaunchKernelGGL(k_stitch_chains, dim3(pgrid < cap ? (pgrid > 0 ? pgrid : 1) : cap), dim3(64), 0, c->side, c->dG, c->dT, b->dB, (const uint8_t*)B.pair_deferred, 2, 0, 0); }
+              hipLaunchKernelGGL(k_stitch_chains, dim3(pgrid < cap ? (pgrid > 0 ? pgrid : 1) : cap), dim3(64), 0, c->side, c->G, c->dT, b->B, (const uint8_t*)B.pair_deferred, 2, 0, 0); }
             rc = check_launch(c, "k_stitch_chains (side)"); if(rc) return rc;
             HIP_TRY(c, hipEventRecord(b->evDone, c->side));
             HIP_TRY(c, hipEventRecord(c->evSideTail, c->side)); c->sideTailValid = true;
             b->side_inflight = true; b->side_used = true; b->side_pending = true;
         }
         if(mainPart) {
-        hipLaunchKernelGGL(k_stitch_chains, dim3(sgrid), dim3(64), 0, c->active, c->dG, c->dT, b->dB, (const uint8_t*)B.pair_deferred, fused ? 1 : 0, c->stitch_draw, c->stitch_by_row);
+        hipLaunchKernelGGL(k_stitch_chains, dim3(sgrid), dim3(64), 0, c->active, c->G, c->dT, b->B, (const uint8_t*)B.pair_deferred, fused ? 1 : 0, c->stitch_draw, c->stitch_by_row);
         rc = check_launch(c, "k_stitch_chains"); if(rc) return rc;
         }
     }
@@ -1112,12 +1112,12 @@ static int pair_impl(hlala_ctx* c, hlala_batch* b, int phase)
             const int g0 = mode == 2 ? (grid < c->pair_grid / 5 ? grid : c->pair_grid / 5) : grid, g1 = grid < c->pair_grid / 5 ? grid : c->pair_grid / 5;      // (the second pass and the general class hold a few thousand pairs at most)
             if(B.unpaired) {
                 hipLaunchKernelGGL((k_pair_chains<true>), dim3(lean), dim3(64), 0, st, c->dG, c->dT, b->dB, (const uint8_t*)B.pair_deferred, mode, counterIdx, multiList, multiBase);
-                hipLaunchKernelGGL((k_pair_multi<true, false>), dim3(g0), dim3(64), 0, st, c->dG, c->dT, b->dB, (const int*)multiList, multiBase, scratch);
-                hipLaunchKernelGGL((k_pair_multi<true, true>), dim3(g1), dim3(64), 0, st, c->dG, c->dT, b->dB, (const int*)multiList, multiBase, scratch);
+                hipLaunchKernelGGL((k_pair_multi<true, false>), dim3(g0), dim3(64), 0, st, c->G, b->B, c->dG, c->dT, b->dB, (const int*)multiList, multiBase, scratch);
+                hipLaunchKernelGGL((k_pair_multi<true, true>), dim3(g1), dim3(64), 0, st, c->G, b->B, c->dG, c->dT, b->dB, (const int*)multiList, multiBase, scratch);
             } else {
                 hipLaunchKernelGGL((k_pair_chains<false>), dim3(lean), dim3(64), 0, st, c->dG, c->dT, b->dB, (const uint8_t*)B.pair_deferred, mode, counterIdx, multiList, multiBase);
-                hipLaunchKernelGGL((k_pair_multi<false, false>), dim3(g0), dim3(64), 0, st, c->dG, c->dT, b->dB, (const int*)multiList, multiBase, scratch);
-                hipLaunchKernelGGL((k_pair_multi<false, true>), dim3(g1), dim3(64), 0, st, c->dG, c->dT, b->dB, (const int*)multiList, multiBase, scratch);
+                hipLaunchKernelGGL((k_pair_multi<false, false>), dim3(g0), dim3(64), 0, st, c->G, b->B, c->dG, c->dT, b->dB, (const int*)multiList, multiBase, scratch);
+                hipLaunchKernelGGL((k_pair_multi<false, true>), dim3(g1), dim3(64), 0, st, c->G, b->B, c->dG, c->dT, b->dB, (const int*)multiList, multiBase, scratch);
             }
             return check_launch(c, "k_pair_chains / k_pair_multi");
         };

@@ -633,8 +633,8 @@ __device__ __forceinline__ int tier_for_targets(int n) { return n <= (DpMid::HC 
 
 #define DP_FAIL(code) do { if(gl == 0 && S.err == 0) S.err = (code); } while(0)
 
-template <class C>
-__device__ inline int dp_begin(DpLdsT<C>& S, const DpSlabT<C>& sl, const DevGraph& G, const DpItem& it, int itemIdx)
+template <class C, class DG>
+__device__ inline int dp_begin(DpLdsT<C>& S, const DpSlabT<C>& sl, const DG& G, const DpItem& it, int itemIdx)
 {
     constexpr int GW = C::GW;
     const int gl = grp_lane<GW>();
@@ -667,8 +667,8 @@ __device__ inline int dp_begin(DpLdsT<C>& S, const DpSlabT<C>& sl, const DevGrap
 // One iteration of extensionAligner::fullNeedleman_diagonal_extension_gapJumper (extensionAligner.cpp:531-1105) with
 // returnGlobalScore = false, preferSequenceCompleAlignments = true, empty blockedPathsTable,
 // diagonal_stop_threshold = -16 (the only configuration extendSeedChain uses, :229-241, :281-293).
-template <class C>
-__device__ inline int dp_iterate(DpLdsT<C>& S, const DpSlabT<C>& sl, const DevGraph& G, const int4* nrec, const uint8_t* readBases, const bool fwd, int& edgesAcc, u64* sortScratch)
+template <class C, class DG>
+__device__ inline int dp_iterate(DpLdsT<C>& S, const DpSlabT<C>& sl, const DG& G, const int4* nrec, const uint8_t* readBases, const bool fwd, int& edgesAcc, u64* sortScratch)
 {
     constexpr int GW = C::GW;
     const int gl = grp_lane<GW>();
@@ -1264,8 +1264,8 @@ __device__ inline int dp_iterate(DpLdsT<C>& S, const DpSlabT<C>& sl, const DevGr
 // many ties (allele-rich levels: thousands of sequence-complete cells): every tie gets a number whose order is the string order (xz_key), the
 // ties are compacted into the slab, and the selectedIndex-th smallest number is found bit by bit.  Register-hungry: only the classes that can hold thousands of complete
 // cells (frontier > 64) carry it; in the 16- / 32- / 64-lane kernels it cost 8 more spilled VGPRs in the persistent loop (+16 % kernel time).
-template <class C>
-__device__ inline int dp_select_many(const DpSlabT<C>& sl, const DevGraph& G, int nCompleted, int best, int selectedIndex)
+template <class C, class DG>
+__device__ inline int dp_select_many(const DpSlabT<C>& sl, const DG& G, int nCompleted, int best, int selectedIndex)
 {
     constexpr int GW = C::GW;
     const int gl = grp_lane<GW>();
@@ -1291,8 +1291,8 @@ __device__ inline int dp_select_many(const DpSlabT<C>& sl, const DevGraph& G, in
 }
 
 // ---- end cell, :1381-1517
-template <class C>
-__device__ inline int dp_select(DpLdsT<C>& S, const DpSlabT<C>& sl, const DevGraph& G, u32 rng_seed, const bool fwd)
+template <class C, class DG>
+__device__ inline int dp_select(DpLdsT<C>& S, const DpSlabT<C>& sl, const DG& G, u32 rng_seed, const bool fwd)
 {
     constexpr int GW = C::GW;
     const int gl = grp_lane<GW>();
@@ -1418,8 +1418,8 @@ __device__ inline int dp_backtrace(DpLdsT<C>& S, const DpSlabT<C>& sl, int maxSt
 // ---- all lanes of the group expand the steps into alignment columns, written into the chain's output row:
 // the left extension at its final place [seq_begin, seq_begin + n), the right extension right-aligned in the row
 // (k_stitch_chains moves it next to the seed once the left extension's length is known)
-template <class C>
-__device__ inline int dp_expand(DpLdsT<C>& S, const DpSlabT<C>& sl, const DevGraph& G, const DevBatch& B, const int4* nrec, const bool fwd)
+template <class C, class DG, class DB>
+__device__ inline int dp_expand(DpLdsT<C>& S, const DpSlabT<C>& sl, const DG& G, const DB& B, const int4* nrec, const bool fwd)
 {
     constexpr int GW = C::GW;
     const int gl = grp_lane<GW>();
@@ -1496,7 +1496,8 @@ __device__ inline int dp_expand(DpLdsT<C>& S, const DpSlabT<C>& sl, const DevGra
 // Input checks of extendSeedChain (extensionAligner.cpp:184-319) per chain and the list of DP items.
 // work_counter[8] / [9] count the left / right items; chains without any usable seed get their final status here.
 // The DP item of chain c in direction d (0 = left, 1 = right), extensionAligner.cpp:220-319; false: no such DP.
-__device__ inline bool dp_item_for(const DevGraph& G, const DevBatch& B, int c, int d, DpItem& it)
+template <class DG, class DB>
+__device__ inline bool dp_item_for(const DG& G, const DB& B, int c, int d, DpItem& it)
 {
     if(B.unpaired) return false;            // alignOneLongRead only pads the seed chain (extendToFullSequenceLength, processBAM.cpp:3733-3735)
     if(B.seed_status[c] != HLALA_CHAIN_OK) return false;
@@ -1522,10 +1523,8 @@ __device__ inline bool dp_item_for(const DevGraph& G, const DevBatch& B, int c, 
     return true;
 }
 
-__global__ void k_dp_items(const DevGraph* __restrict__ Gp, const DevBatch* __restrict__ Bp, DpItem* items)
+__global__ void k_dp_items(const DevGraph G, const DevBatch B, DpItem* items)
 {
-    const DevGraph& G = *Gp;
-    const DevBatch& B = *Bp;
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     // ---- every chain: DP outputs reset; chains that did not pass stage A get their final status here (dp_alias_head / dp_alias_next: memset by the host)
     if(t < B.n_chains) {
@@ -1627,9 +1626,8 @@ __global__ void k_dp_items(const DevGraph* __restrict__ Gp, const DevBatch* __re
 // The ten dense item lists of the first DP classes: list k (DPL_BAND16 / DPL_BAND32 / DPL_BAND64 / DPL_JF / DPL_GEN, + 1 for the right extensions) occupies
 // dp_list[dp_blk[k * nBlk] .. dp_blk[(k + 1) * nBlk]) -- dp_blk after its exclusive scan: entry k * nBlk + b = where block b's items of list k start --, its
 // entries are the slots of k_dp_items' item arrays in position order.  Same grid as k_dp_items.
-__global__ void k_dp_lists(const DevBatch* __restrict__ Bp, const DpItem* __restrict__ items)
+__global__ void k_dp_lists(const DevBatch B, const DpItem* __restrict__ items)
 {
-    const DevBatch& B = *Bp;
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     const int nOrd = ordered_chains(B);
     int kL = -1, kR = -1;             // list of the left / right item of this slot
@@ -1677,9 +1675,15 @@ struct DpPoolArgs {
     const uint8_t* bases[DP_POOL_MAX];
 };
 
-template <class C, int TIER>
-__device__ __forceinline__ void dp_class_run(const DevGraph& G, const DevBatch& B, const DpItem* __restrict__ items, DpLdsT<C>& S, DpSlabT<C> sl, u64* sortScratch, const u32 rng_seed,
+template <class C, int TIER, class DG, class DB>
+__device__ __forceinline__ void dp_class_run(const DG& G, const DB& B, const DpItem* __restrict__ items, DpLdsT<C>& S, DpSlabT<C> sl, u64* sortScratch, const u32 rng_seed,
                                              const int4* __restrict__ nrecOut, const int4* __restrict__ nrecIn, const uint8_t* __restrict__ readBases);
+
+// Which instantiations read the descriptors through the device view.  With the view no access of a class is a FLAT instruction (tiers 0 .. 5; the in-memory
+// class keeps the few whose pointer is LDS in the other classes).  Kept in the plain form: the general 16-lane instantiation and the 32- and 64-lane classes, which
+// the kernel trace of the resident loop showed 0.4-0.7 ms SLOWER with the view, against a run-to-run spread of 0.01 ms (the 32- / 64-lane classes also spill one / five
+// more registers with it), and the broad and the in-memory class, where the view was slower by about the spread (profiles/flat_to_global.txt section 4).
+template <class C, int TIER> __host__ __device__ constexpr int dp_desc_form() { return ((TIER == 0 && C::JF) || TIER == 3 || TIER == 5) ? DESC_VIEW : DESC_GENERIC; }
 
 template <class C, int TIER>
 __global__ __launch_bounds__(C::THREADS, C::WAVES) void k_dp(const DevGraph* __restrict__ Gp, const DevBatch* __restrict__ Bp, const DpItem* __restrict__ items,
@@ -1691,8 +1695,10 @@ __global__ __launch_bounds__(C::THREADS, C::WAVES) void k_dp(const DevGraph* __r
     constexpr int GW = C::GW;
     constexpr int NG = GW >= 64 ? 1 : 64 / GW;           // DPs per block: groups of a wavefront, or one DP for the whole block
     static_assert(C::THREADS == (GW >= 64 ? GW : 64), "block size");
-    // graph / batch descriptors stay in memory (scalar loads on demand): passing them by value costs ~150 SGPRs
-    const DevGraph& G = *Gp;
+    // graph / batch descriptors stay in memory (scalar loads on demand): passing them by value costs ~150 SGPRs, which spill into the registers the classes
+    // compiled for 128 have none to spare of.  dp_desc_form(): read through the device view (global pointers) or as plain structs (generic pointers).
+    constexpr int FORM = dp_desc_form<C, TIER>();
+    const auto& G = desc_of<FORM>(*Gp, Gp);
     const int g = (int)((threadIdx.x & 63) / GW);
     DpLdsT<C>* Sp; DpSlabT<C> sl; u64* sortScratch = nullptr;
     if constexpr (C::IN_MEMORY) {
@@ -1706,15 +1712,15 @@ __global__ __launch_bounds__(C::THREADS, C::WAVES) void k_dp(const DevGraph* __r
     if constexpr (TIER >= DP_POOL_TIER) {
         const int nB = __builtin_amdgcn_readfirstlane(pool.n);
         for(int bi = 0; bi < nB; bi++) {
-            dp_class_run<C, TIER>(G, *pool.B[bi], pool.items[bi], *Sp, sl, sortScratch, pool.seed[bi], nrecOut, nrecIn, pool.bases[bi]);
+            dp_class_run<C, TIER>(G, desc_of<FORM>(*pool.B[bi], pool.B[bi]), pool.items[bi], *Sp, sl, sortScratch, pool.seed[bi], nrecOut, nrecIn, pool.bases[bi]);
             DSYNC();
         }
-    } else dp_class_run<C, TIER>(G, *Bp, items, *Sp, sl, sortScratch, rng_seed, nrecOut, nrecIn, readBasesArg);
+    } else dp_class_run<C, TIER>(G, desc_of<FORM>(*Bp, Bp), items, *Sp, sl, sortScratch, rng_seed, nrecOut, nrecIn, readBasesArg);
 }
 
 // one class over the lists of one batch (the body of k_dp)
-template <class C, int TIER>
-__device__ __forceinline__ void dp_class_run(const DevGraph& G, const DevBatch& B, const DpItem* __restrict__ items, DpLdsT<C>& S, DpSlabT<C> sl, u64* sortScratch, const u32 rng_seed,
+template <class C, int TIER, class DG, class DB>
+__device__ __forceinline__ void dp_class_run(const DG& G, const DB& B, const DpItem* __restrict__ items, DpLdsT<C>& S, DpSlabT<C> sl, u64* sortScratch, const u32 rng_seed,
                                              const int4* __restrict__ nrecOut, const int4* __restrict__ nrecIn, const uint8_t* __restrict__ readBases)
 {
     constexpr int GW = C::GW;
@@ -1881,8 +1887,8 @@ __device__ __forceinline__ void dp_class_run(const DevGraph& G, const DevBatch& 
 // columns of the final row and fetches each from where it lives (pad: the read; left extension: in place; seed row; right extension at the end of the
 // row) -- one round trip for every column of the chain --, writes what has to move, and keeps level / graph character / read character in registers for
 // the likelihood terms and for the first / last levels (ballots, no loads).  The read qualities are the one dependent gather left.
-template <int PER>
-__device__ __forceinline__ void stitch_rounds(const DevBatch& B, const DevTables& T, const size_t cb, const int rOff, const int total, const int padL, const int nL, const int nSeed,
+template <int PER, class DB>
+__device__ __forceinline__ void stitch_rounds(const DB& B, const DevTables& T, const size_t cb, const int rOff, const int total, const int padL, const int nL, const int nSeed,
                                               const int nR, const int newEnd, const int stride, const int lane, double& llOut, int& f0, int& f1, int& l0, int& l1)
 {
     const int seedAt = padL + nL, rightAt = seedAt + nSeed, padRAt = rightAt + nR;
@@ -1989,7 +1995,8 @@ __device__ __forceinline__ void stitch_rounds(const DevBatch& B, const DevTables
 
 // The chains of one draw: lane q holds chain cq (-1: none).  Descriptors of all of them in two round trips (the fields, then what they point to), then one
 // chain after the other.  deferMode 1: the chains of deferred pairs stay pending (the second pass takes them), 0 / 2: every pending chain given.
-__device__ __forceinline__ void stitch_draw(const DevBatch& B, const DevTables& T, const uint8_t* __restrict__ deferPairs, const int deferMode, const int lane, const int cq,
+template <class DB>
+__device__ __forceinline__ void stitch_draw(const DB& B, const DevTables& T, const uint8_t* __restrict__ deferPairs, const int deferMode, const int lane, const int cq,
                                             u64& accChains, u64& accCols)
 {
     const int stride = B.stride;
@@ -2051,10 +2058,9 @@ __device__ __forceinline__ void stitch_draw(const DevBatch& B, const DevTables& 
 // the draws keep small is the WINDOW of 4 KB rows, out of 30 GB of column arrays, that the 5 120 waves touch at one time.
 // Pass 2 does not look at chains at all: the waves take the PAIRS 64 at a time (no atomic), and the chains of the few deferred ones -- ~2.5 k pairs per million --
 // are stitched; it used to test all 6.1 M chains beside the next batch's kernels (25 ms on the side stream for a few thousand chains; 0.15 ms now).
-__global__ __launch_bounds__(64, 5) void k_stitch_chains(const DevGraph* __restrict__ Gp, const DevTables* __restrict__ Tp, const DevBatch* __restrict__ Bp,
+__global__ __launch_bounds__(64, 5) void k_stitch_chains(const DevGraph G, const DevTables* __restrict__ Tp, const DevBatch B,
                                                         const uint8_t* __restrict__ deferPairs, const int deferMode, const int draw, const int byRow)      // draw: chains per wave and round (1 .. 64)
 {
-    const DevBatch& B = *Bp;
     const DevTables& T = *Tp;
     const int lane = lane_id();
     u64 accChains = 0, accCols = 0;          // work counters, flushed once per wave (same-address atomics serialise at the L2)

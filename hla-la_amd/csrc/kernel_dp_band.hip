@@ -63,8 +63,8 @@ template <int GW> __device__ __forceinline__ int band_prev(int v, int gl)
 #define BAND_T(i) do { } while(0)
 #endif
 
-template <class C, bool FWD>
-__device__ __forceinline__ void band_pass(const DevGraph& G, const DevBatch& B, const DpItem* __restrict__ items, const u32 rng_seed, const uint8_t* __restrict__ readBases,
+template <class C, bool FWD, class DG, class DB>
+__device__ __forceinline__ void band_pass(const DG& G, const DB& B, const DpItem* __restrict__ items, const u32 rng_seed, const uint8_t* __restrict__ readBases,
                                           const u32* __restrict__ linLabel, const int* __restrict__ linEid, BandLds<C>& S,
                                           u64& accCalls, u64& accIters, u64& accCells, u64& accEdges)
 {
@@ -306,12 +306,10 @@ __device__ __forceinline__ void band_pass(const DevGraph& G, const DevBatch& B, 
 }
 
 template <int GW>
-__global__ __launch_bounds__(64, BandCfg<GW>::WAVES) void k_dp_band(const DevGraph* __restrict__ Gp, const DevBatch* __restrict__ Bp, const DpItem* __restrict__ items, const u32 rng_seed,
+__global__ __launch_bounds__(64, BandCfg<GW>::WAVES) void k_dp_band(const DevGraph G, const DevBatch B, const DpItem* __restrict__ items, const u32 rng_seed,
                                                                     const uint8_t* __restrict__ readBases, const u32* __restrict__ linLabel, const int* __restrict__ linEid)
 {
     typedef BandCfg<GW> C;
-    const DevGraph& G = *Gp;
-    const DevBatch& B = *Bp;
     __shared__ BandLds<C> SS[64 / GW];
     BandLds<C>& S = SS[lane_id() / GW];
     u64 accCalls = 0, accIters = 0, accCells = 0, accEdges = 0;          // first lane of every group: flushed once

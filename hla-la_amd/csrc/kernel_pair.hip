@@ -58,7 +58,8 @@ __device__ __forceinline__ unsigned char pair_phred(const PairLds& P, double pCo
 }
 
 // position of sequence `id` at `level` (the level's entries are sorted by sequence id, flat_graph.cpp), -1 if the sequence does not pass through it
-__device__ inline int lp_find(const DevGraph& G, int level, int id)
+template <class DG>
+__device__ inline int lp_find(const DG& G, int level, int id)
 {
     long long lo = G.lp_off[level], hi = G.lp_off[level + 1];
     while(lo < hi) {
@@ -73,7 +74,8 @@ __device__ inline int lp_find(const DevGraph& G, int level, int id)
 // arguments: the lanes share the sequences of the upstream level and look each one up in the downstream levels by binary search (a level of a gene
 // window carries dozens to thousands of sequences; one lane walking both lists against each other was most of this kernel's time on Graph M).
 // The maximum does not depend on the order of the candidates.
-__device__ inline double pair_insert_ll(const DevGraph& G, const DevTables& T, const int up0, const int up1, const int dn0, const int dn1)
+template <class DG>
+__device__ inline double pair_insert_ll(const DG& G, const DevTables& T, const int up0, const int up1, const int dn0, const int dn1)
 {
     const int lane = lane_id();
     // Levels of the backbone carry a handful of sequences.  When none of the four levels has more than 16, a quarter of the wave takes each level: the four
@@ -107,7 +109,7 @@ __device__ inline double pair_insert_ll(const DevGraph& G, const DevTables& T, c
             if(have) {
                 const long long d = (long long)beginPos - pos - 1;
                 const long long k = d - T.is_dmin;
-                best = (k >= 0 && k < T.is_n) ? T.is_logpdf[k] : T.is_penalty;      // pdf <= 0 -> penalty (:3447-3464)
+                best = (k >= 0 && k < T.is_n) ? glob(T.is_logpdf)[k] : T.is_penalty;      // pdf <= 0 -> penalty (:3447-3464)
             }
             for(int o = 32; o; o >>= 1) { const double ov = __shfl_xor(best, o); if(ov > best) best = ov; }
             return __ballot(have) ? best : T.is_penalty;
@@ -128,7 +130,7 @@ __device__ inline double pair_insert_ll(const DevGraph& G, const DevTables& T, c
             if(beginPos < 0) continue;
             const long long d = (long long)beginPos - endPos - 1;
             const long long k = d - T.is_dmin;
-            const double v = (k >= 0 && k < T.is_n) ? T.is_logpdf[k] : T.is_penalty;      // pdf <= 0 -> penalty (:3447-3464)
+            const double v = (k >= 0 && k < T.is_n) ? glob(T.is_logpdf)[k] : T.is_penalty;      // pdf <= 0 -> penalty (:3447-3464)
             if(!have || v > best) { best = v; have = true; }
         }
     }
@@ -190,7 +192,8 @@ __global__ void k_pair_distances(const DevGraph* __restrict__ Gp, const DevBatch
 // (1-2 us with the TLB miss), and there used to be four in a row before the first combination was scored (status -> list -> levels / strand / likelihood;
 // later length / row / first level again for the per-position pass, and the selected chains' levels once more for the pair's outputs).
 struct PairChain { int4 fl; int rev, nk, row; double ll; };
-__device__ __forceinline__ PairChain pair_chain_load(const DevBatch& B, const int c)
+template <class DB>
+__device__ __forceinline__ PairChain pair_chain_load(const DB& B, const int c)
 {
     PairChain x;
     x.fl = *(const int4*)(B.ext_firstlast + 4 * (size_t)c); x.rev = B.chain_reverse[c]; x.ll = B.ext_ll[c]; x.nk = B.ext_ncols[c]; x.row = B.chain_row ? B.chain_row[c] : c;
@@ -214,8 +217,8 @@ __device__ __forceinline__ PairChain pair_chain_from_lane(const PairChain& x, co
 // level -- that hold what the comparison needs, so the comparison itself reads LDS only.  (Rounds 1-4: column numbers in LDS, the compared fields read back
 // from HBM per column, the chain's length / row / first level through three dependent wave-uniform loads, and PCorrectToPhred's binary search on the
 // table in global memory: ~75 dependent round trips for a pair of two chains per mate, 85 k cycles.)
-template <bool UNPAIRED, int PER>
-__device__ __forceinline__ void pair_positions(const DevBatch& B, PairLds& P, const double* __restrict__ LL, const int p, const int n1, const int n2, const int nComb,
+template <bool UNPAIRED, int PER, class DB>
+__device__ __forceinline__ void pair_positions(const DB& B, PairLds& P, const double* __restrict__ LL, const int p, const int n1, const int n2, const int nComb,
                                                const int best1, const int best2, const PairChain& cA, const PairChain& cB, const int lane, const int stride)
 {
     constexpr int NM = UNPAIRED ? 1 : 2;
@@ -321,8 +324,8 @@ __device__ __forceinline__ void pair_positions(const DevBatch& B, PairLds& P, co
 #define PAIR_T(i) do { } while(0)
 #endif
 
-template <bool UNPAIRED, bool BIG>
-__device__ __forceinline__ void pair_finish(const DevGraph& G, const DevTables& T, const DevBatch& B, PairLds& P, double* __restrict__ LL,
+template <bool UNPAIRED, bool BIG, class DG, class DB>
+__device__ __forceinline__ void pair_finish(const DG& G, const DevTables& T, const DB& B, PairLds& P, double* __restrict__ LL,
                                             const int p, const int n1, const int n2, const int nComb, const int mxc, const PairChain& cA, const PairChain& cB, const int lane, const int stride, long long* tAcc, long long& tMark)
 {
     constexpr int NM = UNPAIRED ? 1 : 2;
@@ -407,8 +410,8 @@ __device__ __forceinline__ void pair_finish(const DevGraph& G, const DevTables& 
 // ---- lists of extended chains per mate (read1_extendedChains / read2_extendedChains, :3408-3420), error propagation, and the facts of the listed chains in list
 // order (PairChain: lane k holds the k-th chain of either mate's list).  cLo / cHi: the chain ranges of the pair's mates (wave-uniform).
 // Returns 1 when the pair cannot be scored (a flagged chain, an empty list, more chains / combinations / columns than the tables hold).
-template <bool UNPAIRED>
-__device__ __forceinline__ int pair_lists(const DevBatch& B, PairListLds& L, const int* cLo, const int* cHi, const int lane, int& n1, int& n2, int& mxcOut, PairChain* cL)
+template <bool UNPAIRED, class DB>
+__device__ __forceinline__ int pair_lists(const DB& B, PairListLds& L, const int* cLo, const int* cHi, const int lane, int& n1, int& n2, int& mxcOut, PairChain* cL)
 {
     constexpr int NM = UNPAIRED ? 1 : 2;
     int bad = 0;
@@ -469,6 +472,8 @@ __global__ __launch_bounds__(64, PAIR_LEAN_WAVES) void k_pair_chains(const DevGr
                                                    const uint8_t* __restrict__ deferPairs, const int deferMode, const int counterIdx,      // deferMode 1: skip deferred pairs, 2: only those
                                                    int* __restrict__ multiList, const int multiBase)
 {
+    // (descriptors as plain structs in device memory, as before: this kernel's time follows what runs beside it and the trace showed neither other form
+    //  faster, profiles/flat_to_global.txt section 4)
     const DevGraph& G = *Gp;
     const DevBatch& B = *Bp;
     __shared__ PairListLds L;
@@ -551,11 +556,13 @@ __global__ __launch_bounds__(64, PAIR_LEAN_WAVES) void k_pair_chains(const DevGr
 // trip), then combinations, first maximum, posteriors, per-position pass.  BIG = false: up to PAIR_COMB_LDS combinations in LDS and chains of up to 192 columns
 // (three columns per lane); BIG = true: the general form (combination table in the wave's HBM scratch when it does not fit, eight columns per lane).
 template <bool UNPAIRED, bool BIG>
-__global__ __launch_bounds__(64, BIG ? 3 : PAIR_MULTI_WAVES) void k_pair_multi(const DevGraph* __restrict__ Gp, const DevTables* __restrict__ Tp, const DevBatch* __restrict__ Bp,
+__global__ __launch_bounds__(64, BIG ? 3 : PAIR_MULTI_WAVES) void k_pair_multi(const DevGraph Gv, const DevBatch Bv, const DevGraph* __restrict__ Gp, const DevTables* __restrict__ Tp, const DevBatch* __restrict__ Bp,
                                                   const int* __restrict__ multiList, const int multiBase, double* __restrict__ bigLL)                    // bigLL: [gridDim.x][PAIR_COMB]
 {
-    const DevGraph& G = *Gp;
-    const DevBatch& B = *Bp;
+    // the LDS form takes the descriptors by value; the general form keeps the plain device copies (two spilled registers by value, not faster under the trace
+    // with the view: profiles/flat_to_global.txt)
+    const auto& G = desc_of<BIG ? DESC_GENERIC : DESC_VALUE>(Gv, Gp);
+    const auto& B = desc_of<BIG ? DESC_GENERIC : DESC_VALUE>(Bv, Bp);
     __shared__ PairLds P;
     const int lane = lane_id();
     const DevTables& T = *Tp;

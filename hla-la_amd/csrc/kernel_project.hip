@@ -221,12 +221,14 @@ constexpr int PJL_U = 4;            // rows of lanes the copy loops of the long-
 #define HLALA_PROJ_WPS 2           // the LDS layouts: the compiler's own choice (153 registers = three wavefronts per SIMD; their 11.7 KB of LDS allow 13 blocks per CU)
 #endif
 template <class PL>
-__global__ __launch_bounds__(64, PL::LONG ? HLALA_PROJ_LONG_WPS : HLALA_PROJ_WPS) void k_project_chains(const DevGraph* __restrict__ Gp, const DevBatch* __restrict__ Bp, const long long* contig_off, const uint8_t* contig_seq,
+__global__ __launch_bounds__(64, PL::LONG ? HLALA_PROJ_LONG_WPS : HLALA_PROJ_WPS) void k_project_chains(const DevGraph Gv, const DevBatch Bv, const DevGraph* __restrict__ Gp, const DevBatch* __restrict__ Bp, const long long* contig_off, const uint8_t* contig_seq,
                                                        const int* contig_level, char* slabs, size_t slabBytes, char* longSlabs, size_t longSlabBytes,
                                                        int deferRethread)      // 1: chains that need the chunked form and fit k_rethread_chains are left to it
 {
-    const DevGraph& G = *Gp;
-    const DevBatch& B = *Bp;
+    // the LDS layouts take the descriptors by value (their words sit in SGPRs from the start); the long-read layout, compiled for five waves per SIMD, reads the device
+    // copies through the view (by value: five spilled registers instead of two)
+    const auto& G = desc_of<PL::LONG ? DESC_VIEW : DESC_VALUE>(Gv, Gp);
+    const auto& B = desc_of<PL::LONG ? DESC_VIEW : DESC_VALUE>(Bv, Bp);
     __shared__ PL P;
     const int lane = lane_id();
     if(PL::LONG) { if(lane == 0) proj_bind(P, longSlabs + (size_t)blockIdx.x * longSlabBytes); WSYNC(); }
@@ -1420,8 +1422,8 @@ struct __align__(16) RethreadLds {
 
 __global__ __launch_bounds__(64, 6) void k_rethread_chains(const DevGraph* __restrict__ Gp, const DevBatch* __restrict__ Bp, char* slabs, size_t slabBytes)
 {
-    const DevGraph& G = *Gp;
-    const DevBatch& B = *Bp;
+    const DevGraphG& G = dev_view(Gp);
+    const DevBatchG& B = dev_view(Bp);
     __shared__ RethreadLds P;
     const int lane = lane_id();
     // back pointer of a window node: from-node rank (low half, 0xFFFF = none) | chosen in-edge, window-relative (high half) -- ONE word per node (the 8-byte
