@@ -1660,7 +1660,9 @@ int orc_exon_loglik(const hlala_exon_in* in, int long_read_mode, double* LL, int
                     if(readGenotype[0] == '_') log_likelihood_position += log_likelihood_deletion;
                     else {
                         log_likelihood_position += log_likelihood_match_mismatch;
-                        double pCorrect = PhredToPCorrect(in->pos_qual[i]);
+                        /* (the reference asserts illuminaPhred >= 0, Utilities.cpp:364: a quality byte below 33 is no valid input.  The library reads it as 33
+                           instead of ending the run, and so does this restatement) */
+                        double pCorrect = PhredToPCorrect(in->pos_qual[i] < 33 ? (unsigned char)33 : in->pos_qual[i]);
                         if(pCorrect > 0.999) pCorrect = 0.999;
                         if(pCorrect == 0) pCorrect = 0.001;
                         if(exonGenotype == readGenotype[0]) log_likelihood_position += log(pCorrect);
