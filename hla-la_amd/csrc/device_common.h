@@ -160,12 +160,12 @@ __device__ __forceinline__ u64 wave_min_u64(u64 v)
 // exp(x) for x <= 0, correctly rounded (double-double evaluation: ln2 in three exact pieces, 24 Taylor terms with double-double
 // coefficients 1/k!).  The posteriors of the pairing step decide integer outputs at the p == 1 boundary (PCorrectToPhred, Utilities.cpp:178-203):
 // the host's libm returns the correctly rounded exponential in all but rare cases, the device library's exp is off by an ulp in one call of
-// ten.  Arguments below -700 (results near the subnormal range, irrelevant to a normalised posterior) take the library exp.
+// ten.  A subnormal result (arguments below -708.39) is rounded once, from the double-double value, to a multiple of 2^-1074; below -746 it is zero.
 __device__ inline double exp_cr_nonpos(double x)
 {
 #pragma clang fp contract(off)      // the error-free transformations below must not be fused behind their back
     if(!(x < 0.0)) return 1.0;
-    if(x < -700.0) return exp(x);
+    if(x < -746.0) return 0.0;          // exp(x) < 2^-1076: rounds to zero
     const double n = rint(x * 0x1.71547652b82fep+0);
     // r = x - n ln2, exact in the first two steps (n has 11 bits, the pieces 32)
     const double r0 = fma(-n, 0x1.62e42fee00000p-1, x);
@@ -190,7 +190,16 @@ __device__ inline double exp_cr_nonpos(double x)
         const double s = mh + ch[k]; const double b2 = s - mh; double e2 = (mh - (s - b2)) + (ch[k] - b2); e2 += ml + cl[k];
         ph = s + e2; pl = e2 - (ph - s);
     }
-    return ldexp(ph, (int)n);
+    if(n >= -1021.0) return ldexp(ph, (int)n);          // ph >= 0.7: a normal result, the scaling is exact
+    // (ph + pl) 2^n in units of 2^-1074, rounded to an integer once: a and b are exact, s = fl(a + b) with its error e; only where s itself lies halfway
+    // between two integers does e decide (rint alone would round the rounded sum a second time)
+    const int sh = (int)n + 1074;
+    const double a = ldexp(ph, sh), b = ldexp(pl, sh);
+    const double s = a + b; const double sb = s - a; const double e = (a - (s - sb)) + (b - sb);
+    double k = rint(s);
+    const double fl = floor(s);
+    if(s - fl == 0.5 && e != 0.0) k = e > 0.0 ? fl + 1.0 : fl;
+    return ldexp(k, -1074);
 }
 
 __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)

@@ -192,9 +192,18 @@ typedef struct {
 
 /* Pair-level results (mapper::reads::verboseSeedChainPair, verboseSeedChain.h:318-346):
  * the selected chain of each mate with mapping qualities.  Any pointer may be NULL (that array is then not
- * transferred); of the column arrays only the first n_cols entries of a row are meaningful, the rest come back zero. */
+ * transferred); of the column arrays only the first n_cols entries of a row are meaningful, the rest come back zero.
+ *
+ * A pair (or single read) that stage C cannot score is REFUSED: pair_status = -1, best_chain = -1 for both mates, n_combinations = 0; its other
+ * entries are not meaningful (n_cols comes back 0).  That is the case when
+ *   - a record of the pair is flagged (status < 0 in hlala_chains_out: an HLALA_CHAIN_ERR_*), or a mate has no kept alignment;
+ *   - a mate has more than 64 kept alignments (records that pass the strand / duplicate filters; the number of records is not limited);
+ *   - the pair has more than 1024 combinations (kept alignments of mate 1 times those of mate 2);
+ *   - the pair has several combinations and one of its chains has more than 512 columns (one combination: any length up to max_columns).
+ * The reference has none of the three capacities.  hlala_batch_get_stats' n_errors counts flagged CHAINS: a pair refused for a capacity alone adds nothing to
+ * it; count the refused pairs from pair_status. */
 typedef struct {
-    int32_t* pair_status;   /* [n] 0 ok, <0: a chain of the pair hit an HLALA_CHAIN_ERR_*    */
+    int32_t* pair_status;   /* [n] 0 ok, -1: refused (a flagged chain, an empty list, or a capacity: see above) */
     int32_t* best_chain;    /* [2n] absolute chain index selected for each mate              */
     int32_t* n_combinations;/* [n] read1_extendedChains.size()*read2_extendedChains.size()   */
     double*  pair_ll;       /* [n] combinations_max.first (processBAM.cpp:3538)              */
@@ -248,7 +257,8 @@ int  hlala_project_chains(hlala_ctx* ctx, hlala_batch* b);
  * (verboseSeedChain.cpp:23-136), then extensionAligner::scoreOneAlignment (:52-182).         */
 int  hlala_extend_chains(hlala_ctx* ctx, hlala_batch* b);
 /* Stage C -- the pairing loop of processBAM::alignOneReadPair (mapper/processBAM.cpp:3408-3546)
- * and processBAM::assignMappingQualities (:4062-4312).                                       */
+ * and processBAM::assignMappingQualities (:4062-4312).  Capacities: 64 kept alignments per mate, 1024 combinations per pair, 512 columns per chain
+ * of a pair with several combinations; a pair beyond one of them is refused (hlala_pairs_out), the call itself succeeds.       */
 int  hlala_pair_chains(hlala_ctx* ctx, hlala_batch* b);
 /* A + B + C: processBAM::alignOneReadPair (mapper/processBAM.cpp:3129-3616) over the batch.
  * Asynchronous like the stage calls.  On a paired batch the few percent of DP calls with wide frontiers (allele-rich gene levels) and the

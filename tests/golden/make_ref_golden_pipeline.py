@@ -12,6 +12,8 @@ files directly.
   fan          the fan world around its fans (hundreds of edges per node)
   graphm       one gene window of a Graph M world, cut out of its graph and its contigs
   secondaries  identical haplotypes, a secondary for every read (p_secondary = 1.0), records in reverse order, every fourth pair on one strand
+  limits       tests/pair_edge_cases.limits(): 64 kept chains per mate, 128 / 129 / 1023 / 1024 combinations (ref_pair_limits.npz only; no larger than the largest
+               ref_pair_*.npz that was here before it)
   ref_unpaired_long.npz   single reads of 200 to 400 bases with long-read error rates (below the 512 columns up to which the product takes reads with several
                           alignments), most with a second alignment: assignMappingQualities_unpaired (the finished chains are the oracle's: an input)
   ref_unpaired_short.npz  the mates of a tie-heavy paired batch read as single reads (several records per read, mapping qualities below 1)
@@ -81,7 +83,10 @@ def cut_world(w, b, lo, hi, margin):
     return dict(graph=graph, contigs=contigs), nb
 
 
-def write(world_name, w, b, unpaired=False, long_read_mode=0, stride=STRIDE):
+MAX_PAIR_LIMITS_BYTES = 47851          # ref_pair_graphm.npz, the largest ref_pair_*.npz before ref_pair_limits.npz
+
+
+def write(world_name, w, b, unpaired=False, long_read_mode=0, stride=STRIDE, kinds=("proj", "pair"), max_bytes=MAX_BYTES):
     o = Oracle(w["graph"], w["contigs"], insert_mean=b.get("insert_mean", 200.0), insert_sd=b.get("insert_sd", 35.0), rng_seed=RNG_SEED, long_read_mode=long_read_mode, max_columns=stride)
     res = o.align_long_reads(b) if unpaired else o.align_batch(b, stop_after_projection=True)
     status = res["seeds"]["status"][:b["n_chains"]]
@@ -89,7 +94,7 @@ def write(world_name, w, b, unpaired=False, long_read_mode=0, stride=STRIDE):
     meta = dict(rng_seed=RNG_SEED, max_columns=stride, insert_mean=float(b.get("insert_mean", 200.0)), insert_sd=float(b.get("insert_sd", 35.0)), long_read_mode=long_read_mode,
                 ref_sources_sha256=rb.sources_hash(pipeline=True))
     inputs = gp.pack_inputs(w["graph"], w["contigs"], b, status == 0, meta)
-    names = ["ref_unpaired_%s.npz" % world_name] if unpaired else ["ref_proj_%s.npz" % world_name, "ref_pair_%s.npz" % world_name]
+    names = ["ref_unpaired_%s.npz" % world_name] if unpaired else ["ref_%s_%s.npz" % (k, world_name) for k in kinds]
     for name in names:
         path = os.path.join(HERE, name)
         np.savez_compressed(path, **inputs)
@@ -101,7 +106,7 @@ def write(world_name, w, b, unpaired=False, long_read_mode=0, stride=STRIDE):
             extra = ", %d units with several combinations, %d with mapQ < 1" % (int((exp["n_combinations"] > 1).sum()), int((exp["pair_mapq"] < 1).sum()))
         print("wrote %s: %d bytes, %d levels, %d nodes, %d edges, %d contigs, %d units, %d records (%d kept)%s" %
               (name, size, w["graph"]["n_levels"], w["graph"]["n_nodes"], w["graph"]["n_edges"], w["contigs"]["n_contigs"], b["n_pairs"], b["n_chains"], int((status == 0).sum()), extra))
-        assert size <= MAX_BYTES, "%s is larger than the largest fixture that was here before" % name
+        assert size <= max_bytes, "%s is larger than the largest fixture that was here before" % name
 
 
 def main():
@@ -130,6 +135,10 @@ def main():
     w = synth.make_world(seed=52, G=3000, k=2, extra_identical=3, n_largegap=2)
     b = synth.make_batch(w, 30, seed=54, p_secondary=1.0, max_secondary=6, p_random_secondary=0.3, clip_max=45)
     write("secondaries", *cut_world(w, rp.same_strand_pairs(rp.reversed_chain_order(b), every=4), 0, w["graph"]["n_levels"] - 1, 0))
+
+    import pair_edge_cases as pe
+    f = pe.limits()
+    write("limits", f["world"], f["batch"], kinds=("pair",), max_bytes=MAX_PAIR_LIMITS_BYTES)
 
     w = synth.make_world(seed=3, G=3000, k=3)
     write("long", w, {k: v for k, v in synth.make_long_batch(w, 30, seed=5, len_lo=200, len_hi=400, p_second=0.7).items()}, unpaired=True, long_read_mode=1, stride=512)

@@ -17,7 +17,7 @@ import ref_pipeline as rp
 HERE = os.path.dirname(os.path.abspath(__file__))
 WORLDS = ("corner", "gaps", "fan", "graphm", "secondaries")
 PROJ_FIXTURES = tuple("ref_proj_%s.npz" % w for w in WORLDS)
-PAIR_FIXTURES = tuple("ref_pair_%s.npz" % w for w in WORLDS)
+PAIR_FIXTURES = tuple("ref_pair_%s.npz" % w for w in WORLDS) + ("ref_pair_limits.npz",)          # limits: tests/pair_edge_cases.limits(), the pairing stage at its capacities
 UNPAIRED_FIXTURES = ("ref_unpaired_long.npz", "ref_unpaired_short.npz")
 DELTA = ("graph__node_level", "graph__edge_from", "graph__edge_to", "contigs__contig_level")
 GRAPH_KEYS = ("n_levels", "n_nodes", "n_edges", "node_level", "edge_from", "edge_to", "edge_label")

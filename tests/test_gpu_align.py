@@ -177,11 +177,15 @@ def test_known_answer_kernels(pkg, oracle):
     import decimal, math
     decimal.getcontext().prec = 60
     x = np.concatenate([[0.0, -1e-300, -1e-17, -0.5, -1.0, -math.log(2.0), -36.04365338911715, -699.9], -rng.random(6000) * 40, -rng.random(2000) * 700, -10.0 ** (-rng.random(2000) * 12)])
+    # ... and where the result is subnormal (below -708.4) down to where it rounds to zero (half of the smallest double: -745.13), and far below that
+    x = np.concatenate([x, [-700.0, -708.0, -708.3964185322641, -708.3964185322642, -744.4400719213812, -745.1332191019411, -745.1332191019412, -745.2, -746.0, -1000.0, -1e10, -1e300],
+                        -708.0 - rng.random(3000) * 37.2, -700.0 - rng.random(1000) * 8.5])
     y = np.zeros(len(x))
     ctx._check(ctx.lib.hlala_kat_exp(ctx.h, len(x), x.ctypes.data_as(pkg.c_f64p), y.ctypes.data_as(pkg.c_f64p)), "kat_exp")
     ref = np.array([float(decimal.Decimal(float(v)).exp()) for v in x])
     bad = np.nonzero(y != ref)[0]
-    assert len(bad) == 0, [(float(x[i]).hex(), float(y[i]).hex(), float(ref[i]).hex()) for i in bad[:5]]
+    assert len(bad) == 0, (len(bad), [(float(x[i]).hex(), float(y[i]).hex(), float(ref[i]).hex()) for i in bad[:5]])
+    assert np.all(ref[x < -745.2] == 0) and (ref[(x < -708.4) & (x > -745.1)] > 0).all() and int(((ref > 0) & (ref < 2.0 ** -1022)).sum()) > 2500
     host = np.array([math.exp(v) for v in x])
     print("host libm exp differs from the correctly rounded value in %d of %d arguments" % (int((host != ref).sum()), len(x)))
 
