@@ -42,6 +42,15 @@ struct DevBuf {
     void* p = nullptr; size_t bytes = 0;
 };
 
+// One DP class of the extension stage (kernel_dp.hip): launch geometry, slab pool and the instantiation of k_dp that runs it.  `launch` queues the kernel on `ws` for
+// the batch `b` (its descriptor, items, seed and read bases are the kernel's plain arguments) with `pool` = the list of batches the classes from DP_POOL_TIER on walk.
+struct DpClass {
+    int grid = 0, block = 0;
+    char* slabs = nullptr; size_t slab_bytes = 0;      // first slab of the class; bytes from one slab to the next
+    const char* name = "";                             // for error messages
+    void (*launch)(hlala_ctx* c, const DpClass& k, hipStream_t ws, hlala_batch* b, const DpPoolArgs& pool) = nullptr;
+};
+
 struct hlala_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -81,8 +90,12 @@ struct hlala_ctx {
     bool rows_all = false;        // HLALA_ROWS_ALL=1: column rows for every chain of a batch, the filters run with the projection (rounds 1-4)
     bool band_risky = false;      // HLALA_DP_BAND_RISKY=1 (tests: force fail-overs of the band kernel)
     int band_grid = 0, band_margin = 8;      // the band kernel in front of the 16-lane class (kernel_dp_band.hip): blocks (0: HLALA_DP_BAND=0) and the levels beyond the read bases left a call is taken to reach (HLALA_DP_BAND_MARGIN)
-    char* tiny_slabs = nullptr; size_t tiny_slab_bytes = 0; int tiny_grid = 0; int jf_grid = 0;      // jf_grid: blocks of the jump-free instantiation of the 16-lane class
-    char* ext_slabs = nullptr; size_t ext_slab_bytes = 0; char* wide_slabs = nullptr; char* mid_slabs = nullptr; char* large_slabs = nullptr; size_t large_slab_bytes = 0; char* huge_slabs = nullptr; size_t huge_slab_bytes = 0; int huge_grid = 0; int ext_grid = 0; int wide_grid = 0; int broad_grid = 0; int retry_grid = 0; int stitch_grid = 0; int mid_grid = 0; size_t mid_slab_bytes = 0;
+    // The DP classes by tier (0 DpTiny, 1 DpMid, 2 DpSmall, 3 DpWide, 4 DpBroad, 5 DpLarge, 6 DpHuge), filled once by hlala_create; dp_jf = the jump-free instantiation of
+    // the 16-lane class, launched in front of tier 0 on tier 0's slabs.  INVARIANT: the slabs of the tiers >= DP_SIDE_TIER belong to the context, not to a batch, and are
+    // used by ONE stream at a time: by the side stream for fused alignments, each forked from the main stream (side_fork) or queued behind the last one (flush_tail); by
+    // the main stream for a non-fused extension stage, which first flushes the tail pool and then waits for evSideTail, the end of everything queued on the side stream.
+    DpClass dp[DP_LAST_TIER + 1]; DpClass dp_jf;
+    int stitch_grid = 0;
     char* proj_slabs = nullptr; size_t proj_slab_bytes = 0; int proj_grid = 0, pair_grid = 0, pair_lean_grid = 0;
     char* rethread_slabs = nullptr; size_t rethread_slab_bytes = 0; int rethread_grid = 0;      // k_rethread_chains: back pointers of one chain per wave (short reads; HLALA_RETHREAD=0 turns the kernel off)
     double* pair_scratch = nullptr;   // [2 * pair_grid][PAIR_COMB]: combination tables of the rare pairs with more than PAIR_COMB_LDS combinations (main- and side-stream pass)
@@ -100,6 +113,21 @@ struct hlala_ctx {
     std::string err;
 };
 
+// The events of a batch.  All but the last two time the batch's stages (hlala_batch_get_stats) and are recorded on the stream their work runs on.
+enum BatchEvent {
+    EV_PROJECT_BEGIN, EV_PROJECT_END, EV_EXTEND_BEGIN, EV_EXTEND_END, EV_PAIR_BEGIN, EV_PAIR_END,      // the three stages, on the main stream
+    EV_DP_BAND_BEGIN, EV_DP_BAND_END,      // the band kernels
+    EV_DP_BEGIN, EV_DP_CLASS0_END, EV_DP_CLASS2_END, EV_DP_END,      // main stream: in front of the 16-lane class, behind it, behind the 64-lane class, behind the last class of a non-fused extension
+    EV_DP_JUMP_FREE_END,                   // between the jump-free instantiation of the 16-lane class and the general one
+    EV_DP_CLASS_BEGIN,                                       // + tier: start of a DP class, on the stream it ran on
+    EV_DP_CLASS_END = EV_DP_CLASS_BEGIN + DP_LAST_TIER + 1,  // + tier: its end
+    EV_SIDE_FORK = EV_DP_CLASS_END + DP_LAST_TIER + 1,       // main stream: the point the side stream's work of this batch waits for
+    EV_SIDE_BEGIN, EV_SIDE_END,            // side stream: in front of its first class, behind the second pairing pass
+    EV_TIMED_N, EV_MAIN = EV_TIMED_N,                  // end of the last work of this batch on the main stream (readers on `rs` wait for it; valid while mainValid)
+    EV_DONE,                               // end of its last work on the side stream (side_mark; whoever touches the batch while side_inflight waits for it)
+    EV_N
+};
+
 struct hlala_batch {
     hlala_ctx* ctx = nullptr;
     DevBatch B{};
@@ -109,16 +137,17 @@ struct hlala_batch {
     bool prepared = false;           // the filters and the position order ran when the batch was created; B.n_rows = chains that hold column rows (batch.h: chain_row)
     int n_rows_host = 0;             // ... read back with the upload's synchronisation
     bool outputs_ready = false;      // the output arrays (50 GB for a 1 M-pair batch) exist: allocated by the first stage call, not by hlala_batch_create (ensure_outputs)
-    bool side_used = false;      // the last extend of this batch ran its wide classes on the side stream (their times are between the evSide events)
-    bool side_pending = false;   // ... and hlala_pair_chains has yet to enqueue the second pairing pass behind them
-    bool tail_pooled = false;    // the batch waits in its context's tail pool: its deferred pairs are complete after flush_tail (readers and stage calls flush first)
-    bool side_inflight = false;  // work of this batch may still be running on the side stream: evDone orders everything that touches the batch after it
-    hipEvent_t evDone = nullptr;
-    hipEvent_t evMain = nullptr; bool mainValid = false;      // end of the last work of this batch on the main stream (readers on `rs` wait for it)
-    // timing events of THIS batch (created with its first stage call): ev = start / end per stage, [7] / [6] / [10] / [8] = before the 16-lane class / after it /
-    // after the 64-lane class / after the last class; evC = start / end of each DP class on the stream it ran on; evSide[0] fork point on the main stream,
-    // [1] first side-stream class starts, [6] second pairing pass done
-    hipEvent_t ev[14]{}; hipEvent_t evC[7][2]{}; hipEvent_t evSide[8]{}; hipEvent_t evJF = nullptr; /* end of the jump-free instantiation of the 16-lane class */ hipEvent_t evBand[2]{}; /* the band kernel */ bool band_used = false; bool eventsMade = false;
+    // The four side flags.  Every extension stage starts from side_used = side_pending = false (dp_prepare); only a fused alignment (hlala_align_batch) sets any.
+    //   side_used     the last extension ran classes on the side stream (side_fork): their times lie between EV_SIDE_BEGIN and EV_SIDE_END.  Kept until the next extension.
+    //   side_pending  the first stitch pass left the deferred pairs out and their second pairing pass is not queued yet: set in front of stitch_main, cleared by pair_side.
+    //                 Between calls it is true only together with tail_pooled (or after an alignment that failed half way: the pairing stage then pairs every pair itself).
+    //   tail_pooled   the batch is in c->tail: its classes from DP_POOL_TIER on, its second stitch and pairing pass wait for flush_tail.  Cleared by flush_tail, which
+    //                 everything that reads, re-runs or destroys the batch calls first (join_side, ReaderScope, hlala_batch_destroy).
+    //   side_inflight side_mark recorded EV_DONE behind work of this batch on the side stream and nothing has waited for it since: set by side_mark, cleared by join_side
+    //                 (the main stream then waits; readers and hlala_batch_destroy wait for EV_DONE themselves).  A pooled batch is in flight too: its wide class.
+    bool side_used = false, side_pending = false, tail_pooled = false, side_inflight = false;
+    hipEvent_t ev[EV_N]{}; bool eventsMade = false;      // (created with the batch's first stage call: batch_events)
+    bool mainValid = false /* EV_MAIN has been recorded */, band_used = false;
     uint32_t first_chain = 0;    // absolute index of the batch's chain 0 in the caller's numbering (hlala_batch_set_first_chain): offsets the random seeds
     float ms[3] = {0, 0, 0};
 };
@@ -137,36 +166,35 @@ struct DevGuard {
 // the same inside a function that owns temporaries or a half-built object: `cleanup` (a lambda int -> int) releases them and passes the code through
 #define HIP_TRY_F(ctx, call, cleanup) do { hipError_t e_ = (call); if(e_ != hipSuccess) { (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_); return cleanup(HLALA_E_DEVICE); } } while(0)
 
+template<class C, int TIER> static void launch_dp(hlala_ctx* c, const DpClass& k, hipStream_t ws, hlala_batch* b, const DpPoolArgs& pool)
+{
+    hipLaunchKernelGGL((k_dp<C, TIER>), dim3(k.grid), dim3(k.block), 0, ws, c->dG, b->dB, (DpItem*)b->B.dp_items, k.slabs, k.slab_bytes, c->params.rng_seed + 2u * b->first_chain,
+                       c->G.nrec_out, c->G.nrec_in, b->B.read_bases, pool);
+}
+template<class C, int TIER> static DpClass dp_class(int grid, size_t slab_bytes, const char* name) { return DpClass{grid, C::THREADS, nullptr, slab_bytes, name, launch_dp<C, TIER>}; }      // (hlala_create allocates the slabs)
+
 // everything on the main stream that reads or rewrites a batch goes behind the side-stream work of its last fused alignment
 static int flush_tail(hlala_ctx* c);
 static int join_side(hlala_ctx* c, hlala_batch* b)
 {
     if(b->tail_pooled) { int rf = flush_tail(c); if(rf) return rf; }
     if(b->side_inflight) {
-        HIP_TRY(c, hipStreamWaitEvent(c->stream, b->evDone, 0));
-        // evMain is what hlala_batch_destroy and the readers wait for once side_inflight is cleared: it has to lie BEHIND the wait just queued even if the
+        HIP_TRY(c, hipStreamWaitEvent(c->stream, b->ev[EV_DONE], 0));
+        // EV_MAIN is what hlala_batch_destroy and the readers wait for once side_inflight is cleared: it has to lie BEHIND the wait just queued even if the
         // stage call that joined returns early (state / launch error) and never reaches its own mark_main
-        if(b->evMain) { HIP_TRY(c, hipEventRecord(b->evMain, c->stream)); b->mainValid = true; b->side_inflight = false; }
+        if(b->ev[EV_MAIN]) { HIP_TRY(c, hipEventRecord(b->ev[EV_MAIN], c->stream)); b->mainValid = true; b->side_inflight = false; }
     }
     return HLALA_OK;
 }
 static int batch_events(hlala_ctx* c, hlala_batch* b)
 {
     if(b->eventsMade) return HLALA_OK;
-    for(int i = 0; i < 14; i++) HIP_TRY(c, hipEventCreate(&b->ev[i]));
-    for(int i = 0; i < 8; i++) HIP_TRY(c, hipEventCreate(&b->evSide[i]));
-    for(int i = 0; i < 14; i++) HIP_TRY(c, hipEventCreate(&b->evC[i / 2][i % 2]));
-    HIP_TRY(c, hipEventCreate(&b->evJF));
-    for(int i = 0; i < 2; i++) HIP_TRY(c, hipEventCreate(&b->evBand[i]));
-    HIP_TRY(c, hipEventCreateWithFlags(&b->evMain, hipEventDisableTiming));
+    for(int i = 0; i < EV_N; i++) HIP_TRY(c, hipEventCreateWithFlags(&b->ev[i], i < EV_TIMED_N ? hipEventDefault : hipEventDisableTiming));
     b->eventsMade = true;
     return HLALA_OK;
 }
-static int mark_main(hlala_ctx* c, hlala_batch* b)       // end of a stage call: what readers of the batch on the reader stream wait for
-{
-    HIP_TRY(c, hipEventRecord(b->evMain, c->stream)); b->mainValid = true;
-    return HLALA_OK;
-}
+// end of a stage call: what readers of the batch on the reader stream wait for
+static int mark_main(hlala_ctx* c, hlala_batch* b) { HIP_TRY(c, hipEventRecord(b->ev[EV_MAIN], c->stream)); b->mainValid = true; return HLALA_OK; }
 // A call that only reads a batch (or works on caller data) runs on the context's reader stream, behind the batch's own work on the main and the side
 // stream -- not behind whatever the caller queued for other batches since.  (Calls on one context are serialised by the caller: `active` is plain state.)
 struct ReaderScope {
@@ -177,8 +205,8 @@ struct ReaderScope {
         if(b && b->tail_pooled) { rc = flush_tail(c); if(rc) return; }          // the batch's tail classes are still pooled: run them now (with whatever the pool holds)
         c->active = c->rs;
         hipError_t e = hipSuccess;
-        if(b && b->mainValid) e = hipStreamWaitEvent(c->rs, b->evMain, 0);
-        if(e == hipSuccess && b && b->side_inflight) e = hipStreamWaitEvent(c->rs, b->evDone, 0);
+        if(b && b->mainValid) e = hipStreamWaitEvent(c->rs, b->ev[EV_MAIN], 0);
+        if(e == hipSuccess && b && b->side_inflight) e = hipStreamWaitEvent(c->rs, b->ev[EV_DONE], 0);
         if(e != hipSuccess) { c->err = std::string("hipStreamWaitEvent: ") + hipGetErrorString(e); rc = HLALA_E_DEVICE; }
     }
     ~ReaderScope() { if(c) c->active = c->stream; }
@@ -469,9 +497,6 @@ int hlala_create(hlala_ctx** out, int device, void* stream, const hlala_graph_de
         if(hipMemsetAsync(*out, 0, bytes, c->active) != hipSuccess) { c->err = std::string("hipMemset(") + what + ") failed"; return HLALA_E_DEVICE; }
         return 0;
     };
-    c->tiny_grid = cus * 4 * DpTiny::WAVES;
-    c->tiny_slab_bytes = dp_slab_bytes<DpTiny>();
-    c->jf_grid = cus * 4 * DpTinyJF::WAVES;
     c->band_grid = cus * 20;          // a few KB of LDS per block, five waves per SIMD (96 VGPRs, nothing spilled)
     if(const char* e = getenv("HLALA_DP_BAND")) { if(atoi(e) == 0) c->band_grid = 0; }      // (A/B and parity: every call in the hashed-frontier classes)
     if(const char* e = getenv("HLALA_DP_BAND_RISKY")) c->band_risky = atoi(e) != 0;
@@ -480,24 +505,28 @@ int hlala_create(hlala_ctx** out, int device, void* stream, const hlala_graph_de
     if(const char* e = getenv("HLALA_POOL_CAP_GB")) { const long g = atol(e); if(g >= 0 && g <= 1024) c->pool_cap = (size_t)g << 30; }
     if(const char* e = getenv("HLALA_DP_BAND_MARGIN")) { const int m = atoi(e); if(m >= 0 && m <= 24) c->band_margin = m; }
     if(const char* e = getenv("HLALA_DP_JF_MARGIN")) { const int m = atoi(e); if(m >= 0 && m <= 200) c->jf_margin = m; }      // (A/B: levels beyond the read bases left that a jump-free call may reach)
-    c->ext_grid = cus * 20;
-    c->mid_grid = cus * 16; c->mid_slab_bytes = dp_slab_bytes<DpMid>();
-    c->retry_grid = cus;
-    c->broad_grid = cus * 3;         // three DpBroad blocks per CU (48 KB of LDS each), slabs of the large layout
-
-    c->wide_grid = cus * 7;          // LDS: seven DpWide blocks per CU (22 KB each); slabs of the 64-lane layout
     c->stitch_grid = cus * 20;        // k_stitch_chains: five waves per SIMD (92 VGPRs, nothing spilled)
     if(const char* e = getenv("HLALA_STITCH_BY_ROW")) c->stitch_by_row = atoi(e) != 0;
-    c->ext_slab_bytes = dp_slab_bytes<DpSmall>() > dp_slab_bytes<DpWide>() ? dp_slab_bytes<DpSmall>() : dp_slab_bytes<DpWide>();
-    c->large_slab_bytes = dp_slab_bytes<DpLarge>() > dp_slab_bytes<DpBroad>() ? dp_slab_bytes<DpLarge>() : dp_slab_bytes<DpBroad>();       // one / three blocks per CU: a few MB each
-    c->huge_grid = cus / 4 > 0 ? cus / 4 : 1;      // the in-memory backstop class: a handful of DP calls per million pairs
-    c->huge_slab_bytes = dp_inmemory_bytes<DpHuge>();
-    if((rc = slab_pool(&c->tiny_slabs, c->tiny_slab_bytes * (size_t)(64 / DpTiny::GW) * (size_t)std::max(c->tiny_grid, c->jf_grid), "16-lane DP slabs"))) return fail(rc);
-    if((rc = slab_pool(&c->mid_slabs, c->mid_slab_bytes * (size_t)(64 / DpMid::GW) * (size_t)c->mid_grid, "32-lane DP slabs"))) return fail(rc);
-    if((rc = slab_pool(&c->ext_slabs, c->ext_slab_bytes * (size_t)c->ext_grid, "64-lane DP slabs"))) return fail(rc);
-    if((rc = slab_pool(&c->wide_slabs, c->ext_slab_bytes * (size_t)c->wide_grid, "wide-class DP slabs"))) return fail(rc);
-    if((rc = slab_pool(&c->large_slabs, c->large_slab_bytes * (size_t)(c->broad_grid + c->retry_grid), "large-class DP slabs"))) return fail(rc);       // broad blocks first, then the large ones
-    if((rc = slab_pool(&c->huge_slabs, c->huge_slab_bytes * (size_t)c->huge_grid, "in-memory DP class"))) return fail(rc);
+    // The table of DP classes: blocks, bytes per slab, then one pool per slab layout.  The 64-lane and the wide class have slabs of one size (the larger layout of the two),
+    // so have the broad and the large class, which also share a pool: broad blocks first, then the large ones.
+    const size_t extBytes = std::max(dp_slab_bytes<DpSmall>(), dp_slab_bytes<DpWide>()), largeBytes = std::max(dp_slab_bytes<DpLarge>(), dp_slab_bytes<DpBroad>());      // (large: one / three blocks per CU, a few MB each)
+    DpClass* const dp = c->dp;
+    c->dp_jf = dp_class<DpTinyJF, 0>(cus * 4 * DpTinyJF::WAVES, dp_slab_bytes<DpTiny>(), "k_dp<DpTinyJF>");
+    dp[0] = dp_class<DpTiny, 0>(cus * 4 * DpTiny::WAVES, dp_slab_bytes<DpTiny>(), "k_dp<DpTiny>");
+    dp[1] = dp_class<DpMid, 1>(cus * 16, dp_slab_bytes<DpMid>(), "k_dp<DpMid>");
+    dp[2] = dp_class<DpSmall, 2>(cus * 20, extBytes, "k_dp<DpSmall>");
+    dp[3] = dp_class<DpWide, 3>(cus * 7, extBytes, "k_dp<DpWide>");              // LDS: seven DpWide blocks per CU (22 KB each)
+    dp[4] = dp_class<DpBroad, 4>(cus * 3, largeBytes, "k_dp<DpBroad>");          // three DpBroad blocks per CU (48 KB of LDS each)
+    dp[5] = dp_class<DpLarge, 5>(cus, largeBytes, "k_dp<DpLarge>");
+    dp[6] = dp_class<DpHuge, 6>(cus / 4 > 0 ? cus / 4 : 1, dp_inmemory_bytes<DpHuge>(), "k_dp<DpHuge>");      // the in-memory backstop class: a handful of DP calls per million pairs
+    if((rc = slab_pool(&dp[0].slabs, dp[0].slab_bytes * (size_t)(64 / DpTiny::GW) * (size_t)std::max(dp[0].grid, c->dp_jf.grid), "16-lane DP slabs"))) return fail(rc);
+    c->dp_jf.slabs = dp[0].slabs;
+    if((rc = slab_pool(&dp[1].slabs, dp[1].slab_bytes * (size_t)(64 / DpMid::GW) * (size_t)dp[1].grid, "32-lane DP slabs"))) return fail(rc);
+    if((rc = slab_pool(&dp[2].slabs, extBytes * (size_t)dp[2].grid, "64-lane DP slabs"))) return fail(rc);
+    if((rc = slab_pool(&dp[3].slabs, extBytes * (size_t)dp[3].grid, "wide-class DP slabs"))) return fail(rc);
+    if((rc = slab_pool(&dp[4].slabs, largeBytes * (size_t)(dp[4].grid + dp[5].grid), "large-class DP slabs"))) return fail(rc);
+    dp[5].slabs = dp[4].slabs + largeBytes * (size_t)dp[4].grid;
+    if((rc = slab_pool(&dp[6].slabs, dp[6].slab_bytes * (size_t)dp[6].grid, "in-memory DP class"))) return fail(rc);
     // k_project_chains<384 columns>: 143 VGPRs = three waves per SIMD = 12 resident blocks per CU (its 11.7 KB of LDS would allow 13); the 512-column
     // layout: 173 VGPRs = two per SIMD (-Rpass-analysis=kernel-resource-usage; a cap of 128 VGPRs for a fourth wave costs 287 spilled SGPRs and wins one block)
     c->proj_grid = cus * (c->params.max_columns <= PROJ_CAP_SHORT ? 12 : 8); c->pair_grid = cus * 16; c->pair_lean_grid = cus * 24;      // k_pair_multi<., false>: four waves per SIMD (125 registers, nothing spilled); k_pair_chains (0.7 KB of LDS, 80 registers): six
@@ -882,16 +911,11 @@ void hlala_batch_destroy(hlala_batch* b)
         if(b->tail_pooled) (void)flush_tail(c);       // (its pending classes run with whatever the pool holds; should that fail, the batch leaves the pool below)
         c->tail.erase(std::remove(c->tail.begin(), c->tail.end(), b), c->tail.end());
         c->batches.erase(b);
-        if(b->side_inflight) (void)hipEventSynchronize(b->evDone);
-        if(b->mainValid) (void)hipEventSynchronize(b->evMain);       // nothing of this batch may still be running when its buffers are handed to the next one (readers and uploads return synchronised)
+        if(b->side_inflight) (void)hipEventSynchronize(b->ev[EV_DONE]);
+        if(b->mainValid) (void)hipEventSynchronize(b->ev[EV_MAIN]);       // nothing of this batch may still be running when its buffers are handed to the next one (readers and uploads return synchronised)
         for(void* p : b->allocs) pool_release(c, p);
     } else for(void* p : b->allocs) if(p) (void)hipFree(p);
-    if(b->evDone) (void)hipEventDestroy(b->evDone);
-    if(b->evMain) (void)hipEventDestroy(b->evMain);
-    for(int i = 0; i < 14; i++) { if(b->ev[i]) (void)hipEventDestroy(b->ev[i]); if(b->evC[i / 2][i % 2]) (void)hipEventDestroy(b->evC[i / 2][i % 2]); }
-    for(int i = 0; i < 8; i++) if(b->evSide[i]) (void)hipEventDestroy(b->evSide[i]);
-    if(b->evJF) (void)hipEventDestroy(b->evJF);
-    for(int i = 0; i < 2; i++) if(b->evBand[i]) (void)hipEventDestroy(b->evBand[i]);
+    for(hipEvent_t e : b->ev) if(e) (void)hipEventDestroy(e);
     delete b;
 }
 
@@ -913,7 +937,7 @@ int hlala_project_chains(hlala_ctx* c, hlala_batch* b)
     DevBatch& B = b->B;
     HIP_TRY(c, hipMemsetAsync(B.work_counter, 0, WC_N * sizeof(int), c->active));
     HIP_TRY(c, hipMemsetAsync(B.counters, 0, 32 * sizeof(u64), c->active));
-    HIP_TRY(c, hipEventRecord(b->ev[0], c->active));
+    HIP_TRY(c, hipEventRecord(b->ev[EV_PROJECT_BEGIN], c->active));
     if(B.n_chains > 0) {
         int threads = 256, blocks = (B.n_reads + threads - 1) / threads;
         // (the filters and the position order of a batch ran when it was created, hlala_batch_create: they read inputs only)
@@ -942,231 +966,221 @@ int hlala_project_chains(hlala_ctx* c, hlala_batch* b)
             rc = check_launch(c, "k_rethread_chains"); if(rc) return rc;
         }
     }
-    HIP_TRY(c, hipEventRecord(b->ev[1], c->active));
+    HIP_TRY(c, hipEventRecord(b->ev[EV_PROJECT_END], c->active));
     b->staged |= 1;
     return mark_main(c, b);
 }
 
-static int extend_impl(hlala_ctx* c, hlala_batch* b, bool fused, int phase = 0);
-int hlala_extend_chains(hlala_ctx* c, hlala_batch* b) { return extend_impl(c, b, false); }
-
-// fused = called from hlala_align_batch on a paired batch.  The 16- / 32- / 64-lane classes hold all but a few percent of the DP calls; the rest (wide,
-// broad, large, in-memory) are few, long calls that cannot fill the chip.  Fused, they run on the side stream, followed there by a second stitch /
-// pairing pass over the pairs that own them (pair_deferred, set by the DP kernels when they hand an item to one of these classes), while the main
-// stream stitches and pairs everything else and is then free for the caller's next batch.  b->evDone orders later users of the batch behind the side work.
-// phase (fused only; hlala_align_batch): 0 = the whole stage, the side-stream classes forked off as soon as the 64-lane class is done; 1 = the main-stream part alone (classes
-// before DP_SIDE_TIER, first stitch pass), 2 = the side-stream part alone (the later classes, second stitch pass) -- queued by hlala_align_batch AFTER the main stream's
-// pairing pass: k_pair_chains is a short, latency-bound kernel that needs 6 KB of LDS per wavefront, and beside the wide class (seven blocks of 22 KB per CU: 154 of a
-// CU's 160 KB) hardly a block of it fits: 20.9 ms for a pairing pass that takes 4.1 ms alone (profiles/r05_experiments.txt, 19).  Not the default: the next batch's
-// projection (11.7 KB per block) then meets the wide class instead.
-static int extend_impl(hlala_ctx* c, hlala_batch* b, bool fused, int phase)
+#define STEP(call) do { int rc_ = (call); if(rc_) return rc_; } while(0)
+// Extension and pairing are written as STEPS -- each queues one thing on one stream; without a stream argument, on the main stream (c->active) -- and as five SCHEDULES,
+// plain sequences of steps: the stage calls, the three fused alignments of hlala_align_batch (default, HLALA_SIDE_AFTER_PAIR=1, tail pool) and flush_tail.
+// Fused (hlala_align_batch on a paired batch).  The 16- / 32- / 64-lane classes hold all but a few percent of the DP calls; the rest (wide, broad, large, in-memory) are
+// few, long calls that cannot fill the chip.  Fused, they run on the side stream, followed there by a second stitch / pairing pass over the pairs that own them
+// (pair_deferred, set by the DP kernels when they hand an item to one of these classes), while the main stream stitches and pairs everything else and is then free for
+// the caller's next batch.  EV_DONE orders later users of the batch behind the side work.
+static bool fusable(const hlala_batch* b) { const DevBatch& B = b->B; return !(B.unpaired || B.from_seeds || B.n_pairs <= 0 || B.n_chains <= 0); }
+// start of every extension: the stage's counters, then (a batch with chains) the DP items and their lists
+static int dp_prepare(hlala_ctx* c, hlala_batch* b)
 {
-    DEV_GUARD(c);
-    if(!c || !b) return HLALA_E_ARG;
-    if(!(b->staged & 1)) { c->err = "hlala_extend_chains before seed chains exist"; return HLALA_E_STATE; }
-    // phases 3 / 4 (round 6, tail pool): 3 = the main-stream part + the first side-stream class (wide) of THIS batch, the later classes left pending; 4 = the second stitch
-    // pass alone, queued by flush_tail behind the pooled launches of those classes
-    const bool sidePartOnly = phase == 2 || phase == 4;
-    if(!sidePartOnly) { int rj = join_side(c, b); if(rj) return rj; }
-    { int re = batch_events(c, b); if(re) return re; }
     DevBatch& B = b->B;
-    if(B.unpaired || B.from_seeds || B.n_pairs <= 0 || B.n_chains <= 0) { fused = false; if(sidePartOnly) return HLALA_OK; phase = 0; }
-    const bool mainPart = !sidePartOnly;
-    if(mainPart) {
     b->side_used = false; b->side_pending = false;
     if(B.n_pairs > 0) HIP_TRY(c, hipMemsetAsync(B.pair_deferred, 0, (size_t)B.n_pairs, c->active));
     HIP_TRY(c, hipMemsetAsync(B.work_counter + 1, 0, sizeof(int), c->active));
     HIP_TRY(c, hipMemsetAsync(B.work_counter + 4, 0, (WC_N - 4) * sizeof(int), c->active));       // [4..6] jump-free lists, [7..] stitch, DP items, retry lists, band / fail-over lists
     if(B.from_seeds) HIP_TRY(c, hipMemsetAsync(B.counters, 0, 32 * sizeof(u64), c->active));
-    HIP_TRY(c, hipEventRecord(b->ev[2], c->active));
-    }
-    if(B.n_chains > 0) {
-        DpItem* items = (DpItem*)B.dp_items;
-        const u32 seed = c->params.rng_seed + 2u * b->first_chain;
-        int rc = 0;
-        if(mainPart) {
-        HIP_TRY(c, hipMemsetAsync(B.dp_alias_head, 0xFF, (size_t)2 * B.n_chains * sizeof(int), c->active));       // -1: k_dp_items links the duplicates of a DP to it
-        HIP_TRY(c, hipMemsetAsync(B.dp_alias_next, 0xFF, (size_t)2 * B.n_chains * sizeof(int), c->active));
-        // items, then the ten dense lists of the first classes (three band lists, jump-free, general; left / right each) in position order: counts per block, their scan, the slots
-        HIP_TRY(c, hipMemsetAsync(B.dp_blk, 0, ((size_t)DPL_N * B.dp_nblk + 1) * sizeof(int), c->active));
-        hipLaunchKernelGGL(k_dp_items, dim3(B.dp_nblk), dim3(256), 0, c->active, c->G, b->B, items);
-        rc = check_launch(c, "k_dp_items"); if(rc) return rc;
-        hipLaunchKernelGGL(k_order_scan, dim3(1), dim3(ORDER_SCAN_THREADS), 0, c->active, B.dp_blk, DPL_N * B.dp_nblk + 1);
-        hipLaunchKernelGGL(k_dp_lists, dim3(B.dp_nblk), dim3(256), 0, c->active, b->B, (const DpItem*)items);
-        rc = check_launch(c, "k_dp_lists"); if(rc) return rc;
-        }
-        // every DP item first runs in the 16-lane class; the item count lives on the device, idle groups leave at once.
-        // Items that outgrew it: two DPs per wave, then one wave per DP, then the classes with wider frontiers (fewer blocks per CU).
-        // Each class is timed with its own pair of events on the stream it runs on (evC); ev[7] / ev[6] / ev[10] keep marking the start of the 16-lane
-        // class, its end and the end of the 64-lane class on the main stream.
-        hipStream_t ws = c->active;
-        const DpPoolArgs noPool{};                                   // classes before DP_POOL_TIER take the batch of their plain arguments
-        DpPoolArgs one{}; one.n = 1; one.seed[0] = seed; one.B[0] = b->dB; one.items[0] = items; one.bases[0] = (const uint8_t*)B.read_bases;      // the later ones a list of batches: this one
-        auto run_class = [&](int tier) -> int {
-            if(fused && tier == DP_SIDE_TIER) {
-                if(!b->evDone) HIP_TRY(c, hipEventCreateWithFlags(&b->evDone, hipEventDisableTiming));
-                HIP_TRY(c, hipEventRecord(b->evSide[0], c->active)); HIP_TRY(c, hipStreamWaitEvent(c->side, b->evSide[0], 0));
-                ws = c->side;
-                HIP_TRY(c, hipEventRecord(b->evSide[1], c->side));
-            }
-            // the slabs of the classes from DP_SIDE_TIER on belong to the context: a launch on the main stream (stage calls, unpaired and from-seeds batches)
-            // goes behind whatever an earlier fused alignment of ANOTHER batch still has queued on the side stream
-            if(!fused && tier == DP_SIDE_TIER && c->sideTailValid) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->evSideTail, 0));
-            HIP_TRY(c, hipEventRecord(b->evC[tier][0], ws));
-            switch(tier) {
-            case 0: {
-                // the calls that meet no gap-path jump in the instantiation without the early-cell machinery, then the others (same slabs: one after the other)
-                hipLaunchKernelGGL((k_dp<DpTinyJF, 0>), dim3(c->jf_grid), dim3(DpTinyJF::THREADS), 0, ws, c->dG, b->dB, items, c->tiny_slabs, c->tiny_slab_bytes, seed, c->G.nrec_out, c->G.nrec_in, B.read_bases, noPool);
-                int rcj = check_launch(c, "k_dp<DpTinyJF>"); if(rcj) return rcj;
-                HIP_TRY(c, hipEventRecord(b->evJF, ws));
-                hipLaunchKernelGGL((k_dp<DpTiny, 0>), dim3(c->tiny_grid), dim3(DpTiny::THREADS), 0, ws, c->dG, b->dB, items, c->tiny_slabs, c->tiny_slab_bytes, seed, c->G.nrec_out, c->G.nrec_in, B.read_bases, noPool); break; }
-            case 1: hipLaunchKernelGGL((k_dp<DpMid, 1>), dim3(c->mid_grid), dim3(DpMid::THREADS), 0, ws, c->dG, b->dB, items, c->mid_slabs, c->mid_slab_bytes, seed, c->G.nrec_out, c->G.nrec_in, B.read_bases, noPool); break;
-            case 2: hipLaunchKernelGGL((k_dp<DpSmall, 2>), dim3(c->ext_grid), dim3(DpSmall::THREADS), 0, ws, c->dG, b->dB, items, c->ext_slabs, c->ext_slab_bytes, seed, c->G.nrec_out, c->G.nrec_in, B.read_bases, noPool); break;
-            case 3: hipLaunchKernelGGL((k_dp<DpWide, 3>), dim3(c->wide_grid), dim3(DpWide::THREADS), 0, ws, c->dG, b->dB, items, c->wide_slabs, c->ext_slab_bytes, seed, c->G.nrec_out, c->G.nrec_in, B.read_bases, noPool); break;
-            case 4: hipLaunchKernelGGL((k_dp<DpBroad, 4>), dim3(c->broad_grid), dim3(DpBroad::THREADS), 0, ws, c->dG, b->dB, items, c->large_slabs, c->large_slab_bytes, seed, c->G.nrec_out, c->G.nrec_in, B.read_bases, one); break;
-            case 5: hipLaunchKernelGGL((k_dp<DpLarge, 5>), dim3(c->retry_grid), dim3(DpLarge::THREADS), 0, ws, c->dG, b->dB, items, c->large_slabs + c->large_slab_bytes * (size_t)c->broad_grid, c->large_slab_bytes, seed, c->G.nrec_out, c->G.nrec_in, B.read_bases, one); break;
-            default: hipLaunchKernelGGL((k_dp<DpHuge, 6>), dim3(c->huge_grid), dim3(DpHuge::THREADS), 0, ws, c->dG, b->dB, items, c->huge_slabs, c->huge_slab_bytes, seed, c->G.nrec_out, c->G.nrec_in, B.read_bases, one); break;
-            }
-            int rc_ = check_launch(c, "k_dp"); if(rc_) return rc_;
-            HIP_TRY(c, hipEventRecord(b->evC[tier][1], ws));
-            return 0;
-        };
-        if(mainPart) {
-        // calls on linear stretches of the graph first: anti-diagonals in registers, four calls per wavefront (kernel_dp_band.hip); what it cannot finish is on the
-        // fail-over list the general 16-lane instantiation draws after its own
-        b->band_used = c->band_grid > 0;
-        if(b->band_used) {
-            HIP_TRY(c, hipEventRecord(b->evBand[0], c->active));
-            hipLaunchKernelGGL((k_dp_band<16>), dim3(c->band_grid), dim3(64), 0, c->active, c->G, b->B, (const DpItem*)items, seed, (const uint8_t*)B.read_bases, c->G.lin_label, c->G.lin_eid);
-            hipLaunchKernelGGL((k_dp_band<32>), dim3(c->band_grid), dim3(64), 0, c->active, c->G, b->B, (const DpItem*)items, seed, (const uint8_t*)B.read_bases, c->G.lin_label, c->G.lin_eid);
-            hipLaunchKernelGGL((k_dp_band<64>), dim3(c->band_grid), dim3(64), 0, c->active, c->G, b->B, (const DpItem*)items, seed, (const uint8_t*)B.read_bases, c->G.lin_label, c->G.lin_eid);
-            rc = check_launch(c, "k_dp_band"); if(rc) return rc;
-            HIP_TRY(c, hipEventRecord(b->evBand[1], c->active));
-        }
-        HIP_TRY(c, hipEventRecord(b->ev[7], c->active));
-        rc = run_class(0); if(rc) return rc;
-        HIP_TRY(c, hipEventRecord(b->ev[6], c->active));
-        }
-        for(int tier = 1; tier <= DP_LAST_TIER; tier++) {
-            if(phase == 4) break;
-            if(phase == 1 && tier >= DP_SIDE_TIER) break;
-            if(phase == 2 && tier < DP_SIDE_TIER) continue;
-            if(phase == 3 && tier >= DP_POOL_TIER) break;
-            rc = run_class(tier); if(rc) return rc;
-            if(tier == 2) HIP_TRY(c, hipEventRecord(b->ev[10], c->active));
-        }
-        if(!fused) HIP_TRY(c, hipEventRecord(b->ev[8], c->active));
-        const int sgrid = B.n_chains < c->stitch_grid ? B.n_chains : c->stitch_grid;
-        if(fused && phase == 1) b->side_pending = true;
-        if(fused && phase == 3) { b->side_pending = true; b->side_used = true; }
-        if(fused && phase != 1 && phase != 3) {
-            // second pass (side): the chains of the deferred pairs, work counter 36; first pass (main): all the others, work counter 7
-            { const int pgrid = (B.n_pairs + 63) / 64, cap = c->stitch_grid / 20;       // the second pass sweeps the pairs' flags, 64 per wave and round: one wave per CU finds room beside the next batch's persistent kernels
-              hipLaunchKernelGGL(k_stitch_chains, dim3(pgrid < cap ? (pgrid > 0 ? pgrid : 1) : cap), dim3(64), 0, c->side, c->G, c->dT, b->B, (const uint8_t*)B.pair_deferred, 2, 0, 0); }
-            rc = check_launch(c, "k_stitch_chains (side)"); if(rc) return rc;
-            HIP_TRY(c, hipEventRecord(b->evDone, c->side));
-            HIP_TRY(c, hipEventRecord(c->evSideTail, c->side)); c->sideTailValid = true;
-            b->side_inflight = true; b->side_used = true; b->side_pending = true;
-        }
-        if(mainPart) {
-        hipLaunchKernelGGL(k_stitch_chains, dim3(sgrid), dim3(64), 0, c->active, c->G, c->dT, b->B, (const uint8_t*)B.pair_deferred, fused ? 1 : 0, c->stitch_draw, c->stitch_by_row);
-        rc = check_launch(c, "k_stitch_chains"); if(rc) return rc;
-        }
-    }
-    if(sidePartOnly) return HLALA_OK;
-    HIP_TRY(c, hipEventRecord(b->ev[3], c->active));
-    b->staged |= 2;
-    return mark_main(c, b);
+    HIP_TRY(c, hipEventRecord(b->ev[EV_EXTEND_BEGIN], c->active));
+    if(B.n_chains <= 0) return HLALA_OK;
+    DpItem* items = (DpItem*)B.dp_items;
+    HIP_TRY(c, hipMemsetAsync(B.dp_alias_head, 0xFF, (size_t)2 * B.n_chains * sizeof(int), c->active));       // -1: k_dp_items links the duplicates of a DP to it
+    HIP_TRY(c, hipMemsetAsync(B.dp_alias_next, 0xFF, (size_t)2 * B.n_chains * sizeof(int), c->active));
+    // items, then the ten dense lists of the first classes (three band lists, jump-free, general; left / right each) in position order: counts per block, their scan, the slots
+    HIP_TRY(c, hipMemsetAsync(B.dp_blk, 0, ((size_t)DPL_N * B.dp_nblk + 1) * sizeof(int), c->active));
+    hipLaunchKernelGGL(k_dp_items, dim3(B.dp_nblk), dim3(256), 0, c->active, c->G, b->B, items);
+    STEP(check_launch(c, "k_dp_items"));
+    hipLaunchKernelGGL(k_order_scan, dim3(1), dim3(ORDER_SCAN_THREADS), 0, c->active, B.dp_blk, DPL_N * B.dp_nblk + 1);
+    hipLaunchKernelGGL(k_dp_lists, dim3(B.dp_nblk), dim3(256), 0, c->active, b->B, (const DpItem*)items);
+    return check_launch(c, "k_dp_lists");
 }
+// calls on linear stretches of the graph first: anti-diagonals in registers, four calls per wavefront (kernel_dp_band.hip); what it cannot finish is on the
+// fail-over list the general 16-lane instantiation draws after its own
+static int dp_band(hlala_ctx* c, hlala_batch* b)
+{
+    DevBatch& B = b->B;
+    b->band_used = c->band_grid > 0;
+    if(!b->band_used) return HLALA_OK;
+    const DpItem* items = (const DpItem*)B.dp_items; const u32 seed = c->params.rng_seed + 2u * b->first_chain;
+    HIP_TRY(c, hipEventRecord(b->ev[EV_DP_BAND_BEGIN], c->active));
+    hipLaunchKernelGGL((k_dp_band<16>), dim3(c->band_grid), dim3(64), 0, c->active, c->G, b->B, items, seed, (const uint8_t*)B.read_bases, c->G.lin_label, c->G.lin_eid);
+    hipLaunchKernelGGL((k_dp_band<32>), dim3(c->band_grid), dim3(64), 0, c->active, c->G, b->B, items, seed, (const uint8_t*)B.read_bases, c->G.lin_label, c->G.lin_eid);
+    hipLaunchKernelGGL((k_dp_band<64>), dim3(c->band_grid), dim3(64), 0, c->active, c->G, b->B, items, seed, (const uint8_t*)B.read_bases, c->G.lin_label, c->G.lin_eid);
+    STEP(check_launch(c, "k_dp_band"));
+    HIP_TRY(c, hipEventRecord(b->ev[EV_DP_BAND_END], c->active)); return HLALA_OK;
+}
+// The DP classes `first` .. `last` on `ws`, for the n batches of `bs`: one batch, or (tiers from DP_POOL_TIER on only) the batches of a tail pool in one launch per class.
+// Every DP item first runs in the 16-lane class; the item count lives on the device, idle groups leave at once.  Items that outgrew it: two DPs per wave, then one wave
+// per DP, then the classes with wider frontiers (fewer blocks per CU).  Each class is timed with its own pair of events on the stream it runs on; EV_DP_BEGIN /
+// EV_DP_CLASS0_END / EV_DP_CLASS2_END mark the start of the 16-lane class, its end and the end of the 64-lane class on the main stream.
+static int dp_classes(hlala_ctx* c, hlala_batch* const* bs, int n, int first, int last, hipStream_t ws)
+{
+    const DpPoolArgs noPool{};       // classes before DP_POOL_TIER take the batch of their plain arguments, the later ones a list of batches
+    DpPoolArgs pool{}; pool.n = n; hlala_batch* b0 = bs[0];
+    for(int i = 0; i < n; i++) { const hlala_batch* b = bs[i]; pool.seed[i] = c->params.rng_seed + 2u * b->first_chain; pool.B[i] = b->dB; pool.items[i] = (const DpItem*)b->B.dp_items; pool.bases[i] = (const uint8_t*)b->B.read_bases; }
+    for(int tier = first; tier <= last; tier++) {
+        const DpClass& k = c->dp[tier];
+        if(tier == 0) HIP_TRY(c, hipEventRecord(b0->ev[EV_DP_BEGIN], c->active));
+        for(int i = 0; i < n; i++) HIP_TRY(c, hipEventRecord(bs[i]->ev[EV_DP_CLASS_BEGIN + tier], ws));
+        if(tier == 0) {
+            // the calls that meet no gap-path jump in the instantiation without the early-cell machinery, then the others (same slabs: one after the other)
+            c->dp_jf.launch(c, c->dp_jf, ws, b0, noPool);
+            STEP(check_launch(c, c->dp_jf.name));
+            HIP_TRY(c, hipEventRecord(b0->ev[EV_DP_JUMP_FREE_END], ws));
+        }
+        k.launch(c, k, ws, b0, tier < DP_POOL_TIER ? noPool : pool);
+        STEP(check_launch(c, k.name));
+        for(int i = 0; i < n; i++) HIP_TRY(c, hipEventRecord(bs[i]->ev[EV_DP_CLASS_END + tier], ws));
+        if(tier == 0 || tier == 2) HIP_TRY(c, hipEventRecord(b0->ev[tier == 0 ? EV_DP_CLASS0_END : EV_DP_CLASS2_END], c->active));
+    }
+    return HLALA_OK;
+}
+// the side stream goes on from here: whatever the batch has queued on the main stream so far lies in front of its side-stream work
+static int side_fork(hlala_ctx* c, hlala_batch* b)
+{
+    HIP_TRY(c, hipEventRecord(b->ev[EV_SIDE_FORK], c->active)); HIP_TRY(c, hipStreamWaitEvent(c->side, b->ev[EV_SIDE_FORK], 0));
+    HIP_TRY(c, hipEventRecord(b->ev[EV_SIDE_BEGIN], c->side)); b->side_used = true;
+    return HLALA_OK;
+}
+// The end of a sequence of side-stream work of `b`, and the only place that says so: EV_DONE for whoever touches the batch next, evSideTail for a later launch on the
+// main stream of the classes whose slabs the side stream uses (hlala_ctx::dp).  Every sequence that queued anything on the side stream ends here.
+static int side_mark(hlala_ctx* c, hlala_batch* b)
+{
+    HIP_TRY(c, hipEventRecord(b->ev[EV_DONE], c->side)); b->side_inflight = true;
+    HIP_TRY(c, hipEventRecord(c->evSideTail, c->side)); c->sideTailValid = true;
+    return HLALA_OK;
+}
+// first stitch pass (work counter 7).  mode 0: every chain; 1: all but the chains of the deferred pairs, which stitch_side takes behind their DP classes
+static int stitch_main(hlala_ctx* c, hlala_batch* b, int mode)
+{
+    const int sgrid = b->B.n_chains < c->stitch_grid ? b->B.n_chains : c->stitch_grid;
+    hipLaunchKernelGGL(k_stitch_chains, dim3(sgrid), dim3(64), 0, c->active, c->G, c->dT, b->B, (const uint8_t*)b->B.pair_deferred, mode, c->stitch_draw, c->stitch_by_row);
+    return check_launch(c, "k_stitch_chains");
+}
+// second stitch pass, on the side stream: the chains of the deferred pairs (work counter 36)
+static int stitch_side(hlala_ctx* c, hlala_batch* b)
+{
+    const int pgrid = (b->B.n_pairs + 63) / 64, cap = c->stitch_grid / 20;       // it sweeps the pairs' flags, 64 per wave and round: one wave per CU finds room beside the next batch's persistent kernels
+    hipLaunchKernelGGL(k_stitch_chains, dim3(pgrid < cap ? (pgrid > 0 ? pgrid : 1) : cap), dim3(64), 0, c->side, c->G, c->dT, b->B, (const uint8_t*)b->B.pair_deferred, 2, 0, 0);
+    return check_launch(c, "k_stitch_chains (side)");
+}
+static int extend_end(hlala_ctx* c, hlala_batch* b) { HIP_TRY(c, hipEventRecord(b->ev[EV_EXTEND_END], c->active)); b->staged |= 2; return mark_main(c, b); }
+static int pair_begin(hlala_ctx* c, hlala_batch* b) { HIP_TRY(c, hipMemsetAsync(b->B.work_counter + 2, 0, sizeof(int), c->active)); HIP_TRY(c, hipEventRecord(b->ev[EV_PAIR_BEGIN], c->active)); return HLALA_OK; }
+// One pairing pass on `st`.  mode 0: every pair (a stage call); 1: all but the deferred pairs; 2: those (the side stream's pass, behind stitch_side).  k_pair_chains
+// finishes the pairs with one combination and lists the others, k_pair_multi<., false / true> runs the two lists (kernel_pair.hip); the main- and the side-stream pass
+// have their own work counter (2 / 37), lists, list counters and combination scratch.
+static int pair_pass(hlala_ctx* c, hlala_batch* b, hipStream_t st, int mode)
+{
+    DevBatch& B = b->B;
+    const int grid = B.n_pairs < c->pair_grid ? B.n_pairs : c->pair_grid, lean = B.n_pairs < c->pair_lean_grid ? B.n_pairs : c->pair_lean_grid;
+    const int pass = st == c->side ? 1 : 0, counterIdx = pass ? 37 : 2, multiBase = WC_PAIR_MULTI + 4 * pass;
+    int* multiList = B.pair_multi + (size_t)pass * 2 * (size_t)B.n_pairs; double* scratch = c->pair_scratch + (pass ? (size_t)c->pair_grid * PAIR_COMB : 0);
+    // (the lists' counters are among those the extension stage clears; a pairing stage called again on its own clears them here.  Not on the side stream: a fill
+    //  kernel queued there waits 13-36 ms for a wave slot beside the persistent kernels -- profiles/r06_experiments.txt)
+    if(mode == 0) HIP_TRY(c, hipMemsetAsync(B.work_counter + multiBase, 0, 4 * sizeof(int), st));
+    const int g0 = mode == 2 ? (grid < c->pair_grid / 5 ? grid : c->pair_grid / 5) : grid, g1 = grid < c->pair_grid / 5 ? grid : c->pair_grid / 5;      // (the second pass and the general class hold a few thousand pairs at most)
+    const auto chains = B.unpaired ? k_pair_chains<true> : k_pair_chains<false>;
+    const auto multi = B.unpaired ? k_pair_multi<true, false> : k_pair_multi<false, false>, multiBig = B.unpaired ? k_pair_multi<true, true> : k_pair_multi<false, true>;
+    hipLaunchKernelGGL(chains, dim3(lean), dim3(64), 0, st, c->dG, c->dT, b->dB, (const uint8_t*)B.pair_deferred, mode, counterIdx, multiList, multiBase);
+    hipLaunchKernelGGL(multi, dim3(g0), dim3(64), 0, st, c->G, b->B, c->dG, c->dT, b->dB, (const int*)multiList, multiBase, scratch);
+    hipLaunchKernelGGL(multiBig, dim3(g1), dim3(64), 0, st, c->G, b->B, c->dG, c->dT, b->dB, (const int*)multiList, multiBase, scratch);
+    return check_launch(c, "k_pair_chains / k_pair_multi");
+}
+// second pairing pass, behind the side-stream classes and the second stitch pass: the deferred pairs
+static int pair_side(hlala_ctx* c, hlala_batch* b)
+{
+    STEP(pair_pass(c, b, c->side, 2));
+    HIP_TRY(c, hipEventRecord(b->ev[EV_SIDE_END], c->side)); b->side_pending = false;
+    return HLALA_OK;
+}
+static int pair_end(hlala_ctx* c, hlala_batch* b) { HIP_TRY(c, hipEventRecord(b->ev[EV_PAIR_END], c->active)); b->staged |= 4; return mark_main(c, b); }
 
-static int pair_impl(hlala_ctx* c, hlala_batch* b, int phase);
-int hlala_pair_chains(hlala_ctx* c, hlala_batch* b) { return pair_impl(c, b, 0); }
-// phase: 0 = the whole stage; 1 = the main-stream pass alone, 2 = the side-stream pass alone (hlala_align_batch: extend_impl)
-static int pair_impl(hlala_ctx* c, hlala_batch* b, int phase)
+// In the schedules below one line = consecutive steps on ONE stream (named at its end), so the lines also give the order in which the host alternates between the streams.
+// Schedule 1, the stage calls: everything on the main stream (unpaired, from-seeds and empty batches take them from hlala_align_batch as well).  The slabs of the
+// classes from DP_SIDE_TIER on may still be in use on the side stream (hlala_ctx::dp): pending pooled launches are queued first, and the main stream waits for the end
+// of the side stream's queue in front of the first of these classes.
+int hlala_extend_chains(hlala_ctx* c, hlala_batch* b)
+{
+    DEV_GUARD(c);
+    if(!c || !b) return HLALA_E_ARG;
+    if(!(b->staged & 1)) { c->err = "hlala_extend_chains before seed chains exist"; return HLALA_E_STATE; }
+    STEP(flush_tail(c));                                                                                                        // side
+    STEP(join_side(c, b)); STEP(batch_events(c, b)); STEP(dp_prepare(c, b));                                                    // main, as all below
+    if(b->B.n_chains > 0) {
+        STEP(dp_band(c, b)); STEP(dp_classes(c, &b, 1, 0, DP_SIDE_TIER - 1, c->active));
+        if(c->sideTailValid) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->evSideTail, 0));
+        STEP(dp_classes(c, &b, 1, DP_SIDE_TIER, DP_LAST_TIER, c->active)); HIP_TRY(c, hipEventRecord(b->ev[EV_DP_END], c->active));
+        STEP(stitch_main(c, b, 0));
+    }
+    return extend_end(c, b);
+}
+int hlala_pair_chains(hlala_ctx* c, hlala_batch* b)
 {
     DEV_GUARD(c);
     if(!c || !b) return HLALA_E_ARG;
     if(b->B.from_seeds) { c->err = "batch was created from seeds: stage C not available"; return HLALA_E_STATE; }
     if(!(b->staged & 2)) { c->err = "hlala_pair_chains before hlala_extend_chains"; return HLALA_E_STATE; }
-    { int re = batch_events(c, b); if(re) return re; }
-    DevBatch& B = b->B;
-    const bool fused = b->side_pending;
-    if(!fused) { if(phase == 2) return HLALA_OK; phase = 0; }
-    if(!fused) { int rj = join_side(c, b); if(rj) return rj; }
-    if(phase != 2) {
-    HIP_TRY(c, hipMemsetAsync(B.work_counter + 2, 0, sizeof(int), c->active));
-    HIP_TRY(c, hipEventRecord(b->ev[4], c->active));
-    }
-    if(B.n_pairs > 0) {
-        const int grid = B.n_pairs < c->pair_grid ? B.n_pairs : c->pair_grid;
-        // k_pair_chains finishes the pairs with one combination and lists the others, k_pair_multi<., false / true> runs the two lists (kernel_pair.hip); the main-
-        // and the side-stream pass have their own lists, counters and combination scratch
-        auto launch_pair = [&](hipStream_t st, int mode, int counterIdx) -> int {
-            const int pass = st == c->side ? 1 : 0, multiBase = WC_PAIR_MULTI + 4 * pass;
-            int* multiList = B.pair_multi + (size_t)pass * 2 * (size_t)B.n_pairs;
-            double* scratch = c->pair_scratch + (pass ? (size_t)c->pair_grid * PAIR_COMB : 0);
-            // (the lists' counters are among those the extension stage clears; a pairing stage called again on its own clears them here.  Not on the side stream: a fill
-            //  kernel queued there waits 13-36 ms for a wave slot beside the persistent kernels -- profiles/r06_experiments.txt)
-            if(!fused) HIP_TRY(c, hipMemsetAsync(B.work_counter + multiBase, 0, 4 * sizeof(int), st));
-            const int lean = B.n_pairs < c->pair_lean_grid ? B.n_pairs : c->pair_lean_grid;
-            const int g0 = mode == 2 ? (grid < c->pair_grid / 5 ? grid : c->pair_grid / 5) : grid, g1 = grid < c->pair_grid / 5 ? grid : c->pair_grid / 5;      // (the second pass and the general class hold a few thousand pairs at most)
-            if(B.unpaired) {
-                hipLaunchKernelGGL((k_pair_chains<true>), dim3(lean), dim3(64), 0, st, c->dG, c->dT, b->dB, (const uint8_t*)B.pair_deferred, mode, counterIdx, multiList, multiBase);
-                hipLaunchKernelGGL((k_pair_multi<true, false>), dim3(g0), dim3(64), 0, st, c->G, b->B, c->dG, c->dT, b->dB, (const int*)multiList, multiBase, scratch);
-                hipLaunchKernelGGL((k_pair_multi<true, true>), dim3(g1), dim3(64), 0, st, c->G, b->B, c->dG, c->dT, b->dB, (const int*)multiList, multiBase, scratch);
-            } else {
-                hipLaunchKernelGGL((k_pair_chains<false>), dim3(lean), dim3(64), 0, st, c->dG, c->dT, b->dB, (const uint8_t*)B.pair_deferred, mode, counterIdx, multiList, multiBase);
-                hipLaunchKernelGGL((k_pair_multi<false, false>), dim3(g0), dim3(64), 0, st, c->G, b->B, c->dG, c->dT, b->dB, (const int*)multiList, multiBase, scratch);
-                hipLaunchKernelGGL((k_pair_multi<false, true>), dim3(g1), dim3(64), 0, st, c->G, b->B, c->dG, c->dT, b->dB, (const int*)multiList, multiBase, scratch);
-            }
-            return check_launch(c, "k_pair_chains / k_pair_multi");
-        };
-        int rc = 0;
-        if(phase != 2) { rc = launch_pair(c->active, fused ? 1 : 0, 2); if(rc) return rc; }
-        if(fused && phase != 1) {
-            // second pass, behind the side-stream classes and the second stitch pass: the deferred pairs (work counter 37)
-            rc = launch_pair(c->side, 2, 37); if(rc) return rc;
-            HIP_TRY(c, hipEventRecord(b->evSide[6], c->side));
-            HIP_TRY(c, hipEventRecord(b->evDone, c->side));
-            HIP_TRY(c, hipEventRecord(c->evSideTail, c->side)); c->sideTailValid = true;
-            b->side_inflight = true; b->side_pending = false;
-        }
-    }
-    if(phase == 2) return HLALA_OK;
-    HIP_TRY(c, hipEventRecord(b->ev[5], c->active));
-    b->staged |= 4;
-    return mark_main(c, b);
+    STEP(batch_events(c, b)); STEP(join_side(c, b));
+    b->side_pending = false;       // (still set only after a fused alignment that failed between its stages: its chains are stitched, this pass takes every pair)
+    STEP(pair_begin(c, b));
+    if(b->B.n_pairs > 0) STEP(pair_pass(c, b, c->active, 0));
+    return pair_end(c, b);
 }
-
-// The tail pool (round 6).  The broad, large and in-memory DP classes hold 0.07 % of a batch's DP calls and took 100 ms of side stream per batch: their cost is the
-// latency of their slowest calls, paid per launch, while their blocks hold most of every CU's LDS beside the next batch's kernels.  With hlala_set_tail_pool(ctx, k)
-// a fused alignment runs its main-stream part and its wide class as before and leaves those three classes PENDING; the k-th pending batch (or hlala_flush, or any
-// call that reads or re-runs a pending batch) launches each of them once over all pending batches (k_dp: DpPoolArgs), then the second stitch / pairing pass of every
-// batch.  Results do not depend on k (tests/test_graph_m.py).
+// Schedule 2, the default fused alignment: the side stream's classes are forked off as soon as the 64-lane class is queued, and its whole extension part is queued
+// before the main stream's stitch pass.
+static int align_default(hlala_ctx* c, hlala_batch* b)
+{
+    STEP(dp_prepare(c, b)); STEP(dp_band(c, b)); STEP(dp_classes(c, &b, 1, 0, DP_SIDE_TIER - 1, c->active)); STEP(side_fork(c, b));        // main
+    STEP(dp_classes(c, &b, 1, DP_SIDE_TIER, DP_LAST_TIER, c->side)); STEP(stitch_side(c, b)); STEP(side_mark(c, b));                       // side
+    b->side_pending = true;
+    STEP(stitch_main(c, b, 1)); STEP(extend_end(c, b)); STEP(pair_begin(c, b)); STEP(pair_pass(c, b, c->active, 1));                       // main
+    STEP(pair_side(c, b)); STEP(side_mark(c, b));                                                                                          // side
+    return pair_end(c, b);                                                                                                                 // main
+}
+// Schedule 3, HLALA_SIDE_AFTER_PAIR=1: the main stream's part of the batch first -- DP classes up to the 64-lane one, stitch, pairing --, then the side stream's classes
+// and its second stitch / pairing pass.  k_pair_chains is a short, latency-bound kernel that needs 6 KB of LDS per wavefront, and beside the wide class (seven blocks of
+// 22 KB per CU: 154 of a CU's 160 KB) hardly a block of it fits: 20.9 ms for a pairing pass that takes 4.1 ms alone (profiles/r05_experiments.txt, 19).  Not the
+// default: the next batch's projection (11.7 KB per block) then meets the wide class instead.
+static int align_side_after_pair(hlala_ctx* c, hlala_batch* b)
+{
+    STEP(dp_prepare(c, b)); STEP(dp_band(c, b)); STEP(dp_classes(c, &b, 1, 0, DP_SIDE_TIER - 1, c->active));                               // main, down to side_fork
+    b->side_pending = true;
+    STEP(stitch_main(c, b, 1)); STEP(extend_end(c, b)); STEP(pair_begin(c, b)); STEP(pair_pass(c, b, c->active, 1)); STEP(pair_end(c, b));
+    STEP(side_fork(c, b));
+    STEP(dp_classes(c, &b, 1, DP_SIDE_TIER, DP_LAST_TIER, c->side)); STEP(stitch_side(c, b)); STEP(side_mark(c, b));                       // side
+    STEP(pair_side(c, b)); return side_mark(c, b);
+}
+// The tail pool.  The broad, large and in-memory DP classes hold 0.07 % of a batch's DP calls and took 100 ms of side stream per batch: their cost is the latency of
+// their slowest calls, paid per launch, while their blocks hold most of every CU's LDS beside the next batch's kernels.  With hlala_set_tail_pool(ctx, k) a fused
+// alignment runs its main-stream part and its wide class as before and leaves those three classes PENDING; the k-th pending batch (or hlala_flush, or any call that
+// reads or re-runs a pending batch, or a non-fused extension stage on the context) launches each of them once over all pending batches (k_dp: DpPoolArgs), then the
+// second stitch / pairing pass of every batch.  Results do not depend on k (tests/test_graph_m.py).
+// Schedule 4, the pooled alignment: as the default one up to the classes before DP_POOL_TIER; the batch then waits in c->tail with its second passes pending.
+static int align_pooled(hlala_ctx* c, hlala_batch* b)
+{
+    STEP(dp_prepare(c, b)); STEP(dp_band(c, b)); STEP(dp_classes(c, &b, 1, 0, DP_SIDE_TIER - 1, c->active)); STEP(side_fork(c, b));        // main
+    STEP(dp_classes(c, &b, 1, DP_SIDE_TIER, DP_POOL_TIER - 1, c->side)); STEP(side_mark(c, b));                                            // side
+    b->side_pending = true;
+    STEP(stitch_main(c, b, 1)); STEP(extend_end(c, b)); STEP(pair_begin(c, b)); STEP(pair_pass(c, b, c->active, 1)); STEP(pair_end(c, b)); // main
+    c->tail.push_back(b); b->tail_pooled = true;
+    return (int)c->tail.size() >= c->tail_pool_k ? flush_tail(c) : HLALA_OK;
+}
+// Schedule 5: the pooled classes once for all pending batches, then every batch's second passes.  All on the side stream, behind the batches' wide classes.
 static int flush_tail(hlala_ctx* c)
 {
     if(c->tail.empty()) return HLALA_OK;
     DEV_GUARD(c);
     std::vector<hlala_batch*> pool; pool.swap(c->tail);
     for(hlala_batch* b : pool) b->tail_pooled = false;           // (whatever happens below, nobody waits for this flush again)
-    DpPoolArgs a{}; a.n = (int)pool.size();
-    for(int i = 0; i < a.n; i++) { hlala_batch* b = pool[i]; a.seed[i] = c->params.rng_seed + 2u * b->first_chain; a.B[i] = b->dB; a.items[i] = (const DpItem*)b->B.dp_items; a.bases[i] = (const uint8_t*)b->B.read_bases; }
-    const hipStream_t ws = c->side;
-    for(int tier = DP_POOL_TIER; tier <= DP_LAST_TIER; tier++) {
-        for(hlala_batch* b : pool) HIP_TRY(c, hipEventRecord(b->evC[tier][0], ws));
-        hlala_batch* b0 = pool[0];
-        switch(tier) {
-        case 4: hipLaunchKernelGGL((k_dp<DpBroad, 4>), dim3(c->broad_grid), dim3(DpBroad::THREADS), 0, ws, c->dG, b0->dB, (DpItem*)b0->B.dp_items, c->large_slabs, c->large_slab_bytes, a.seed[0], c->G.nrec_out, c->G.nrec_in, b0->B.read_bases, a); break;
-        case 5: hipLaunchKernelGGL((k_dp<DpLarge, 5>), dim3(c->retry_grid), dim3(DpLarge::THREADS), 0, ws, c->dG, b0->dB, (DpItem*)b0->B.dp_items, c->large_slabs + c->large_slab_bytes * (size_t)c->broad_grid, c->large_slab_bytes, a.seed[0], c->G.nrec_out, c->G.nrec_in, b0->B.read_bases, a); break;
-        default: hipLaunchKernelGGL((k_dp<DpHuge, 6>), dim3(c->huge_grid), dim3(DpHuge::THREADS), 0, ws, c->dG, b0->dB, (DpItem*)b0->B.dp_items, c->huge_slabs, c->huge_slab_bytes, a.seed[0], c->G.nrec_out, c->G.nrec_in, b0->B.read_bases, a); break;
-        }
-        int rc_ = check_launch(c, "k_dp (pooled)"); if(rc_) return rc_;
-        for(hlala_batch* b : pool) HIP_TRY(c, hipEventRecord(b->evC[tier][1], ws));
-    }
-    for(hlala_batch* b : pool) {
-        int rc = extend_impl(c, b, true, 4); if(rc) return rc;      // second stitch pass over the deferred pairs
-        rc = pair_impl(c, b, 2); if(rc) return rc;                   // second pairing pass; records evDone
-    }
+    STEP(dp_classes(c, pool.data(), (int)pool.size(), DP_POOL_TIER, DP_LAST_TIER, c->side));
+    for(hlala_batch* b : pool) { STEP(stitch_side(c, b)); STEP(side_mark(c, b)); STEP(pair_side(c, b)); STEP(side_mark(c, b)); }
     return HLALA_OK;
 }
 
@@ -1177,33 +1191,15 @@ int hlala_set_tail_pool(hlala_ctx* c, int k)
     c->tail_pool_k = k;
     return HLALA_OK;
 }
-int hlala_flush(hlala_ctx* c)
-{
-    if(!c) return HLALA_E_ARG;
-    return flush_tail(c);
-}
+int hlala_flush(hlala_ctx* c) { return c ? flush_tail(c) : HLALA_E_ARG; }
 
 int hlala_align_batch(hlala_ctx* c, hlala_batch* b)
 {
     int rc = hlala_project_chains(c, b); if(rc) return rc;
-    if(c->tail_pool_k > 1 && DP_POOL_TIER > DP_SIDE_TIER) {
-        rc = extend_impl(c, b, true, 3); if(rc) return rc;
-        if(!b->side_pending) return hlala_pair_chains(c, b);          // not a fused alignment (unpaired, from seeds, empty): nothing to pool
-        rc = pair_impl(c, b, 1); if(rc) return rc;
-        c->tail.push_back(b); b->tail_pooled = true;
-        if((int)c->tail.size() >= c->tail_pool_k) return flush_tail(c);
-        return HLALA_OK;
-    }
-    if(!c->side_after_pair) {
-        rc = extend_impl(c, b, true); if(rc) return rc;
-        return hlala_pair_chains(c, b);
-    }
-    // the main stream's part of the batch first -- DP classes up to the 64-lane one, stitch, pairing --, then the side stream's classes and its second stitch / pairing pass
-    // are queued behind it (extend_impl): the main stream's short kernels do not share the CUs with the wide class
-    rc = extend_impl(c, b, true, 1); if(rc) return rc;
-    rc = pair_impl(c, b, 1); if(rc) return rc;
-    rc = extend_impl(c, b, true, 2); if(rc) return rc;
-    return pair_impl(c, b, 2);
+    if(!fusable(b)) { rc = hlala_extend_chains(c, b); return rc ? rc : hlala_pair_chains(c, b); }
+    DEV_GUARD(c);
+    if(c->tail_pool_k > 1 && DP_POOL_TIER > DP_SIDE_TIER) return align_pooled(c, b);
+    return c->side_after_pair ? align_side_after_pair(c, b) : align_default(c, b);
 }
 
 int hlala_batch_get_chains(hlala_ctx* c, hlala_batch* b, int stage, hlala_chains_out* o)
@@ -1677,16 +1673,16 @@ int hlala_batch_get_stats(hlala_ctx* c, hlala_batch* b, hlala_batch_stats* out)
     HIP_TRY(c, hipStreamSynchronize(c->active));
     u64 cnt[16];
     HIP_TRY(c, hipMemcpyAsync(cnt, b->B.counters, sizeof(cnt), hipMemcpyDeviceToHost, c->active)); HIP_TRY(c, hipStreamSynchronize(c->active));
-    if((b->staged & 1) && !b->B.from_seeds) (void)hipEventElapsedTime(&out->ms_project, b->ev[0], b->ev[1]);
-    if(b->staged & 2) { (void)hipEventElapsedTime(&out->ms_extend, b->ev[2], b->ev[3]); if(b->B.n_chains > 0) { (void)hipEventElapsedTime(&out->ms_extend_retry, b->ev[6], b->side_used ? b->ev[10] : b->ev[8]); (void)hipEventElapsedTime(&out->ms_dp_main, b->ev[7], b->ev[6]);
-          for(int k = 0; k <= DP_LAST_TIER; k++) (void)hipEventElapsedTime(&out->ms_dp_class[k], b->evC[k][0], b->evC[k][1]);
-          (void)hipEventElapsedTime(&out->ms_dp_jump_free, b->evC[0][0], b->evJF);
-          if(b->band_used) (void)hipEventElapsedTime(&out->ms_dp_band, b->evBand[0], b->evBand[1]);
-          if(b->side_used) (void)hipEventElapsedTime(&out->ms_side, b->evSide[1], b->evSide[6]); } }
+    if((b->staged & 1) && !b->B.from_seeds) (void)hipEventElapsedTime(&out->ms_project, b->ev[EV_PROJECT_BEGIN], b->ev[EV_PROJECT_END]);
+    if(b->staged & 2) { (void)hipEventElapsedTime(&out->ms_extend, b->ev[EV_EXTEND_BEGIN], b->ev[EV_EXTEND_END]); if(b->B.n_chains > 0) { (void)hipEventElapsedTime(&out->ms_extend_retry, b->ev[EV_DP_CLASS0_END], b->ev[b->side_used ? EV_DP_CLASS2_END : EV_DP_END]); (void)hipEventElapsedTime(&out->ms_dp_main, b->ev[EV_DP_BEGIN], b->ev[EV_DP_CLASS0_END]);
+          for(int k = 0; k <= DP_LAST_TIER; k++) (void)hipEventElapsedTime(&out->ms_dp_class[k], b->ev[EV_DP_CLASS_BEGIN + k], b->ev[EV_DP_CLASS_END + k]);
+          (void)hipEventElapsedTime(&out->ms_dp_jump_free, b->ev[EV_DP_CLASS_BEGIN], b->ev[EV_DP_JUMP_FREE_END]);
+          if(b->band_used) (void)hipEventElapsedTime(&out->ms_dp_band, b->ev[EV_DP_BAND_BEGIN], b->ev[EV_DP_BAND_END]);
+          if(b->side_used) (void)hipEventElapsedTime(&out->ms_side, b->ev[EV_SIDE_BEGIN], b->ev[EV_SIDE_END]); } }
     { int wc[WC_N]; HIP_TRY(c, hipMemcpyAsync(wc, b->B.work_counter, sizeof(wc), hipMemcpyDeviceToHost, c->active)); HIP_TRY(c, hipStreamSynchronize(c->active)); out->n_chains_retried = 0; for(int k = 1; k <= 6; k++) out->n_chains_retried += wc[12 + 4 * (k - 1)] + wc[14 + 4 * (k - 1)]; out->n_dp_retried_large = wc[28] + wc[30];
       out->n_dp_band = b->band_used ? wc[WC_BAND_CALLS] : 0; out->n_dp_band_failed = b->band_used ? wc[WC_BAND_FAILED] : 0; out->n_dp_jump_free_failed = wc[WC_JF_FAILED];
       out->n_dp_class[0] = wc[8] + wc[9] - out->n_dp_band + out->n_dp_band_failed; out->n_dp_jump_free = wc[6]; for(int k = 1; k <= 6; k++) out->n_dp_class[k] = wc[12 + 4 * (k - 1)] + wc[14 + 4 * (k - 1)]; }
-    if(b->staged & 4) (void)hipEventElapsedTime(&out->ms_pair, b->ev[4], b->ev[5]);
+    if(b->staged & 4) (void)hipEventElapsedTime(&out->ms_pair, b->ev[EV_PAIR_BEGIN], b->ev[EV_PAIR_END]);
     out->n_chains_extended = (int64_t)cnt[CNT_CHAINS_EXT]; out->n_dp_calls = (int64_t)cnt[CNT_DP_CALLS];
     out->n_dp_iterations = (int64_t)cnt[CNT_DP_ITERS]; out->n_dp_cells = (int64_t)cnt[CNT_DP_CELLS];
     out->n_seed_columns = (int64_t)cnt[CNT_SEED_COLS]; out->n_out_columns = (int64_t)cnt[CNT_OUT_COLS];

@@ -145,6 +145,45 @@ def test_tail_pool_of_two_over_three_alignments_and_flush(pkg, dense):
     ctx.close()
 
 
+def test_stage_calls_on_one_batch_while_two_alignments_wait_in_the_tail_pool(pkg, dense):
+    """(d') hlala_set_tail_pool(3) with two alignments pending, the third batch taken through the three stage calls: its extension runs every DP class on
+    the main stream, on the slabs that the pending alignments' wide classes used on the side stream and their pooled classes have yet to use.  The stage
+    call queues the pooled launches first and waits for the side stream.  Each batch is the stage-call batch once; all three match the oracle every time."""
+    ctx = pkg.Context(dense["w"]["graph"], dense["w"]["contigs"], **dense["kw"])
+    ctx.set_tail_pool(3)
+    staged_tail = 0
+    for k in range(3):
+        gbs = [ctx.batch(b) for b in dense["bs"]]
+        for i in range(3):
+            if i != k:
+                gbs[i].align()
+        gbs[k].project(); gbs[k].extend(); gbs[k].pair()
+        for i in range(3):
+            st = check_aligned(gbs[i], dense["bs"][i], dense["exp"][i], "stage calls on batch %d, batch %d" % (k, i))
+            if i == k:
+                staged_tail += sum(int(x) for x in list(st.n_dp_class)[4:])
+        for g in gbs:
+            g.close()
+    assert staged_tail > 0                                                # a stage-call batch had calls in the classes the pool defers
+    ctx.close()
+
+
+def test_pairing_stage_call_on_a_batch_that_waits_in_the_tail_pool(pkg, dense):
+    """(d'') hlala_pair_chains on a batch whose alignment is still pending in the tail pool: the call flushes the pool first, so the pooled classes and the
+    batch's second stitch pass lie in front of the pairing pass, which then takes every pair on the main stream.  Results are the oracle's."""
+    ctx = pkg.Context(dense["w"]["graph"], dense["w"]["contigs"], **dense["kw"])
+    ctx.set_tail_pool(3)
+    gbs = [ctx.batch(b) for b in dense["bs"][:2]]
+    for g in gbs:
+        g.align()                                                         # two of three: both stay pending
+    gbs[0].pair()
+    for i in (0, 1):
+        check_aligned(gbs[i], dense["bs"][i], dense["exp"][i], "pair() on a pooled batch, batch %d" % i)
+    for g in gbs:
+        g.close()
+    ctx.close()
+
+
 def test_every_dp_class_up_to_the_in_memory_one(pkg, oracle):
     """(e) A pair whose DP calls outgrow every LDS class (tests/test_full_scale.py: pair 13 255 of the 5 M-level Graph M world's gene-window batch -- the first
     13 256 pairs of that batch are the same whatever its size): the in-memory class keeps its table structure in the HBM slab, where a pointer into it is a
