@@ -304,6 +304,20 @@ class SeedBatch:
         self.lib.hlala_seed_batch_timing(self.h, s.ctypes.data_as(c_f64p), t.ctypes.data_as(c_i32p))
         return dict(zip(("index", "inflate", "parse", "group", "name_sort", "layout"), [float(x) for x in s]), threads=int(t[0]))
 
+    def parse_counts(self):
+        """(records scanned on the GPU, rounds scanned there, rounds that fell back to the host's hop and parse)"""
+        cnt = (C.c_int64 * 3)()
+        self.lib.hlala_seed_batch_parse_counts.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        self.lib.hlala_seed_batch_parse_counts(self.h, cnt)
+        return tuple(int(x) for x in cnt)
+
+    def transfer_bytes(self):
+        """(bytes the decoder's GPU paths moved to the device, bytes they moved back)"""
+        b = (C.c_int64 * 2)()
+        self.lib.hlala_seed_batch_transfer_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        self.lib.hlala_seed_batch_transfer_bytes(self.h, b)
+        return tuple(int(x) for x in b)
+
     def inflate_counts(self):
         """(blocks inflated on the GPU, blocks the GPU rejected and the host engine ran again, blocks inflated on the host only)"""
         cnt = (C.c_int64 * 3)()
@@ -327,6 +341,7 @@ class SeedBatch:
 
 
 SEEDS_PACKED = 1          # HLALA_SEEDS_PACKED
+SEEDS_GPU_PARSE = 2       # HLALA_SEEDS_GPU_PARSE (Inflater.bam_open_seeds only): the record pass of every round on the GPU as well
 
 
 def bam_open_seeds(lib, path, intervals, long_read_mode=False, threads=0, flags=0) -> SeedBatch:
@@ -348,6 +363,36 @@ class BgzfBlock(C.Structure):
 
 class InflateStats(C.Structure):
     _fields_ = [("n_blocks", C.c_int64), ("n_ok", C.c_int64), ("n_rejected", C.c_int64), ("ms_h2d", C.c_double), ("ms_kernel", C.c_double), ("ms_d2h", C.c_double), ("ms_wall", C.c_double)]
+
+
+class BamScanIn(C.Structure):
+    _fields_ = [("n_ref", C.c_int32), ("n_intervals", C.c_int32), ("ref_iv_off", C.c_void_p), ("ref_iv", C.c_void_p), ("iv_start", C.c_void_p), ("iv_stop", C.c_void_p), ("iv_contig", C.c_void_p),
+                ("long_read_mode", C.c_int32), ("max_rehops", C.c_int32), ("hash_mask", C.c_uint64), ("first_seq", C.c_uint64), ("slice_bytes", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class BamScanStats(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("n_records", "n_kept", "n_recs", "examined", "consumed", "compact_bytes")] + [("status", C.c_int32), ("pad", C.c_int32), ("status_record", C.c_int64),
+               ("n_slices", C.c_int64), ("n_rehops", C.c_int64)] + [(k, C.c_double) for k in ("ms_h2d", "ms_guess", "ms_link", "ms_starts", "ms_parse", "ms_scan", "ms_emit", "ms_d2h", "ms_wall")]
+
+
+# hlala_bam_rec
+BAM_REC_DTYPE = np.dtype([("hash", "<u8"), ("order", "<u8"), ("rec_off", "<u8"), ("contig", "<i4"), ("pos", "<i4"), ("as", "<i4"), ("l_seq", "<i4"), ("n_cigar", "<u2"), ("nameLen", "<u2"),
+                          ("which", "u1"), ("flags", "u1"), ("l_read_name", "u1"), ("pad1", "u1")])
+BAMSCAN_STATUS = ("ok", "bad length", "corrupt record", "corrupt tag", "unknown tag type", "no AS", "unpaired", "too many re-hops")      # HLALA_BAMSCAN_*
+BAMSCAN_DEFAULT_SLICE, BAMSCAN_DEFAULT_MAX_REHOPS = 16384, 1024
+
+
+def bam_scan_in(n_ref, ref_intervals, intervals, long_read_mode=False, hash_mask=(1 << 64) - 1, first_seq=0, slice_bytes=0, max_rehops=None):
+    """hlala_bam_scan_in: ref_intervals[r] = the interval numbers of reference id r (in the order the decoder visits them), intervals = [(start_0based, stop_0based, contig)].
+    max_rehops: None = the default cap, 0 = none allowed.  Returns (struct, the arrays it points into: keep them alive)."""
+    off = np.zeros(max(1, n_ref + 1), np.int32)
+    for r in range(n_ref):
+        off[r + 1] = off[r] + len(ref_intervals[r])
+    flat = np.array([i for r in range(n_ref) for i in ref_intervals[r]] + [0], np.int32)
+    cols = [np.array([iv[k] for iv in intervals] + [0], np.int32) for k in range(3)]
+    a = BamScanIn(int(n_ref), len(intervals), off.ctypes.data, flat.ctypes.data, cols[0].ctypes.data, cols[1].ctypes.data, cols[2].ctypes.data, int(bool(long_read_mode)),
+                  0 if max_rehops is None else (-1 if max_rehops == 0 else int(max_rehops)), int(hash_mask), int(first_seq), int(slice_bytes), 0)
+    return a, (off, flat, cols)
 
 
 INFLATE_MIN_CHUNK, INFLATE_DEFAULT_CHUNK = 1 << 17, 32 << 20          # HLALA_INFLATE_MIN_CHUNK, HLALA_INFLATE_DEFAULT_CHUNK
@@ -383,6 +428,24 @@ class Inflater:
         if rc != 0:
             raise HlalaError(f"hlala_bgzf_inflate failed ({rc}): {self.lib.hlala_inflater_last_error(self.h).decode(errors='replace')}")
         return status[:len(blocks)], st
+
+    def bam_scan(self, data, scan_in, first=0, last=False, cap_recs=None, cap_compact=None, guard=0, canary=0):
+        """hlala_bam_scan on inflated BAM bytes (a contiguous uint8 array); scan_in: the struct of bam_scan_in().  Returns (return code, descriptors as a structured array of
+        BAM_REC_DTYPE, compact bytes, BamScanStats); HLALA_E_CAPACITY (-4) is returned, not raised: the stats say what is needed.  cap_*: sizes of the arrays handed in (default:
+        always enough).  guard: that many canary bytes before and behind both arrays, which the caller gets back as well (tests)."""
+        data = np.ascontiguousarray(data, np.uint8); n = data.size
+        cr = n // 36 * max(1, scan_in.n_intervals) if cap_recs is None else int(cap_recs)
+        cc = n if cap_compact is None else int(cap_compact)
+        recs = np.full(2 * guard + cr * BAM_REC_DTYPE.itemsize, canary, np.uint8); comp = np.full(2 * guard + cc, canary, np.uint8)
+        st = BamScanStats()
+        self.lib.hlala_bam_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int32, C.POINTER(BamScanIn), C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.POINTER(BamScanStats)]
+        rc = self.lib.hlala_bam_scan(self.h, data.ctypes.data, n, int(first), int(bool(last)), C.byref(scan_in), recs.ctypes.data + guard, cr, comp.ctypes.data + guard, cc, C.byref(st))
+        if rc not in (0, -4):
+            raise HlalaError(f"hlala_bam_scan failed ({rc}): {self.lib.hlala_inflater_last_error(self.h).decode(errors='replace')}")
+        if guard:
+            return rc, recs, comp, st
+        ok = rc == 0 and st.status == 0
+        return rc, recs[:(st.n_recs if ok else 0) * BAM_REC_DTYPE.itemsize].view(BAM_REC_DTYPE), comp[:st.compact_bytes if ok else 0], st
 
     def bam_open_seeds(self, path, intervals, long_read_mode=False, threads=0, flags=0) -> SeedBatch:
         """hlala_bam_extract_seeds_gpu: the sample of bam_open_seeds, its blocks inflated by this handle (SeedBatch.inflate_counts says how many)"""
@@ -753,7 +816,7 @@ def load_library(path: str | None = None):
     return lib
 
 
-ABI_VERSION = 6              # HLALA_ABI_VERSION of include/hlala_gpu.h
+ABI_VERSION = 7              # HLALA_ABI_VERSION of include/hlala_gpu.h
 DEBUG_WC_N, DEBUG_WC_BAND_FETCH, DEBUG_WC_BAND_WHY, DEBUG_WC_BAND_TIED = 88, 48, 62, 68      # include/hlala_gpu.h: debug section
 BUILD_AGENT_RELEASE = 2      # hlala_build_flags(): the in-memory DP class releases at agent scope (make EXTRA=-DHLALA_DP_AGENT_RELEASE)
 
@@ -775,6 +838,7 @@ EXPORTED_SYMBOLS = [
     "hlala_typer_open", "hlala_typer_close", "hlala_typer_last_error", "hlala_typer_n_levels", "hlala_typer_level_name", "hlala_typer_level_of", "hlala_typer_n_genes",
     "hlala_typer_gene", "hlala_typer_load_g_groups", "hlala_typer_g_translate", "hlala_typer_locus", "hlala_locus_free", "hlala_locus_get", "hlala_locus_cluster_id", "hlala_locus_type_cluster",
     "hlala_inflater_create", "hlala_inflater_destroy", "hlala_inflater_last_error", "hlala_bgzf_inflate", "hlala_bam_extract_seeds_gpu", "hlala_seed_batch_inflate_counts",
+    "hlala_bam_scan", "hlala_bam_scan_status_text", "hlala_seed_batch_parse_counts", "hlala_seed_batch_transfer_bytes",
     "hlala_locus_cluster_kmers", "hlala_type_locus", "hlala_kmer_presence", "hlala_kmer_keep_reads", "hlala_kmer_presence_kept", "hlala_kmer_forget_reads", "hlala_unit_alignment_stats", "hlala_typer_write_summary", "hlala_typer_begin_output", "hlala_locus_write_files", "hlala_locus_write_pairs_file", "hlala_typer_end_output",
 ]
 

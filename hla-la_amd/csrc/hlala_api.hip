@@ -29,6 +29,7 @@
 #include "kernel_kmer.hip"
 #include "kernel_dp_band.hip"
 #include "kernel_inflate.hip"
+#include "kernel_bamscan.hip"
 
 namespace hlala {
 size_t proj_slab_bytes_host(int stride, int maxNodesPerLevel) { return proj_slab_bytes(stride, maxNodesPerLevel); }
@@ -2284,9 +2285,15 @@ struct InflateSlot {
     hlala_bgzf_block* hDesc = nullptr; hlala_bgzf_block* dDesc = nullptr; int* hStatus = nullptr; int* dStatus = nullptr;
     int64_t first = 0, count = 0; size_t outBytes = 0; bool busy = false;
 };
+// device buffers of hlala_bam_scan: grown on demand, kept by the handle
+struct ScanBuf { void* p = nullptr; size_t cap = 0; };
+enum { SCAN_DATA, SCAN_CARRY, SCAN_SLICES, SCAN_TOTALS, SCAN_INTERVALS, SCAN_RECORDS, SCAN_OFFSETS, SCAN_RECS, SCAN_COMPACT, SCAN_NBUF };
+constexpr int SCAN_NEV = 11;
 struct hlala_inflater {
     int device = 0; size_t chunk = 0, outCap = 0; int64_t maxBlocks = 0;
     InflateSlot slot[3];
+    ScanBuf scan[SCAN_NBUF]; hipEvent_t scanEv[SCAN_NEV]{}; bool scanEvReady = false;
+    size_t roundBytes = 0;          // bytes of the decoder's last round in scan[SCAN_DATA] (hlala_host::bam_scan_round: their tail is the next round's carry)
     std::string err;
 };
 static thread_local std::string g_inflater_create_error;
@@ -2302,6 +2309,8 @@ extern "C" void hlala_inflater_destroy(hlala_inflater* f)
         if(s.hComp) (void)hipHostFree(s.hComp); if(s.hOut) (void)hipHostFree(s.hOut); if(s.hDesc) (void)hipHostFree(s.hDesc); if(s.hStatus) (void)hipHostFree(s.hStatus);
         if(s.dComp) (void)hipFree(s.dComp); if(s.dOut) (void)hipFree(s.dOut); if(s.dDesc) (void)hipFree(s.dDesc); if(s.dStatus) (void)hipFree(s.dStatus);
     }
+    for(ScanBuf& b : f->scan) if(b.p) (void)hipFree(b.p);
+    for(hipEvent_t e : f->scanEv) if(e) (void)hipEventDestroy(e);
     delete f;
 }
 extern "C" int hlala_inflater_create(int32_t device, size_t chunk_bytes, hlala_inflater** out)
@@ -2338,11 +2347,14 @@ extern "C" int hlala_inflater_create(int32_t device, size_t chunk_bytes, hlala_i
 // `landed` (may be null) is told about every chunk, in ascending block order, once its accepted blocks stand in `out` and its statuses in `status`; a non-zero
 // answer ends the call (HLALA_E_STATE) after the chunks in flight have been drained.
 static int inflate_run(hlala_inflater* f, const uint8_t* comp, size_t comp_bytes, const hlala_bgzf_block* blocks, int64_t n, uint8_t* out, size_t out_bytes, int32_t* status,
-                       hlala_inflate_stats* stats, int (*landed)(void*, int64_t, int64_t), void* user)
+                       hlala_inflate_stats* stats, int (*landed)(void*, int64_t, int64_t), void* user, uint8_t* dOutBase = nullptr)
 {
+    // dOutBase (device memory of out_bytes bytes; `out` is not used then): the blocks' output stays on the device -- block i goes to dOutBase + blocks[i].uoff, straight
+    // from the kernel; only the statuses come back.  The output ranges must follow one another without gaps (a chunk's kernel writes one contiguous range).
     if(!f) return HLALA_E_ARG;
     f->err.clear();
-    if(n < 0 || (n > 0 && (!blocks || !status)) || (comp_bytes && !comp) || (out_bytes && !out)) { f->err = "hlala_bgzf_inflate: null argument"; return HLALA_E_ARG; }
+    if(dOutBase) { uint64_t at = 0; for(int64_t i = 0; i < n && blocks; i++) { if(blocks[i].uoff != at) { f->err = "hlala_bgzf_inflate: output ranges with gaps cannot stay on the device"; return HLALA_E_ARG; } at += blocks[i].isize; } }
+    if(n < 0 || (n > 0 && (!blocks || !status)) || (comp_bytes && !comp) || (out_bytes && !out && !dOutBase)) { f->err = "hlala_bgzf_inflate: null argument"; return HLALA_E_ARG; }
     const auto tWall = std::chrono::steady_clock::now();
     // ---- the descriptors, before anything is launched
     for(int64_t i = 0; i < n; i++) {
@@ -2376,7 +2388,7 @@ static int inflate_run(hlala_inflater* f, const uint8_t* comp, size_t comp_bytes
             const hlala_bgzf_block& b = blocks[s.first + k];
             const int v = s.hStatus[k];
             status[s.first + k] = v;
-            if(v == HLALA_INFLATE_OK) { st.n_ok++; if(b.isize) memcpy(out + b.uoff, s.hOut + s.hDesc[k].uoff, b.isize); } else st.n_rejected++;
+            if(v == HLALA_INFLATE_OK) { st.n_ok++; if(b.isize && !dOutBase) memcpy(out + b.uoff, s.hOut + s.hDesc[k].uoff, b.isize); } else st.n_rejected++;
         }
         if(landed && landed(user, s.first, s.count) != 0) { f->err = "hlala_bgzf_inflate: ended by the caller"; rc = HLALA_E_STATE; }
     };
@@ -2400,9 +2412,9 @@ static int inflate_run(hlala_inflater* f, const uint8_t* comp, size_t comp_bytes
         if(e == hipSuccess && cb) e = hipMemcpyAsync(s.dComp, s.hComp, cb, hipMemcpyHostToDevice, s.stream);
         if(e == hipSuccess) e = hipMemcpyAsync(s.dDesc, s.hDesc, (size_t)cnt * sizeof(hlala_bgzf_block), hipMemcpyHostToDevice, s.stream);
         if(e == hipSuccess) e = hipEventRecord(s.ev[1], s.stream);
-        if(e == hipSuccess) { hipLaunchKernelGGL(k_bgzf_inflate, dim3((unsigned)cnt), dim3(64), 0, s.stream, (const uint8_t*)s.dComp, (const hlala_bgzf_block*)s.dDesc, (int)cnt, s.dOut, s.dStatus); e = hipGetLastError(); }
+        if(e == hipSuccess) { hipLaunchKernelGGL(k_bgzf_inflate, dim3((unsigned)cnt), dim3(64), 0, s.stream, (const uint8_t*)s.dComp, (const hlala_bgzf_block*)s.dDesc, (int)cnt, dOutBase ? dOutBase + blocks[s.first].uoff : s.dOut, s.dStatus); e = hipGetLastError(); }
         if(e == hipSuccess) e = hipEventRecord(s.ev[2], s.stream);
-        if(e == hipSuccess && ob) e = hipMemcpyAsync(s.hOut, s.dOut, ob, hipMemcpyDeviceToHost, s.stream);
+        if(e == hipSuccess && ob && !dOutBase) e = hipMemcpyAsync(s.hOut, s.dOut, ob, hipMemcpyDeviceToHost, s.stream);
         if(e == hipSuccess) e = hipMemcpyAsync(s.hStatus, s.dStatus, (size_t)cnt * sizeof(int), hipMemcpyDeviceToHost, s.stream);
         if(e == hipSuccess) e = hipEventRecord(s.ev[3], s.stream);
         s.busy = true;
@@ -2427,12 +2439,199 @@ static int bam_inflate_hook(void* inflater, const uint8_t* comp, size_t comp_byt
     if(rc != HLALA_OK && err) *err = f->err;
     return rc;
 }
+static int bam_scan_hook(void* inflater, hlala_host::bam_scan_round* R, std::string* err);      // (behind hlala_bam_scan, below)
 extern "C" int hlala_bam_extract_seeds_gpu(hlala_inflater* f, const char* path, int32_t n_intervals, const hlala_bam_interval* iv, int32_t long_read_mode, int32_t n_threads, int32_t flags,
                                            hlala_seed_batch** out)
 {
     static std::once_flag hookOnce;                  // (samples may decode on several threads)
-    std::call_once(hookOnce, []() { hlala_host::g_bam_inflate_hook = bam_inflate_hook; });
+    std::call_once(hookOnce, []() { hlala_host::g_bam_inflate_hook = bam_inflate_hook; hlala_host::g_bam_scan_hook = bam_scan_hook; });
     return hlala_host::bam_extract_seeds_impl(path, n_intervals, iv, long_read_mode, n_threads, flags, true, f, out);
+}
+
+// ---- the BAM record pass (include/hlala_gpu.h; kernel_bamscan.hip).  Three stretches of one stream, the host looking at the totals between them: upload, guess, link
+// (how many records: the size of the per-record arrays; too many re-hops end the call here) -- starts, parse, the two scans (the verdict, and what the caller's
+// arrays must hold) -- emit, download.
+static hipError_t scan_grow(hlala_inflater* f, int which, size_t bytes)
+{
+    ScanBuf& b = f->scan[which];
+    if(bytes <= b.cap) return hipSuccess;
+    if(b.p) { (void)hipFree(b.p); b.p = nullptr; b.cap = 0; }
+    const size_t want = bytes + bytes / 4 + 256;
+    const hipError_t r = hipMalloc(&b.p, want);
+    if(r == hipSuccess) b.cap = want; else b.p = nullptr;
+    return r;
+}
+// where the results of a scan go: asked for once their sizes are known (null: they do not fit, HLALA_E_CAPACITY)
+struct ScanSink { void* user; hlala_bam_rec* (*recs)(void*, int64_t); uint8_t* (*compact)(void*, size_t); };
+// data == null: the n bytes stand in scan[SCAN_DATA] already (the decoder's round buffer); the arguments have been checked
+static int scan_run(hlala_inflater* f, const uint8_t* data, size_t n, size_t first, int32_t last, const hlala_bam_scan_in* in, const ScanSink& sink, hlala_bam_scan_stats* stats)
+{
+    using namespace hlala_bamscan;
+    const auto tWall = std::chrono::steady_clock::now();
+    memset(stats, 0, sizeof(*stats));
+    stats->status_record = -1;
+    const uint32_t S = scan_slice(*in), maxRehops = scan_max_rehops(*in);
+    const uint32_t nSlices = (uint32_t)(((uint64_t)n + S - 1) / S);
+    stats->n_slices = nSlices;
+    if(nSlices == 0) return HLALA_OK;                          // no byte, no record
+    DevGuard g(f->device);
+    hipStream_t st = f->slot[0].stream;
+    hipError_t e = hipSuccess;
+    auto failed = [&](const char* what) { f->err = std::string("hlala_bam_scan: ") + what + ": " + hipGetErrorString(e); (void)hipStreamSynchronize(st); (void)hipGetLastError(); return HLALA_E_DEVICE; };
+    if(!f->scanEvReady) {
+        for(hipEvent_t& ev : f->scanEv) if(!ev && (e = hipEventCreate(&ev)) != hipSuccess) return failed("hipEventCreate");
+        f->scanEvReady = true;
+    }
+    auto grow = [&](int which, size_t bytes) -> hipError_t { return scan_grow(f, which, bytes); };
+    hipEvent_t* ev = f->scanEv;
+    auto ms = [&](int a, int b) { float t = 0; return hipEventElapsedTime(&t, ev[a], ev[b]) == hipSuccess ? (double)t : 0.0; };
+    // the intervals as one array: ref_iv_off | ref_iv | iv_start | iv_stop | iv_contig
+    const size_t nOff = in->n_ref > 0 ? (size_t)in->n_ref + 1 : 0, nIv = nOff ? (size_t)in->ref_iv_off[in->n_ref] : 0, nI = nIv ? (size_t)in->n_intervals : 0;
+    std::vector<int32_t> hIv(nOff + nIv + 3 * nI + 1, 0);
+    if(nOff) memcpy(hIv.data(), in->ref_iv_off, nOff * 4);
+    if(nIv) { memcpy(hIv.data() + nOff, in->ref_iv, nIv * 4); memcpy(hIv.data() + nOff + nIv, in->iv_start, nI * 4); memcpy(hIv.data() + nOff + nIv + nI, in->iv_stop, nI * 4); memcpy(hIv.data() + nOff + nIv + 2 * nI, in->iv_contig, nI * 4); }
+    if((data && (e = grow(SCAN_DATA, n)) != hipSuccess) || (e = grow(SCAN_SLICES, (size_t)nSlices * 5 * 4)) != hipSuccess || (e = grow(SCAN_TOTALS, sizeof(BamScanTotals))) != hipSuccess ||
+       (e = grow(SCAN_INTERVALS, hIv.size() * 4)) != hipSuccess) return failed("hipMalloc");
+    const uint8_t* dData = (const uint8_t*)f->scan[SCAN_DATA].p;
+    u32* dG = (u32*)f->scan[SCAN_SLICES].p; u32* dX = dG + nSlices; u32* dCf = dX + nSlices; u32* dEntry = dCf + nSlices; u32* dPrefix = dEntry + nSlices;
+    BamScanTotals* dT = (BamScanTotals*)f->scan[SCAN_TOTALS].p;
+    const int32_t* dIv = (const int32_t*)f->scan[SCAN_INTERVALS].p;
+    hlala_bam_scan_in din = *in;
+    din.ref_iv_off = dIv; din.ref_iv = dIv + nOff; din.iv_start = dIv + nOff + nIv; din.iv_stop = dIv + nOff + nIv + nI; din.iv_contig = dIv + nOff + nIv + 2 * nI;
+    BamScanTotals hT{}; hT.fail_key = ~0ull;
+    // ---- upload, guess, link
+    e = hipEventRecord(ev[0], st);
+    if(e == hipSuccess && data) e = hipMemcpyAsync((void*)dData, data, n, hipMemcpyHostToDevice, st);
+    if(e == hipSuccess) e = hipMemcpyAsync((void*)dIv, hIv.data(), hIv.size() * 4, hipMemcpyHostToDevice, st);
+    if(e == hipSuccess) e = hipMemcpyAsync(dT, &hT, sizeof(hT), hipMemcpyHostToDevice, st);
+    if(e == hipSuccess) e = hipEventRecord(ev[1], st);
+    if(e == hipSuccess) { hipLaunchKernelGGL(k_bam_guess, dim3((nSlices + 3) / 4), dim3(256), 0, st, dData, (u32)n, (u32)first, S, nSlices, (int)in->n_ref, dG, dX, dCf); e = hipGetLastError(); }
+    if(e == hipSuccess) e = hipEventRecord(ev[2], st);
+    if(e == hipSuccess) { hipLaunchKernelGGL(k_bam_link, dim3(1), dim3(64), 0, st, dData, (u32)n, (u32)first, S, nSlices, maxRehops, (const u32*)dG, (const u32*)dX, (const u32*)dCf, dEntry, dPrefix, dT); e = hipGetLastError(); }
+    if(e == hipSuccess) e = hipEventRecord(ev[3], st);
+    if(e == hipSuccess) e = hipMemcpyAsync(&hT, dT, sizeof(hT), hipMemcpyDeviceToHost, st);
+    if(e == hipSuccess) e = hipStreamSynchronize(st);
+    if(e != hipSuccess) return failed("upload / k_bam_guess / k_bam_link");
+    stats->ms_h2d = ms(0, 1); stats->ms_guess = ms(1, 2); stats->ms_link = ms(2, 3);
+    stats->n_rehops = hT.n_rehops;
+    auto done = [&](int rc) { stats->ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tWall).count(); return rc; };
+    if(hT.link_status == HLALA_BAMSCAN_TOO_MANY_REHOPS) { stats->status = HLALA_BAMSCAN_TOO_MANY_REHOPS; return done(HLALA_OK); }
+    const uint32_t nRec = hT.n_records;
+    if((uint64_t)nRec > (uint64_t)n / BAM_HEAD || hT.consumed > n) { f->err = "hlala_bam_scan: k_bam_link counted more records than the bytes hold"; return HLALA_E_DEVICE; }      // (cannot happen; sizes below rest on it)
+    stats->n_records = nRec; stats->consumed = hT.consumed;
+    // ---- starts, parse, the two scans
+    if((e = grow(SCAN_RECORDS, ((size_t)nRec * 3 + 1) * 4)) != hipSuccess || (e = grow(SCAN_OFFSETS, ((size_t)nRec + 1) * 2 * 8)) != hipSuccess) return failed("hipMalloc");
+    u32* dStart = (u32*)f->scan[SCAN_RECORDS].p; u32* dCnt = dStart + nRec; u32* dCsize = dCnt + nRec;
+    u64* dDescOff = (u64*)f->scan[SCAN_OFFSETS].p; u64* dCompOff = dDescOff + nRec + 1;
+    e = hipEventRecord(ev[4], st);
+    if(e == hipSuccess && nRec) { hipLaunchKernelGGL(k_bam_starts, dim3((nSlices + 255) / 256), dim3(256), 0, st, dData, (u32)n, S, nSlices, nRec, (const u32*)dEntry, (const u32*)dPrefix, dStart); e = hipGetLastError(); }
+    if(e == hipSuccess) e = hipEventRecord(ev[5], st);
+    if(e == hipSuccess && nRec) { hipLaunchKernelGGL(k_bam_parse, dim3((nRec + 255) / 256), dim3(256), 0, st, dData, (u32)n, nRec, din, (const u32*)dStart, dCnt, dCsize, dT); e = hipGetLastError(); }
+    if(e == hipSuccess) e = hipEventRecord(ev[6], st);
+    if(e == hipSuccess) { hipLaunchKernelGGL(k_bam_scan2, dim3(2), dim3(BAM_SCAN_THREADS), 0, st, nRec, (const u32*)dCnt, (const u32*)dCsize, dDescOff, dCompOff, dT); e = hipGetLastError(); }
+    if(e == hipSuccess) e = hipEventRecord(ev[7], st);
+    if(e == hipSuccess) e = hipMemcpyAsync(&hT, dT, sizeof(hT), hipMemcpyDeviceToHost, st);
+    if(e == hipSuccess) e = hipStreamSynchronize(st);
+    if(e != hipSuccess) return failed("k_bam_starts / k_bam_parse / k_bam_scan2");
+    stats->ms_starts = ms(4, 5); stats->ms_parse = ms(5, 6); stats->ms_scan = ms(6, 7);
+    stats->n_kept = (int64_t)hT.kept; stats->n_recs = (int64_t)hT.n_desc; stats->examined = (int64_t)hT.examined; stats->compact_bytes = (int64_t)hT.compact_bytes;
+    scan_verdict(hT.link_status, hT.link_record, hT.fail_key, last != 0, hT.consumed, n, nRec, &stats->status, &stats->status_record);
+    if(stats->status != HLALA_BAMSCAN_OK) return done(HLALA_OK);
+    if(hT.compact_bytes > (uint64_t)n) { f->err = "hlala_bam_scan: more compact bytes than bytes"; return HLALA_E_DEVICE; }                                                       // (cannot happen)
+    if(stats->n_recs == 0) return done(HLALA_OK);
+    hlala_bam_rec* recs = sink.recs(sink.user, stats->n_recs); uint8_t* compact = recs ? sink.compact(sink.user, (size_t)hT.compact_bytes) : nullptr;
+    if(!recs || !compact) {
+        f->err = "hlala_bam_scan: " + std::to_string(stats->n_recs) + " descriptors and " + std::to_string(stats->compact_bytes) + " compact bytes do not fit the caller's arrays";
+        return done(HLALA_E_CAPACITY);
+    }
+    // ---- emit, download
+    const size_t recBytes = (size_t)stats->n_recs * sizeof(hlala_bam_rec), compBytes = (size_t)hT.compact_bytes;
+    if((e = grow(SCAN_RECS, recBytes)) != hipSuccess || (e = grow(SCAN_COMPACT, compBytes)) != hipSuccess) return failed("hipMalloc");
+    hlala_bam_rec* dRecs = (hlala_bam_rec*)f->scan[SCAN_RECS].p; uint8_t* dCompact = (uint8_t*)f->scan[SCAN_COMPACT].p;
+    e = hipEventRecord(ev[8], st);
+    if(e == hipSuccess) { hipLaunchKernelGGL(k_bam_emit, dim3((nRec + 255) / 256), dim3(256), 0, st, dData, (u32)n, nRec, din, (const u32*)dStart, (const u32*)dCnt, (const u32*)dCsize, (const u64*)dDescOff, (const u64*)dCompOff, dRecs, dCompact); e = hipGetLastError(); }
+    if(e == hipSuccess) e = hipEventRecord(ev[9], st);
+    if(e == hipSuccess) e = hipMemcpyAsync(recs, dRecs, recBytes, hipMemcpyDeviceToHost, st);
+    if(e == hipSuccess && compBytes) e = hipMemcpyAsync(compact, dCompact, compBytes, hipMemcpyDeviceToHost, st);
+    if(e == hipSuccess) e = hipEventRecord(ev[10], st);
+    if(e == hipSuccess) e = hipStreamSynchronize(st);
+    if(e != hipSuccess) return failed("k_bam_emit / download");
+    stats->ms_emit = ms(8, 9); stats->ms_d2h = ms(9, 10);
+    return done(HLALA_OK);
+}
+extern "C" int hlala_bam_scan(hlala_inflater* f, const uint8_t* data, size_t n, size_t first, int32_t last, const hlala_bam_scan_in* in, hlala_bam_rec* recs, int64_t cap_recs,
+                              uint8_t* compact, size_t cap_compact, hlala_bam_scan_stats* stats)
+{
+    if(!f) return HLALA_E_ARG;
+    f->err.clear();
+    if(const char* bad = hlala_bamscan::scan_check_args(data, n, first, in, recs, cap_recs, compact, cap_compact, stats)) { f->err = std::string("hlala_bam_scan: ") + bad; return HLALA_E_ARG; }
+    struct Caller { hlala_bam_rec* recs; int64_t cap_recs; uint8_t* compact; size_t cap_compact; } c{recs, cap_recs, compact, cap_compact};
+    ScanSink sink{&c, [](void* u, int64_t k) -> hlala_bam_rec* { Caller* c = (Caller*)u; return k <= c->cap_recs ? c->recs : nullptr; },
+                  [](void* u, size_t k) -> uint8_t* { Caller* c = (Caller*)u; return k <= c->cap_compact ? c->compact : nullptr; }};
+    f->roundBytes = 0;
+    uint8_t none = 0;
+    return scan_run(f, n ? data : &none, n, first, last, in, sink, stats);
+}
+// One round of the decoder with HLALA_SEEDS_GPU_PARSE (hlala_host::bam_scan_round): carry to the front, inflate into the device round buffer, the record pass on it.
+static int bam_scan_hook(void* inflater, hlala_host::bam_scan_round* R, std::string* err)
+{
+    hlala_inflater* f = (hlala_inflater*)inflater;
+    if(!f || !R) return HLALA_E_ARG;
+    f->err.clear();
+    auto out = [&](int rc) { if(rc != HLALA_OK && err) *err = f->err; return rc; };
+    const size_t n = R->carry + R->seg_bytes;
+    R->n_gpu = R->n_retried = 0; R->fell_back = false; R->s_inflate = R->s_scan = 0; R->bytes_h2d = R->bytes_d2h = 0;
+    if(n >= ((size_t)1 << 32)) { f->err = "a round of 2^32 bytes or more: lower HLALA_BAM_SEGMENT_BYTES"; return out(HLALA_E_CAPACITY); }
+    if(R->carry > f->roundBytes) { f->err = "more bytes carried than the last round held"; return out(HLALA_E_STATE); }
+    const auto t0 = std::chrono::steady_clock::now();
+    DevGuard g(f->device);
+    hipStream_t st = f->slot[0].stream;
+    hipError_t e = hipSuccess;
+    auto failed = [&](const char* what) { f->err = std::string("BAM record pass: ") + what + ": " + hipGetErrorString(e); (void)hipStreamSynchronize(st); (void)hipGetLastError(); return out(HLALA_E_DEVICE); };
+    // the carried bytes: aside first (the round buffer may have to grow), then to the front
+    if(R->carry) {
+        if((e = scan_grow(f, SCAN_CARRY, R->carry)) != hipSuccess) return failed("hipMalloc");
+        e = hipMemcpyAsync(f->scan[SCAN_CARRY].p, (const uint8_t*)f->scan[SCAN_DATA].p + (f->roundBytes - R->carry), R->carry, hipMemcpyDeviceToDevice, st);
+        if(e == hipSuccess) e = hipStreamSynchronize(st);
+        if(e != hipSuccess) return failed("carry");
+    }
+    if((e = scan_grow(f, SCAN_DATA, n ? n : 1)) != hipSuccess) return failed("hipMalloc");
+    uint8_t* dData = (uint8_t*)f->scan[SCAN_DATA].p;
+    if(R->carry) {
+        e = hipMemcpyAsync(dData, f->scan[SCAN_CARRY].p, R->carry, hipMemcpyDeviceToDevice, st);
+        if(e == hipSuccess) e = hipStreamSynchronize(st);
+        if(e != hipSuccess) return failed("carry");
+    }
+    f->roundBytes = n;
+    std::vector<int32_t> status((size_t)R->n_blocks + 1, 0);
+    int rc = inflate_run(f, R->comp, R->comp_bytes, R->blocks, R->n_blocks, nullptr, R->seg_bytes, status.data(), nullptr, nullptr, nullptr, dData + R->carry);
+    if(rc != HLALA_OK) return out(rc);
+    std::vector<uint8_t> tmp;
+    for(int64_t k = 0; k < R->n_blocks; k++) {
+        const hlala_bgzf_block& b = R->blocks[k];
+        R->bytes_h2d += b.clen;
+        if(status[(size_t)k] == HLALA_INFLATE_OK) { R->n_gpu++; continue; }
+        // the host engine's verdict stands; its bytes go into place before the scan
+        tmp.resize(b.isize ? b.isize : 1);
+        if(R->host_inflate(R->user, k, tmp.data()) != 0) { f->err = "the host engine rejected the block as well"; return out(HLALA_E_STATE); }
+        if(b.isize && (e = hipMemcpy(dData + R->carry + b.uoff, tmp.data(), b.isize, hipMemcpyHostToDevice)) != hipSuccess) return failed("upload of a block inflated on the host");
+        R->n_retried++; R->bytes_h2d += b.isize;
+    }
+    R->s_inflate = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    const auto t1 = std::chrono::steady_clock::now();
+    if(const char* bad = hlala_bamscan::scan_check_args(dData, n, R->first, R->in, nullptr, 0, nullptr, 0, &R->stats)) { f->err = std::string("BAM record pass: ") + bad; return out(HLALA_E_ARG); }
+    ScanSink sink{R->user, R->alloc_recs, R->alloc_compact};
+    rc = scan_run(f, nullptr, n, R->first, R->last, R->in, sink, &R->stats);
+    if(rc != HLALA_OK) return out(rc);
+    if(R->stats.status == HLALA_BAMSCAN_OK) R->bytes_d2h += R->stats.n_recs * (int64_t)sizeof(hlala_bam_rec) + R->stats.compact_bytes;
+    if(R->stats.status == HLALA_BAMSCAN_TOO_MANY_REHOPS) {
+        uint8_t* fb = R->alloc_fallback(R->user, n ? n : 1);
+        if(!fb) { f->err = "no memory for the round's bytes"; return out(HLALA_E_STATE); }
+        if(n && (e = hipMemcpy(fb, dData, n, hipMemcpyDeviceToHost)) != hipSuccess) return failed("download of the round");
+        R->fell_back = true; R->bytes_d2h += (int64_t)n;
+    }
+    R->s_scan = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
+    return HLALA_OK;
 }
 
 extern "C" int hlala_abi_sizeof(const char* name)
@@ -2441,7 +2640,7 @@ extern "C" int hlala_abi_sizeof(const char* name)
     const std::string n(name);
 #define SZ(t) if(n == #t) return (int)sizeof(t);
     SZ(hlala_graph_desc) SZ(hlala_contigs_desc) SZ(hlala_params) SZ(hlala_graph_info) SZ(hlala_batch_in) SZ(hlala_seeds_in)
-    SZ(hlala_chains_out) SZ(hlala_pairs_out) SZ(hlala_batch_stats) SZ(hlala_exon_in) SZ(hlala_call_out) SZ(hlala_locus_desc) SZ(hlala_exon_positions_out) SZ(hlala_filter_params) SZ(hlala_filter_stats) SZ(hlala_insert_size_out) SZ(hlala_locus_info) SZ(hlala_locus_report_in) SZ(hlala_locus_report_out) SZ(hlala_unit_stats_out) SZ(hlala_pairs_packed_out) SZ(hlala_bgzf_block) SZ(hlala_inflate_stats)
+    SZ(hlala_chains_out) SZ(hlala_pairs_out) SZ(hlala_batch_stats) SZ(hlala_exon_in) SZ(hlala_call_out) SZ(hlala_locus_desc) SZ(hlala_exon_positions_out) SZ(hlala_filter_params) SZ(hlala_filter_stats) SZ(hlala_insert_size_out) SZ(hlala_locus_info) SZ(hlala_locus_report_in) SZ(hlala_locus_report_out) SZ(hlala_unit_stats_out) SZ(hlala_pairs_packed_out) SZ(hlala_bgzf_block) SZ(hlala_inflate_stats) SZ(hlala_bam_rec) SZ(hlala_bam_scan_in) SZ(hlala_bam_scan_stats)
 #undef SZ
     return -1;
 }

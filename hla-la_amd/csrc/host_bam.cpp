@@ -233,6 +233,8 @@ struct hlala_seed_batch {
     int64_t n_units = 0; int32_t unpaired = 0; int64_t examined = 0, n_seeds = 0, n_incomplete = 0;
     double seconds[6] = {0, 0, 0, 0, 0, 0}; int32_t threads = 1;
     int64_t inflate_counts[3] = {0, 0, 0};      // blocks inflated on the GPU, rejected there and inflated again on the host, inflated on the host only
+    int64_t parse_counts[3] = {0, 0, 0};        // records scanned on the GPU, rounds scanned there, rounds that fell back to the host's hop and parse
+    int64_t transfer_bytes[2] = {0, 0};         // bytes the GPU paths of the decoder moved to the device and back
     bool pinned = false;
     // page-locking window by window (hlala_seed_batch_pin(S, 2)): per bulk array the bytes locked so far, and the regions to unlock
     bool pin_lazy = false; std::mutex pin_mu; std::vector<size_t> pin_cursor; std::vector<std::pair<void*, size_t>> pin_regions;
@@ -374,6 +376,7 @@ void (*g_seed_batch_pin_upto)(hlala_seed_batch*, int64_t) = nullptr;      // set
 bool& seed_batch_pinned_flag(hlala_seed_batch* S) { return S->pinned; }
 void (*g_seed_batch_unpin)(hlala_seed_batch*) = nullptr;       // set by the GPU library (hlala_seed_batch_pin): a pinned batch is unpinned before it is freed
 bam_inflate_hook_t g_bam_inflate_hook = nullptr;               // set by the GPU library (hlala_bam_extract_seeds_gpu)
+bam_scan_hook_t g_bam_scan_hook = nullptr;                     // ... (HLALA_SEEDS_GPU_PARSE)
 }  // namespace hlala_host
 
 // (host code: no device involved)
@@ -393,6 +396,19 @@ extern "C" int hlala_pack_bases(const uint8_t* read_bases, const int64_t* read_o
 }
 extern "C" const char* hlala_bam_last_error() { return g_bam_error.c_str(); }
 extern "C" const char* hlala_bam_inflate_engine() { return Inflater::engine(); }
+// the texts this decoder throws, by the status of the record pass that stands for them (bam_scan_core.h runs the same checks in the same order)
+extern "C" const char* hlala_bam_scan_status_text(int32_t status)
+{
+    switch(status) {
+        case HLALA_BAMSCAN_BAD_LENGTH: return "truncated BAM record";
+        case HLALA_BAMSCAN_CORRUPT_RECORD: return "corrupt BAM record";
+        case HLALA_BAMSCAN_CORRUPT_TAG: return "corrupt BAM tag";
+        case HLALA_BAMSCAN_UNKNOWN_TAG_TYPE: return "unknown BAM tag type";
+        case HLALA_BAMSCAN_NO_AS: return "Can't get AS tag!";
+        case HLALA_BAMSCAN_UNPAIRED: return "unpaired record in a paired-end BAM (assert(currentAlignment.IsPaired()), processBAM.cpp:783)";
+        default: return "";
+    }
+}
 
 extern "C" int hlala_bam_extract_seeds(const char* path, int32_t n_intervals, const hlala_bam_interval* iv, int32_t long_read_mode, hlala_seed_batch** out)
 {
@@ -414,6 +430,7 @@ namespace {
 struct GpuRound {
     const Block* blocks; const uint8_t* comp; uint8_t* out; uint64_t u0; std::vector<int32_t>* status; std::atomic<uint8_t>* blockDone; Inflater* host;
     int64_t nGpu = 0, nRetried = 0; std::exception_ptr err;
+    int64_t bytesDown = 0;
     static int landed(void* user, int64_t first, int64_t count)
     {
         GpuRound& R = *(GpuRound*)user;
@@ -421,12 +438,26 @@ struct GpuRound {
             for(int64_t k = first; k < first + count; k++) {
                 const Block& b = R.blocks[k];
                 if((*R.status)[(size_t)k] != 0) { R.host->run(R.comp + b.coff, b.clen, R.out + (size_t)(b.uoff - R.u0), b.isize); R.nRetried++; }      // the host engine's verdict stands (it throws what the host path throws)
-                else R.nGpu++;
+                else { R.nGpu++; R.bytesDown += b.isize; }
                 R.blockDone[(size_t)k].store(1, std::memory_order_release);
             }
         } catch(...) { R.err = std::current_exception(); return 1; }
         return 0;
     }
+};
+// what the record pass of a round (hlala_host::bam_scan_round) calls back: the host engine for a rejected block, and where its outputs go
+struct ScanRound {
+    const Block* blocks; const uint8_t* comp; Inflater* host; std::exception_ptr err;
+    std::vector<hlala_bam_rec> recs; std::unique_ptr<uint8_t, BigFree> compact, fallback;
+    static int host_inflate(void* user, int64_t k, uint8_t* out)
+    {
+        ScanRound& R = *(ScanRound*)user;
+        try { const Block& b = R.blocks[k]; R.host->run(R.comp + b.coff, b.clen, out, b.isize); } catch(...) { R.err = std::current_exception(); return 1; }
+        return 0;
+    }
+    static hlala_bam_rec* alloc_recs(void* user, int64_t n) { ScanRound& R = *(ScanRound*)user; try { R.recs.resize((size_t)n); } catch(...) { R.err = std::current_exception(); return nullptr; } return R.recs.data(); }
+    static uint8_t* alloc_compact(void* user, size_t n) { ScanRound& R = *(ScanRound*)user; try { R.compact.reset(big_alloc(n)); } catch(...) { R.err = std::current_exception(); return nullptr; } return R.compact.get(); }
+    static uint8_t* alloc_fallback(void* user, size_t n) { ScanRound& R = *(ScanRound*)user; try { R.fallback.reset(big_alloc(n)); } catch(...) { R.err = std::current_exception(); return nullptr; } return R.fallback.get(); }
 };
 }  // namespace
 
@@ -435,6 +466,8 @@ try {
     if(!path || !out || n_intervals < 0 || (n_intervals > 0 && !iv) || n_threads < 0) return HLALA_E_ARG;
     *out = nullptr; g_bam_error.clear();
     if(gpu && (!gpuInflater || !g_bam_inflate_hook)) { g_bam_error = "hlala_bam_extract_seeds_gpu: no inflater"; return HLALA_E_ARG; }
+    const bool gpuParse = (flags & HLALA_SEEDS_GPU_PARSE) != 0;
+    if(gpuParse && (!gpu || !g_bam_scan_hook)) { g_bam_error = "HLALA_SEEDS_GPU_PARSE needs hlala_bam_extract_seeds_gpu"; return HLALA_E_ARG; }
     int T = n_threads;
     // Default: at most 32 threads.  Measured on a 256-thread host (tools/gpu_decode_threads.sh, 8.4 M pairs, 2.6 GB of BAM): 5.2 s on 8 threads, 3.5 on 16, 2.85 on 32,
     // 3.0 on 64, 3.3-3.7 on 128 -- the phases are passes over ~12 GB of inflated records bound by memory latency and by the first touch of their
@@ -506,14 +539,98 @@ try {
     // (tests: HLALA_BAM_TEST_HASH_BITS=k keeps the partition byte and k low bits of the name hashes -- many names per hash, the path that real samples never take)
     uint64_t hashMask = ~0ull;
     if(const char* e = getenv("HLALA_BAM_TEST_HASH_BITS")) { const int k = atoi(e); if(k >= 0 && k < 56) hashMask = (0xFFull << 56) | ((1ull << k) - 1); }
+    // HLALA_SEEDS_GPU_PARSE: the records of a round are found and parsed on the device, so the host reads the header itself -- it inflates the leading blocks with
+    // its own engine until the reference list is complete: n_ref, the intervals per reference id (as a CSR for hlala_bam_scan_in) and the offset of the first record
+    size_t firstRecord = 0;
+    std::vector<int32_t> csrOff, csrIv, ivStart, ivStop, ivContig;
+    int32_t scanMaxRehops = 0;
+    if(gpuParse) {
+        std::vector<uint8_t> hb; size_t nb = 0, o = 0;
+        auto have = [&](size_t k) {
+            while(hb.size() - o < k && nb < blocks.size()) { const Block& b = blocks[nb++]; const size_t at = hb.size(); hb.resize(at + b.isize); inflaters[0].run(mf.p + b.coff, b.clen, hb.data() + at, b.isize); }
+            return hb.size() - o >= k;
+        };
+        auto need = [&](size_t k) { if(!have(k)) throw Fail("truncated BAM header"); };
+        need(4); if(memcmp(hb.data(), "BAM\1", 4) != 0) throw Fail("not a BAM file"); o = 4;
+        need(4); const int32_t l_text = (int32_t)rd32(hb.data() + o); o += 4; if(l_text < 0 || l_text > (1 << 30)) throw Fail("truncated BAM header");
+        need((size_t)l_text); o += (size_t)l_text;
+        need(4); n_ref = (int32_t)rd32(hb.data() + o); o += 4; if(n_ref < 0) throw Fail("truncated BAM header");
+        refIntervals.resize((size_t)n_ref);
+        for(int i = 0; i < n_ref; i++) {
+            if(!have(4)) throw Fail("truncated BAM reference list");
+            const int32_t l_name = (int32_t)rd32(hb.data() + o); o += 4;
+            if(l_name < 1 || l_name > (1 << 20) || !have((size_t)l_name + 4)) throw Fail("truncated BAM reference list");
+            const std::string nm((const char*)hb.data() + o, strnlen((const char*)hb.data() + o, (size_t)l_name));
+            o += (size_t)l_name + 4;
+            auto it = intervalsOfRef.find(nm);
+            if(it != intervalsOfRef.end()) refIntervals[(size_t)i] = it->second;
+        }
+        headerDone = true; firstRecord = o;
+        csrOff.assign((size_t)n_ref + 1, 0);
+        for(int i = 0; i < n_ref; i++) { for(int ii : refIntervals[(size_t)i]) csrIv.push_back(ii); csrOff[(size_t)i + 1] = (int32_t)csrIv.size(); }
+        for(int i = 0; i < n_intervals; i++) { ivStart.push_back(iv[i].start_0based); ivStop.push_back(iv[i].stop_0based); ivContig.push_back(iv[i].contig); }
+        // (tests: HLALA_BAM_SCAN_MAX_REHOPS=k caps the re-hops of a round's k_bam_link; 0 makes any wrong guess a fall-back to the host's hop and parse)
+        if(const char* e = getenv("HLALA_BAM_SCAN_MAX_REHOPS")) { const int k = atoi(e); scanMaxRehops = k <= 0 ? -1 : k; }
+    }
     for(size_t b0 = 0; b0 < blocks.size();) {
         size_t b1 = b0; size_t segBytes = 0;
         while(b1 < blocks.size() && (segBytes == 0 || segBytes + blocks[b1].isize <= SEG_BYTES)) { segBytes += blocks[b1].isize; b1++; }
         auto t0 = Clock::now();
-        W->inflated.emplace_back(big_alloc(carry + segBytes));
-        uint8_t* const bufp = W->inflated.back().get(); const size_t bufn = carry + segBytes;
-        if(carry) memcpy(bufp, carryFrom, carry);
+        const size_t bufn = carry + segBytes;
         const uint64_t u0 = blocks[b0].uoff;
+        const bool lastSegment = b1 == blocks.size();
+        uint8_t* bufp = nullptr;
+        bool scanned = false; size_t scanConsumed = 0; double sGpuInflate = 0;
+        if(gpuParse) {
+            // ---- the round on the device: inflate into the device round buffer, the record pass there; descriptors and compact bytes come back
+            if(b0 == 0 && firstRecord > segBytes) throw Fail("truncated BAM header");              // (as on the host path: the header lies inside the first round)
+            const size_t nBlk = b1 - b0;
+            std::vector<hlala_bgzf_block> desc(nBlk);
+            for(size_t k = 0; k < nBlk; k++) { const Block& b = blocks[b0 + k]; desc[k].coff = b.coff; desc[k].clen = b.clen; desc[k].isize = b.isize; desc[k].uoff = b.uoff - u0; }
+            hlala_bam_scan_in sin; memset(&sin, 0, sizeof(sin));
+            sin.n_ref = n_ref; sin.n_intervals = n_intervals; sin.ref_iv_off = csrOff.data(); sin.ref_iv = csrIv.data(); sin.iv_start = ivStart.data(); sin.iv_stop = ivStop.data(); sin.iv_contig = ivContig.data();
+            sin.long_read_mode = long_read_mode ? 1 : 0; sin.max_rehops = scanMaxRehops; sin.hash_mask = hashMask; sin.first_seq = recSeq;
+            ScanRound U{blocks.data() + b0, mf.p, &inflaters[0]};
+            bam_scan_round R; memset((void*)&R, 0, sizeof(R));
+            R.comp = mf.p; R.comp_bytes = mf.n; R.blocks = desc.data(); R.n_blocks = (int64_t)nBlk; R.seg_bytes = segBytes; R.carry = carry; R.first = b0 == 0 ? firstRecord : 0; R.last = lastSegment ? 1 : 0; R.in = &sin;
+            R.user = &U; R.host_inflate = ScanRound::host_inflate; R.alloc_recs = ScanRound::alloc_recs; R.alloc_compact = ScanRound::alloc_compact; R.alloc_fallback = ScanRound::alloc_fallback;
+            std::string herr;
+            const int rc = g_bam_scan_hook(gpuInflater, &R, &herr);
+            if(U.err) std::rethrow_exception(U.err);
+            if(rc != HLALA_OK) throw Fail("BAM record pass on the GPU failed: " + herr);
+            S->inflate_counts[0] += R.n_gpu; S->inflate_counts[1] += R.n_retried; S->transfer_bytes[0] += R.bytes_h2d; S->transfer_bytes[1] += R.bytes_d2h;
+            sGpuInflate = R.s_inflate;
+            if(!R.fell_back) {
+                if(R.stats.status != HLALA_BAMSCAN_OK) throw Fail(hlala_bam_scan_status_text(R.stats.status));
+                const uint8_t* cb = U.compact.get();
+                if(U.compact) W->inflated.emplace_back(std::move(U.compact));                       // the compact buffer takes the place of the round's buffer: the Recs point into it
+                const std::vector<hlala_bam_rec>& D = U.recs;
+                const int64_t DCH = 8192, nDT = ((int64_t)D.size() + DCH - 1) / DCH;
+                parallel_for(nDT, T, [&](int64_t task, int t) {
+                    Arena& A = arenas[(size_t)t];
+                    const size_t a = (size_t)(task * DCH), z = std::min(D.size(), a + (size_t)DCH);
+                    for(size_t i = a; i < z; i++) {
+                        const hlala_bam_rec& x = D[i];
+                        Rec r; r.hash = x.hash; r.order = x.order; r.rec = cb + x.rec_off; r.contig = x.contig; r.pos = x.pos; r.as = x.as; r.l_seq = x.l_seq;
+                        r.n_cigar = x.n_cigar; r.nameLen = x.nameLen; r.which = x.which; r.flags = x.flags; r.l_read_name = x.l_read_name; r.pad1 = 0;
+                        A.part[(size_t)(x.hash >> 56)].push_back(r);
+                    }
+                });
+                arenas[0].examined += R.stats.examined;
+                recSeq += (uint64_t)R.stats.n_records;
+                scanned = true; scanConsumed = (size_t)R.stats.consumed;
+                S->parse_counts[0] += R.stats.n_records; S->parse_counts[1]++;
+            } else {
+                // more wrong guesses than one wavefront should mend: this round's bytes have come back, the host hops and parses them as ever
+                S->parse_counts[2]++;
+                W->inflated.emplace_back(std::move(U.fallback));
+                bufp = W->inflated.back().get();
+            }
+        } else {
+            W->inflated.emplace_back(big_alloc(bufn));
+            bufp = W->inflated.back().get();
+            if(carry) memcpy(bufp, carryFrom, carry);
+        }
         // The records of a round are found by hopping over their 4-byte length fields, one after the other from the round's first byte: the calling thread does
         // that BESIDE the threads that inflate the round's blocks (handed out in ascending order), right behind the block they have completed last -- on its own
         // after the inflate the hop was half of the parse phase, the one part of it that no thread count shortens.
@@ -522,7 +639,6 @@ try {
         for(size_t k = 0; k < nBlk; k++) blockDone[k].store(0, std::memory_order_relaxed);
         const uint8_t* d = bufp; const size_t dn = bufn;
         size_t o = 0;
-        const bool lastSegment = b1 == blocks.size();
         std::vector<size_t> recStart;
         recStart.reserve(dn / 200 + 16);
         // the round's blocks: on the host, handed out to T threads in ascending order; or on the GPU, fed by ONE thread (chunks land in ascending order; a block the
@@ -541,10 +657,22 @@ try {
             if(R.err) std::rethrow_exception(R.err);
             if(rc != HLALA_OK) throw Fail("BGZF inflate on the GPU failed: " + herr);
             S->inflate_counts[0] += R.nGpu; S->inflate_counts[1] += R.nRetried;
+            for(size_t k = 0; k < nBlk; k++) S->transfer_bytes[0] += blocks[b0 + k].clen;
+            S->transfer_bytes[1] += R.bytesDown;
         };
         if(!gpu) S->inflate_counts[2] += (int64_t)nBlk;
         auto inflateItem = [&](int64_t k, int t) { if(gpu) inflateGpu(k, t); else inflateHost(k, t); };
-        parallel_for_beside(gpu ? (int64_t)1 : (int64_t)nBlk, gpu ? std::min(T, 2) : T, inflateItem, [&](const std::atomic<bool>& stop) {
+        if(gpuParse && !scanned) {
+            o = b0 == 0 ? firstRecord : 0;
+            while(dn - o >= 4) {
+                const int32_t bs = (int32_t)rd32(d + o);
+                if(bs < 32 || bs > (1 << 28)) throw Fail("truncated BAM record");
+                if(dn - o - 4 < (size_t)bs) break;
+                recStart.push_back(o); o += 4 + (size_t)bs;
+            }
+        }
+        if(scanned) o = scanConsumed;
+        if(!gpuParse) parallel_for_beside(gpu ? (int64_t)1 : (int64_t)nBlk, gpu ? std::min(T, 2) : T, inflateItem, [&](const std::atomic<bool>& stop) {
             size_t ready = carry, kReady = 0;                   // bytes [0, ready) of the buffer are final: the carried bytes + the blocks before kReady
             // true when bytes [o, o + k) are there to be read (waits for the blocks that hold them); false: the round ends before o + k, or a worker failed
             auto avail = [&](size_t k) -> bool {
@@ -583,8 +711,9 @@ try {
                 recStart.push_back(o); o += 4 + (size_t)bs;
             }
         });
-        tInflate += since(t0); t0 = Clock::now();
-        if(lastSegment && o != dn) throw Fail("truncated BAM record");
+        if(gpuParse) { tInflate += sGpuInflate; tParse += since(t0) - sGpuInflate; } else tInflate += since(t0);
+        t0 = Clock::now();
+        if(!scanned && lastSegment && o != dn) throw Fail("truncated BAM record");
         const size_t nRec = recStart.size();
         const int64_t CH = std::max<int64_t>(16, std::min<int64_t>(4096, (int64_t)nRec / ((int64_t)T * 8) + 1)); const int64_t nTasks = ((int64_t)nRec + CH - 1) / CH;      // (long reads: few, large records per round)
         const uint64_t seq0 = recSeq;
@@ -655,7 +784,7 @@ try {
         recSeq += nRec;
         if(recSeq >= (1ull << 55)) throw Fail("more BAM records than the sequence numbers hold");
         // bytes of a record that continues in the next segment move to the front
-        carry = dn - o; carryFrom = d + o;
+        carry = dn - o; carryFrom = scanned ? nullptr : d + o;       // (scanned on the GPU: the bytes stay on the device, the next round's buffer gets them there)
         tParse += since(t0);
         b0 = b1;
     }
@@ -862,6 +991,18 @@ extern "C" int hlala_seed_batch_inflate_counts(const hlala_seed_batch* S, int64_
 {
     if(!S || !counts) return HLALA_E_ARG;
     for(int i = 0; i < 3; i++) counts[i] = S->inflate_counts[i];
+    return HLALA_OK;
+}
+extern "C" int hlala_seed_batch_parse_counts(const hlala_seed_batch* S, int64_t* counts)
+{
+    if(!S || !counts) return HLALA_E_ARG;
+    for(int i = 0; i < 3; i++) counts[i] = S->parse_counts[i];
+    return HLALA_OK;
+}
+extern "C" int hlala_seed_batch_transfer_bytes(const hlala_seed_batch* S, int64_t* bytes)
+{
+    if(!S || !bytes) return HLALA_E_ARG;
+    bytes[0] = S->transfer_bytes[0]; bytes[1] = S->transfer_bytes[1];
     return HLALA_OK;
 }
 extern "C" int hlala_seed_batch_timing(const hlala_seed_batch* S, double* seconds6, int32_t* n_threads)

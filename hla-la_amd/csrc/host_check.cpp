@@ -5,6 +5,7 @@
 
 #include "flat_graph.hpp"
 #include "inflate_core.h"
+#include "bam_scan_model.h"
 
 static thread_local std::string g_err;
 
@@ -85,5 +86,15 @@ int hlala_host_inflate_model(const uint8_t* comp, uint32_t clen, uint8_t* out, u
         }
         if(final) return produced == isize ? HLALA_INFLATE_OK : HLALA_INFLATE_OUTPUT_SIZE;
     }
+}
+// The BAM record pass of the device (kernel_bamscan.hip) run serially over the same core (bam_scan_model.h): the arguments, the return codes and every output of
+// hlala_bam_scan, without a device.  hlala_host_last_error() says what HLALA_E_ARG objects to.
+int hlala_host_bam_scan_model(const uint8_t* data, size_t n, size_t first, int32_t last, const hlala_bam_scan_in* in, hlala_bam_rec* recs, int64_t cap_recs, uint8_t* compact,
+                              size_t cap_compact, hlala_bam_scan_stats* stats)
+{
+    const char* why = nullptr;
+    const int rc = hlala_bamscan::scan_model(data, n, first, last, in, recs, cap_recs, compact, cap_compact, stats, &why);
+    g_err = why ? std::string("hlala_host_bam_scan_model: ") + why : std::string();
+    return rc;
 }
 }

@@ -43,6 +43,23 @@ extern void (*g_seed_batch_unpin)(hlala_seed_batch*);
 typedef int (*bam_inflate_hook_t)(void* inflater, const uint8_t* comp, size_t comp_bytes, const hlala_bgzf_block* blocks, int64_t n, uint8_t* out, size_t out_bytes, int32_t* status,
                                   int (*landed)(void*, int64_t, int64_t), void* user, std::string* err);
 extern bam_inflate_hook_t g_bam_inflate_hook;
+// The record pass of a round on the GPU (HLALA_SEEDS_GPU_PARSE): the second hook of the GPU library.  The device keeps the round's buffer [carry | this round's blocks]:
+// the last `carry` bytes of the previous round's buffer move to its front (device to device), the blocks are inflated into it (a block the kernel rejects is
+// inflated by host_inflate and uploaded into place), then hlala_bam_scan's passes run on it.  Descriptors and compact bytes come back through alloc_recs /
+// alloc_compact.  Where the scan ends with HLALA_BAMSCAN_TOO_MANY_REHOPS the round's bytes are downloaded into alloc_fallback's buffer for the host's own hop and parse.
+struct bam_scan_round {
+    const uint8_t* comp; size_t comp_bytes; const hlala_bgzf_block* blocks; int64_t n_blocks;      // uoff: from the first block of the round, without gaps
+    size_t seg_bytes, carry, first; int32_t last; const hlala_bam_scan_in* in;
+    void* user;
+    int (*host_inflate)(void* user, int64_t k, uint8_t* out);          // block k by the host engine into out[0, isize); non-zero: it failed, the caller holds the exception
+    hlala_bam_rec* (*alloc_recs)(void* user, int64_t n);
+    uint8_t* (*alloc_compact)(void* user, size_t bytes);
+    uint8_t* (*alloc_fallback)(void* user, size_t bytes);              // carry + seg_bytes
+    // results
+    hlala_bam_scan_stats stats; int64_t n_gpu, n_retried; bool fell_back; double s_inflate, s_scan; int64_t bytes_h2d, bytes_d2h;
+};
+typedef int (*bam_scan_hook_t)(void* inflater, bam_scan_round* R, std::string* err);
+extern bam_scan_hook_t g_bam_scan_hook;
 // hlala_bam_extract_seeds_opt (gpu = false) and hlala_bam_extract_seeds_gpu (gpu = true: the hook above inflates with `inflater`)
 int bam_extract_seeds_impl(const char* path, int32_t n_intervals, const hlala_bam_interval* iv, int32_t long_read_mode, int32_t n_threads, int32_t flags, bool gpu, void* inflater, hlala_seed_batch** out);
 

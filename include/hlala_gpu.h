@@ -482,6 +482,75 @@ int  hlala_bam_extract_seeds_gpu(hlala_inflater* inf, const char* bam_path, int3
 /* counts[3]: blocks inflated on the GPU, blocks the GPU rejected and the host engine ran again, blocks inflated on the host only */
 int  hlala_seed_batch_inflate_counts(const hlala_seed_batch* s, int64_t* counts);
 
+/* ------------------------------------------------------------------------------------------
+ * BAM record pass on the GPU (opt-in): record boundaries, the filters / CIGAR / AS tag / name hash of the host decoder's parse phase, and compaction of
+ * the kept records, on inflated BAM bytes (csrc/kernel_bamscan.hip; the rules are csrc/bam_scan_core.h, which the host runs as a model).  The buffer is
+ * cut into slices of slice_bytes, independent of BGZF blocks and of records: k_bam_guess finds the lowest plausible record start of every slice and hops
+ * from it to the slice end, k_bam_link walks the slices from `first` and takes a slice's guess only where it equals the true entry (otherwise it hops
+ * through the slice itself, a re-hop: correctness never rests on a guess), k_bam_starts writes the record starts, k_bam_parse runs the parse per record,
+ * k_bam_emit writes descriptors and compact bytes behind two exclusive scans.  Every pass is a launch of its own on one stream.
+ * ---------------------------------------------------------------------------------------- */
+#define HLALA_BAMSCAN_OK                0
+#define HLALA_BAMSCAN_BAD_LENGTH        1   /* "truncated BAM record": a length below 32 or above 1 << 28 on the true chain; with last != 0, bytes behind the last complete record */
+#define HLALA_BAMSCAN_CORRUPT_RECORD    2   /* "corrupt BAM record": l_seq < 0, the fixed part + name + CIGAR + bases + qualities exceed the record, l_read_name < 1               */
+#define HLALA_BAMSCAN_CORRUPT_TAG       3   /* "corrupt BAM tag": a tag runs off its record                                                                                        */
+#define HLALA_BAMSCAN_UNKNOWN_TAG_TYPE  4   /* "unknown BAM tag type"                                                                                                              */
+#define HLALA_BAMSCAN_NO_AS             5   /* "Can't get AS tag!"                                                                                                                 */
+#define HLALA_BAMSCAN_UNPAIRED          6   /* "unpaired record in a paired-end BAM ..."                                                                                           */
+#define HLALA_BAMSCAN_TOO_MANY_REHOPS   7   /* not an error of the file: k_bam_link met more wrong guesses than max_rehops allows; nothing was written                             */
+/* the host decoder's text for a status (the empty string for OK, TOO_MANY_REHOPS and unknown values) */
+const char* hlala_bam_scan_status_text(int32_t status);
+/* one kept alignment per interval it falls into: the decoder's record descriptor with an offset in place of its pointer.  rec_off: where the record's bytes
+ * from refID to the end of the qualities (the layout of a BAM record body; the tags are dropped) start in the compact buffer; a record that lies in several
+ * intervals gives several descriptors with the same rec_off.  order = ((first_seq + record index) << 8) | min(rank, 255); descriptors come in ascending order.
+ * l_seq: 0 for non-primary records.  flags: 1 reverse, 2 primary. */
+typedef struct {
+    uint64_t hash, order, rec_off;
+    int32_t contig, pos, as, l_seq;
+    uint16_t n_cigar, nameLen; uint8_t which, flags, l_read_name, pad1;
+} hlala_bam_rec;
+typedef struct {
+    int32_t n_ref, n_intervals;
+    const int32_t* ref_iv_off;      /* [n_ref + 1] CSR: the intervals of reference id r are ref_iv[ref_iv_off[r] .. ref_iv_off[r + 1])                       */
+    const int32_t* ref_iv;          /* interval numbers, in the order the decoder visits them                                                                */
+    const int32_t* iv_start;        /* [n_intervals] start_0based / stop_0based / contig of hlala_bam_interval                                               */
+    const int32_t* iv_stop;
+    const int32_t* iv_contig;
+    int32_t long_read_mode;
+    int32_t max_rehops;             /* 0 = default (1024 per call); negative = none: any wrong guess ends the call with HLALA_BAMSCAN_TOO_MANY_REHOPS        */
+    uint64_t hash_mask, first_seq;
+    uint32_t slice_bytes, pad;      /* 0 = default (16 KiB); a power of two of at least 64                                                                   */
+} hlala_bam_scan_in;
+/* n_records complete records were found, n_kept of them yield the n_recs descriptors; examined as the decoder counts it; consumed = the offset behind the
+ * last complete record; status / status_record: the failing record with the lowest index (-1: none).  With a status other than OK nothing is written to
+ * recs / compact and n_kept .. compact_bytes are what the passes that ran have counted.  Device times per pass from events. */
+typedef struct {
+    int64_t n_records, n_kept, n_recs, examined, consumed, compact_bytes;
+    int32_t status, pad; int64_t status_record;
+    int64_t n_slices, n_rehops;
+    double ms_h2d, ms_guess, ms_link, ms_starts, ms_parse, ms_scan, ms_emit, ms_d2h, ms_wall;
+} hlala_bam_scan_stats;
+/* data, recs and compact are host memory: upload, the five passes, download of the descriptors and the compact bytes.  `first`: offset of the first record;
+ * last != 0: the buffer ends the file, bytes behind the last complete record are HLALA_BAMSCAN_BAD_LENGTH as on the host.  Checked before anything is launched
+ * (HLALA_E_ARG): first > n, n >= 2^32, a bad CSR, a slice size that is no power of two or below 64.  HLALA_E_CAPACITY (n_recs and compact_bytes of the stats
+ * say what is needed) when recs or compact is too small: known after the parse pass, before anything is written to the caller.  Returns HLALA_OK whenever the
+ * call itself worked: stats->status is the verdict on the bytes. */
+int  hlala_bam_scan(hlala_inflater* inf, const uint8_t* data, size_t n, size_t first, int32_t last, const hlala_bam_scan_in* in,
+                    hlala_bam_rec* recs, int64_t cap_recs, uint8_t* compact, size_t cap_compact, hlala_bam_scan_stats* stats);
+/* Flag of hlala_bam_extract_seeds_gpu: the record pass of every round runs on the device as well.  The host reads the BAM header itself (it inflates the leading blocks
+ * with its own engine); a round's blocks are inflated into a device buffer [bytes carried from the round before | this round's blocks] and are NOT downloaded
+ * (statuses are; a block the kernel rejects is inflated by the host engine and uploaded into place); hlala_bam_scan's passes run there; only the descriptors and the
+ * compact bytes of the kept records come back, and the compact buffer takes the place of the round's inflated bytes in the decoder's working memory.  Grouping, sorting
+ * and the lazy fill are the host decoder's.  A file error throws the host path's text (hlala_bam_scan_status_text).  A round whose scan ends with
+ * HLALA_BAMSCAN_TOO_MANY_REHOPS falls back: its bytes are downloaded and hopped and parsed by the host.  HLALA_BAM_SCAN_MAX_REHOPS=k (tests) sets the cap, 0 = any
+ * wrong guess falls back. */
+#define HLALA_SEEDS_GPU_PARSE 2
+/* counts[3]: records scanned on the GPU, rounds scanned there, rounds that fell back to the host's hop and parse */
+int  hlala_seed_batch_parse_counts(const hlala_seed_batch* s, int64_t* counts);
+/* bytes[2]: what the decoder's GPU paths moved to the device (compressed blocks, blocks the host engine redid) and back (inflated blocks; or descriptors, compact
+ * bytes and the rounds that fell back) */
+int  hlala_seed_batch_transfer_bytes(const hlala_seed_batch* s, int64_t* bytes);
+
 /* Page-locked host memory for the buffers a caller hands to hlala_batch_create / hlala_batch_get_pairs_packed / the getters: transfers from and
  * to such buffers are true DMA (asynchronous, full PCIe rate); pageable buffers work everywhere, at about a third of the rate.  hlala_host_register
  * pins an existing allocation in place (e.g. the arrays of a seed batch: hlala_seed_batch_pin), hlala_host_unregister undoes it.  */
@@ -817,10 +886,11 @@ int  hlala_abi_sizeof(const char* struct_name);
  * 3 = hlala_batch_stats ends with n_dp_jump_free / ms_dp_jump_free, hlala_batch_in with read_bases_packed / first_read (round 4);
  * 4 = hlala_batch_stats ends with n_dp_band / n_dp_band_failed / n_dp_jump_free_failed / ms_dp_band (round 5);
  * 5 = ... with n_dp_band2 / n_dp_band2_failed / ms_dp_band2, hlala_set_tail_pool / hlala_flush / hlala_comm_* exist (round 6);
- * 6 = hlala_inflater_* / hlala_bgzf_inflate / hlala_bam_extract_seeds_gpu / hlala_seed_batch_inflate_counts exist (additive).  A caller compares
+ * 6 = hlala_inflater_* / hlala_bgzf_inflate / hlala_bam_extract_seeds_gpu / hlala_seed_batch_inflate_counts exist (additive);
+ * 7 = hlala_bam_scan / hlala_bam_scan_status_text and their structs, HLALA_SEEDS_GPU_PARSE, hlala_seed_batch_parse_counts / _transfer_bytes exist (additive).  A caller compares
  * hlala_abi_version() with the HLALA_ABI_VERSION it was compiled against and refuses to run on a mismatch (hla-la_amd/__init__.py and
  * hla-la_amd/host/hlala_host.hpp do). */
-#define HLALA_ABI_VERSION 6
+#define HLALA_ABI_VERSION 7
 int  hlala_abi_version(void);
 /* ---- debug / diagnostics section (tests and tools only; not part of the path the reference calls).  Layouts may change between rounds: the constants below are
  * checked against the library's own at compile time (hlala_api.hip). */

@@ -1,11 +1,15 @@
 #!/usr/bin/env python3
-"""BGZF inflate: the host engine against the GPU kernel on one BAM (its output is meant for profiles/inflate_gpu.txt, which is yet to be produced).
+"""BGZF inflate and the BAM record pass: the host decoder against GPU inflate and against GPU inflate + parse on one BAM (its output is meant for
+profiles/inflate_gpu.txt and profiles/bam_scan_gpu.txt).
 
 A sample is drawn with the generators of bench.py's end-to-end leg (tools/synth.py: make_world_m, make_batch_m, BamWriter on tools/graphm/bamwriter.cpp;
 reference names of tools/graphm_dir.py) and written coordinate-sorted at level 1, at least --min-inflated-gb of records.  hlala_bam_extract_seeds_opt and
 hlala_bam_extract_seeds_gpu then decode it alternately: one warm-up each, --runs timed runs each, the same thread count.  Printed per run: the six phase times
 of hlala_seed_batch_timing; for the GPU path also the blocks by who inflated them; and once, hlala_bgzf_inflate on all blocks of the file (hlala_inflate_stats:
-upload, kernel, download, wall; blocks/s and inflated GB/s).  There is no threshold: the yardstick is the host engine's inflate phase on the same file and box."""
+upload, kernel, download, wall; blocks/s and inflated GB/s).  The third path, hlala_bam_extract_seeds_gpu with HLALA_SEEDS_GPU_PARSE, runs in the same alternation;
+every run also prints the bytes that crossed PCIe each way (hlala_seed_batch_transfer_bytes) and, for the third path, records / rounds / rounds that fell back.  Last,
+hlala_bam_scan alone on the first --scan-mb MiB of the inflated file at slices of 4, 16 and 64 KiB: device time per pass (median and range over --runs calls), re-hops,
+and the share of the kept records that is tags (what compaction saves).  There is no threshold: the yardstick is the host decoder on the same file and box."""
 import argparse
 import os
 import sys
@@ -32,6 +36,43 @@ def bgzf_blocks(path):
     return raw, out
 
 
+def scan_alone(P, inf, inflated, intervals, args):
+    """hlala_bam_scan on the first --scan-mb MiB of the inflated file (host memory: the upload is part of the call and timed on its own)"""
+    n_ref = int(inflated[8 + int(inflated[4:8].view("<i4")[0]):][:4].view("<i4")[0]); o = 12 + int(inflated[4:8].view("<i4")[0])
+    by_name = {}
+    for i, iv in enumerate(intervals):
+        by_name.setdefault(iv[0], []).append(i)
+    ref_iv = []
+    for _ in range(n_ref):
+        ln = int(inflated[o:o + 4].view("<i4")[0]); nm = inflated[o + 4:o + 4 + ln - 1].tobytes().decode(); o += 8 + ln
+        ref_iv.append(by_name.get(nm, []))
+    n = min(inflated.size, args.scan_mb << 20)
+    data = inflated[:n]
+    passes = ("h2d", "guess", "link", "starts", "parse", "scan", "emit", "d2h", "wall")
+    for S in (4096, 16384, 65536):
+        a, keep = P.bam_scan_in(n_ref, ref_iv, [iv[1:] for iv in intervals], slice_bytes=S)
+        rc, _, _, st = inf.bam_scan(data, a, first=o, cap_recs=0, cap_compact=0)                     # how much comes back
+        if st.status != 0:
+            print("hlala_bam_scan, slices of %d: status %s at record %d" % (S, P.BAMSCAN_STATUS[st.status], st.status_record)); continue
+        nr, nc = st.n_recs, st.compact_bytes
+        t = {k: [] for k in passes}
+        for i in range(args.runs + 1):
+            rc, recs, comp, st = inf.bam_scan(data, a, first=o, cap_recs=nr, cap_compact=nc)
+            assert rc == 0 and st.status == 0
+            if i:
+                for k in passes:
+                    t[k].append(getattr(st, "ms_" + k))
+        print("hlala_bam_scan alone, %.3f GB inflated, slices of %d KiB: %d records (%d kept, %d descriptors), %d slices, %d re-hops (cap %d); %.3f GB of compact bytes + %.3f GB of descriptors come back" % (
+            n / 1e9, S >> 10, st.n_records, st.n_kept, st.n_recs, st.n_slices, st.n_rehops, P.BAMSCAN_DEFAULT_MAX_REHOPS, nc / 1e9, nr * P.BAM_REC_DTYPE.itemsize / 1e9))
+        print("    ms per pass, median (min .. max) of %d calls: %s" % (args.runs, "  ".join("%s %.2f (%.2f .. %.2f)" % (k, float(np.median(t[k])), min(t[k]), max(t[k])) for k in passes)))
+        dev = sum(float(np.median(t[k])) for k in ("guess", "link", "starts", "parse", "scan", "emit"))
+        print("    the six passes: %.2f ms = %.2f GB/s of inflated bytes; consumed %.3f GB" % (dev, n / 1e9 / (dev / 1e3), st.consumed / 1e9))
+    if st.status == 0 and st.n_kept:
+        print("share of the scanned bytes that comes back as compact bytes: %.3f (all records are examined; %.3f of them are kept; what is dropped of a kept record is its length field and its tags)" % (
+            nc / max(1, st.consumed - o), st.n_kept / max(1, st.n_records)))
+        print("    -> with records of one kind, length field + tags are about %.3f of a kept record" % (1.0 - (nc / max(1, st.consumed - o)) / (st.n_kept / max(1, st.n_records))))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--pairs", type=int, default=1 << 20, help="pairs per generated chunk of the sample")
@@ -41,6 +82,7 @@ def main():
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--chunk-mb", type=int, default=0, help="compressed MiB staged per launch (0 = the library's default)")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--scan-mb", type=int, default=256, help="inflated MiB handed to hlala_bam_scan alone (below 4096)")
     ap.add_argument("--bam", default="", help="use this BAM (reference names PRG_<n>) instead of generating one; needs --levels of the world it was made from")
     ap.add_argument("--no-gpu", action="store_true", help="host engine only (a box without a GPU: checks the generator and the host figures)")
     args = ap.parse_args()
@@ -80,22 +122,27 @@ def main():
 
     def run(label, opener, timed):
         t = time.time(); S = opener(); wall = time.time() - t
-        tm = S.timing(); cnt = S.inflate_counts(); units = S.n_units; S.close()
+        tm = S.timing(); cnt = S.inflate_counts(); pc = S.parse_counts(); tb = S.transfer_bytes(); units = S.n_units; S.close()
         if timed:
-            print("%-5s wall %.3f s  %s  threads %d  units %d  blocks gpu/retried/host %d/%d/%d" % (
-                label, wall, "  ".join("%s %.3f" % (k, tm[k]) for k in keys), tm["threads"], units, cnt[0], cnt[1], cnt[2]))
-        return tm["inflate"]
+            print("%-9s wall %.3f s  %s  threads %d  units %d  blocks gpu/retried/host %d/%d/%d  records on the GPU %d in %d rounds, %d rounds fell back  PCIe up %.3f GB, down %.3f GB" % (
+                label, wall, "  ".join("%s %.3f" % (k, tm[k]) for k in keys), tm["threads"], units, cnt[0], cnt[1], cnt[2], pc[0], pc[1], pc[2], tb[0] / 1e9, tb[1] / 1e9))
+        return tm["inflate"], tm["inflate"] + tm["parse"], wall
     host = lambda: P.bam_open_seeds(lib, bam, intervals, threads=args.threads, flags=P.SEEDS_PACKED)                 # noqa: E731
     gpu = (lambda: inf.bam_open_seeds(bam, intervals, threads=args.threads, flags=P.SEEDS_PACKED)) if inf else None      # noqa: E731
-    res = {"host": [], "gpu": []}
+    gpu_parse = (lambda: inf.bam_open_seeds(bam, intervals, threads=args.threads, flags=P.SEEDS_PACKED | P.SEEDS_GPU_PARSE)) if inf else None      # noqa: E731
+    res = {"host": [], "gpu": [], "gpu+parse": []}
     for i in range(args.runs + 1):
         res["host"].append(run("host", host, i > 0))
         if gpu:
             res["gpu"].append(run("gpu", gpu, i > 0))
-    for k in ("host", "gpu"):
+            res["gpu+parse"].append(run("gpu+parse", gpu_parse, i > 0))
+    for k in ("host", "gpu", "gpu+parse"):
         if len(res[k]) > 1:
-            v = res[k][1:]
+            v = [x[0] for x in res[k][1:]]
             print("inflate phase, %s: median %.3f s (%.2f GB/s inflated) of %s" % (k, float(np.median(v)), n_inflated / 1e9 / float(np.median(v)), ["%.3f" % x for x in v]))
+            for j, what in ((1, "inflate + parse phases"), (2, "decode, wall")):
+                v = [x[j] for x in res[k][1:]]
+                print("%s, %s: median %.3f s, range %.3f .. %.3f of %d runs" % (what, k, float(np.median(v)), min(v), max(v), len(v)))
     if inf:
         # the kernel and its copies alone: every block of the file in one call, into one pageable buffer
         out = np.empty(n_inflated, np.uint8); desc = []; u = 0
@@ -107,6 +154,7 @@ def main():
         print("hlala_bgzf_inflate, all blocks in one call (second call): upload %.1f ms, kernel %.1f ms, download %.1f ms (device times summed over the chunks; they overlap), "
               "wall %.1f ms: %.0f blocks/s, %.2f GB/s inflated" % (st.ms_h2d, st.ms_kernel, st.ms_d2h, st.ms_wall, st.n_blocks / (st.ms_wall / 1e3), n_inflated / 1e9 / (st.ms_wall / 1e3)))
         print("kernel alone: %.2f GB/s inflated; download alone: %.2f GB/s" % (n_inflated / 1e9 / (st.ms_kernel / 1e3), n_inflated / 1e9 / max(1e-9, st.ms_d2h / 1e3)))
+        scan_alone(P, inf, out, intervals, args)
         inf.close()
     if tmp:
         import shutil
