@@ -3,36 +3,8 @@ import numpy as np
 import pytest
 
 import oracle_binding as ob
+from exonpos_edge_cases import fake_pairs, locus
 from tools import synth
-
-
-def locus(G, a, exons):
-    """level_min = a; `exons` = list of (start offset, length) inside the locus; exon positions run through consecutively."""
-    width = max(s + n for s, n in exons)
-    l2e = np.full(width, -1, np.int32); k = 0
-    for s, n in exons:
-        l2e[s:s + n] = np.arange(k, k + n); k += n
-    assert a + width < G
-    return a, l2e
-
-
-def fake_pairs(mates, stride=24):
-    """mates = list of (levels, gchars, schars, mapq chars) per mate; reads are the non-gap sequence characters with quality chars given per base."""
-    n = len(mates) // 2
-    pr = dict(pair_status=np.zeros(n, np.int32), n_cols=np.zeros(2 * n, np.int32), col_level=np.zeros(2 * n * stride, np.int32),
-              col_gchar=np.zeros(2 * n * stride, np.uint8), col_schar=np.zeros(2 * n * stride, np.uint8), col_mapq=np.zeros(2 * n * stride, np.uint8),
-              mate_mapq=np.ones(2 * n), strands_valid=np.ones(n, np.uint8))
-    off = [0]; bases = []; quals = []
-    for r, (lv, g, s, mq, q) in enumerate(mates):
-        m = len(lv); pr["n_cols"][r] = m
-        pr["col_level"][r * stride: r * stride + m] = lv
-        pr["col_gchar"][r * stride: r * stride + m] = np.frombuffer(g.encode(), np.uint8)
-        pr["col_schar"][r * stride: r * stride + m] = np.frombuffer(s.encode(), np.uint8)
-        pr["col_mapq"][r * stride: r * stride + m] = np.frombuffer(mq.encode(), np.uint8)
-        rb = s.replace("_", ""); assert len(q) == len(rb)
-        bases.append(np.frombuffer(rb.encode(), np.uint8)); quals.append(np.frombuffer(q.encode(), np.uint8)); off.append(off[-1] + len(rb))
-    batch = dict(n_pairs=n, read_off=np.array(off, np.int32), read_bases=np.concatenate(bases), read_quals=np.concatenate(quals))
-    return pr, batch, stride
 
 
 def test_oracle_exon_positions_hand_derived(oracle):

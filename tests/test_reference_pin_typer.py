@@ -18,6 +18,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import exonpos_edge_cases as ee
+import exonpos_reference as er
 import oracle_binding as ob
 import ref_binding as rb
 import ref_typer as rt
@@ -151,12 +153,18 @@ def test_family_matches_the_reference(pkg, oracle, ref, tmp_path, family):
 
     class Desc:
         pass
-    n_entries = 0
+    n_entries = 0; counts = dict.fromkeys(ee.CENSUS_KEYS, 0)
+    ins = (b["insert_mean"], b["insert_sd"]) if case["paired"] else (0.0, 0.0)
+    walk = er.Model(pairs, b, st, rt.PHRED_TO_P_CORRECT, unpaired=not case["paired"])
     for locus in rt.LOCI:
         D = Desc(); D.level_min, D.level_to_exon = loci[locus]
         eo = be.exon_positions(D)
         compare_exon_positions(eo, R["exon"][locus], (family, locus))
         n_entries += eo["n_reads"]
+        # what the exon-position stage meets in this family (tests/exonpos_edge_cases.py: census; the counts are recorded in DESIGN.md)
+        for k, v in ee.census(pairs, b, st, er.make_locus(D.level_min, D.level_to_exon, ins[0], ins[1], pair_mask=inc), unpaired=not case["paired"], model=walk).items():
+            counts[k] += v
+    print("census of %s over its %d loci: %s" % (family, len(rt.LOCI), {k: v for k, v in counts.items() if v}))
     assert n_entries > 20
     # ---- the files
     out_p = tmp_path / "product"
