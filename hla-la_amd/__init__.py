@@ -824,6 +824,7 @@ BUILD_AGENT_RELEASE = 2      # hlala_build_flags(): the in-memory DP class relea
 EXPORTED_SYMBOLS = [
     "hlala_debug_work_counters", "hlala_debug_dp_items", "hlala_debug_counters", "hlala_debug_buffer", "hlala_debug_memory",
     "hlala_set_tail_pool", "hlala_flush",
+    "hlala_set_pair_overflow", "hlala_get_pair_overflow", "hlala_pair_overflow_need", "hlala_batch_get_pair_overflow",
     "hlala_comm_create", "hlala_comm_destroy", "hlala_comm_uses_rccl", "hlala_comm_last_error", "hlala_gather_pair_records", "hlala_reduce_coverage",
     "hlala_create", "hlala_destroy", "hlala_last_error", "hlala_graph_get_info", "hlala_graph_get_nodes",
     "hlala_graph_get_paths", "hlala_graph_get_gap_stretch", "hlala_batch_create",
@@ -841,6 +842,17 @@ EXPORTED_SYMBOLS = [
     "hlala_bam_scan", "hlala_bam_scan_status_text", "hlala_seed_batch_parse_counts", "hlala_seed_batch_transfer_bytes",
     "hlala_locus_cluster_kmers", "hlala_type_locus", "hlala_kmer_presence", "hlala_kmer_keep_reads", "hlala_kmer_presence_kept", "hlala_kmer_forget_reads", "hlala_unit_alignment_stats", "hlala_typer_write_summary", "hlala_typer_begin_output", "hlala_locus_write_files", "hlala_locus_write_pairs_file", "hlala_typer_end_output",
 ]
+
+
+PAIR_OVERFLOW_WAVES = 64     # HLALA_PAIR_OVERFLOW_WAVES of include/hlala_gpu.h
+
+
+def pair_overflow_need(n1, n2, max_columns, unpaired=False):
+    """hlala_pair_overflow_need: slab bytes that one pair with n1 x n2 kept alignments needs in the overflow class (the formula is in include/hlala_gpu.h)."""
+    lib = load_library()
+    lib.hlala_pair_overflow_need.argtypes = [C.c_int64, C.c_int64, C.c_int32, C.c_int]
+    lib.hlala_pair_overflow_need.restype = C.c_int64
+    return int(lib.hlala_pair_overflow_need(int(n1), int(n2), int(max_columns), int(bool(unpaired))))
 
 
 class Context:
@@ -991,6 +1003,18 @@ class Context:
     def kmer_forget_reads(self):
         self.lib.hlala_kmer_forget_reads.argtypes = [C.c_void_p]; self.lib.hlala_kmer_forget_reads.restype = None
         self.lib.hlala_kmer_forget_reads(self.h)
+
+    def set_pair_overflow(self, scratch_bytes: int):
+        """hlala_set_pair_overflow: 0 = off (the default); else pairs beyond the pairing capacities are scored out of that much device scratch."""
+        self.lib.hlala_set_pair_overflow.argtypes = [C.c_void_p, C.c_int64]
+        self._check(self.lib.hlala_set_pair_overflow(self.h, int(scratch_bytes)), "hlala_set_pair_overflow")
+
+    def pair_overflow(self):
+        """hlala_get_pair_overflow: (scratch bytes set, slab bytes per wave)."""
+        a, b = C.c_int64(0), C.c_int64(0)
+        self.lib.hlala_get_pair_overflow.argtypes = [C.c_void_p, c_i64p, c_i64p]
+        self._check(self.lib.hlala_get_pair_overflow(self.h, C.byref(a), C.byref(b)), "hlala_get_pair_overflow")
+        return int(a.value), int(b.value)
 
     def set_tail_pool(self, k: int):
         """hlala_set_tail_pool: the broad / large / in-memory DP classes of up to k consecutive alignments run in one launch per class."""
@@ -1187,6 +1211,13 @@ class Batch:
         self.ctx.lib.hlala_debug_work_counters.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_int]
         self.ctx._check(self.ctx.lib.hlala_debug_work_counters(self.ctx.h, self.b, wc, DEBUG_WC_N), "hlala_debug_work_counters")
         return np.array(wc[:], np.int64)
+
+    def pair_overflow_counts(self):
+        """hlala_batch_get_pair_overflow: (pairs listed for the overflow class, scored there, refused for want of slab) of the batch's last pairing."""
+        out = (C.c_int64 * 3)()
+        self.ctx.lib.hlala_batch_get_pair_overflow.argtypes = [C.c_void_p, C.c_void_p, c_i64p]
+        self.ctx._check(self.ctx.lib.hlala_batch_get_pair_overflow(self.ctx.h, self.b, out), "hlala_batch_get_pair_overflow")
+        return tuple(int(x) for x in out)
 
     def dp_items(self):
         """(items [2 * n_chains, 8], retry lists [16 * n_chains]) of the batch's last extension stage (hlala_debug_dp_items)."""

@@ -67,7 +67,9 @@ template <template <class> class Ptr> struct DevBatchT {
                                     //      [1]/[10] left / right items fetched, [12..35] retry lists (count, fetched) per tier 1..6 and direction
     Ptr<int> retry_list;                // [16*n_chains] DP items that outgrew a capacity class: (tier 1..6) x (left, right) x n_chains; rows 14 / 15: the fail-over lists of the band kernels and the
                                     //      jump-free instantiation (WC_FO_COUNT)
-    Ptr<int> pair_multi;                // [2 passes][2 classes][n_pairs] pairs with several combinations, listed by k_pair_chains for k_pair_multi (kernel_pair.hip; counts in work_counter[WC_PAIR_MULTI ...])
+    Ptr<int> pair_multi;                // [2 passes][2 classes][n_pairs] pairs with several combinations, listed by k_pair_chains for k_pair_multi (kernel_pair.hip; counts in work_counter[WC_PAIR_MULTI ...]);
+                                    //      and, 4 n_pairs behind the lists of its pass ([4 n_pairs ...] main, [6 n_pairs ...] side stream), the pairs beyond the capacities, listed for
+                                    //      k_pair_overflow (counts in work_counter[WC_PAIR_OVER ...]): 7 n_pairs entries in all
     Ptr<uint8_t> pair_deferred;         // [n_pairs] 1: a DP call of the pair went to the in-memory class; with the fused entry point its chains are stitched and
                                     //           the pair is scored in a second pass, after that class (which runs on a side stream next to the first pass)
     // ---- position order of the chains (kernel_order.hip): the kernels that walk the graph take their chains in this order, so that the work in flight at
@@ -127,9 +129,11 @@ __host__ __device__ inline int dpl_of_class(int cls) { return cls == 0 ? DPL_GEN
 // [40..47] round 6: the lists of the pairs with several combinations (k_pair_chains -> k_pair_multi): per pass (main / side stream) count and fetched of class 0, of class 1; round 5: items fetched by the three band kernels (left, right each), the fail-over list's counts and fetch counters, band calls that
 // failed over, band calls listed, jump-free calls that met a jump, and why band calls failed ([WC_BAND_WHY + 2 .. + 5]: past the staged levels, past the linear run, too
 // many iterations, too many tied end cells)
-// [72..87] unused: they counted the calls of the two-track band kernels of round 6, which were removed; WC_N stays 88 so that the debug export
+// [72..79] the overflow lists of the pairing passes (k_pair_chains -> k_pair_overflow, kernel_pair_overflow.hip): per pass (main / side stream) pairs listed, fetched,
+// scored, refused for want of slab
+// [80..87] unused: [72..87] counted the calls of the two-track band kernels of round 6, which were removed; WC_N stays 88 so that the debug export
 // (include/hlala_gpu.h: HLALA_DEBUG_WC_N) keeps its size
-enum { WC_PAIR_MULTI = 40, WC_BAND_FETCH = 48, WC_FO_COUNT = 54, WC_FO_FETCH = 56, WC_BAND_FAILED = 58, WC_BAND_CALLS = 59, WC_JF_FAILED = 60, WC_BAND_WHY = 62, WC_BAND_TIED = 68,
+enum { WC_PAIR_MULTI = 40, WC_PAIR_OVER = 72, WC_BAND_FETCH = 48, WC_FO_COUNT = 54, WC_FO_FETCH = 56, WC_BAND_FAILED = 58, WC_BAND_CALLS = 59, WC_JF_FAILED = 60, WC_BAND_WHY = 62, WC_BAND_TIED = 68,
        WC_N = 88 };
 // the fail-over list of the first classes: calls the band kernel (kernel_dp_band.hip) or the jump-free instantiation could not finish; k_dp<DpTiny, 0> draws it after
 // its own lists.  Entries (slots of dp_items) at retry_list[(14 + direction) * n_chains ...], counts in work_counter[WC_FO_COUNT + direction].

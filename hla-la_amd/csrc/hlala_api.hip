@@ -23,6 +23,7 @@
 #include "kernel_project.hip"
 #include "kernel_order.hip"
 #include "kernel_pair.hip"
+#include "kernel_pair_overflow.hip"
 #include "kernel_typer.hip"
 #include "kernel_call.hip"
 #include "kernel_exonpos.hip"
@@ -100,6 +101,8 @@ struct hlala_ctx {
     char* proj_slabs = nullptr; size_t proj_slab_bytes = 0; int proj_grid = 0, pair_grid = 0, pair_lean_grid = 0;
     char* rethread_slabs = nullptr; size_t rethread_slab_bytes = 0; int rethread_grid = 0;      // k_rethread_chains: back pointers of one chain per wave (short reads; HLALA_RETHREAD=0 turns the kernel off)
     double* pair_scratch = nullptr;   // [2 * pair_grid][PAIR_COMB]: combination tables of the rare pairs with more than PAIR_COMB_LDS combinations (main- and side-stream pass)
+    // the overflow class of the pairing stage (hlala_set_pair_overflow; kernel_pair_overflow.hip): [2 passes][PAIR_OVER_WAVES] slabs of pair_over_slab_bytes; null: off
+    char* pair_over_slabs = nullptr; long long pair_over_scratch = 0, pair_over_slab_bytes = 0;
     char* proj_long_slabs = nullptr; size_t proj_long_slab_bytes = 0;      // long reads only (max_columns > 512): column / window arrays of k_project_chains<ProjLdsLong>
     void* create_scratch = nullptr; size_t create_scratch_bytes = 0; bool create_scratch_pinned = false;      // host scratch of hlala_batch_create (page-locked when the runtime grants it; one caller thread per context)
     int long_chunk_nodes = 1 << 20, long_max_segs = 1 << 20;      // (batch.h; the kernel clamps them to its array sizes)
@@ -583,6 +586,7 @@ void hlala_destroy(hlala_ctx* c)
     if(!c->tail.empty()) (void)flush_tail(c);
     for(hlala_batch* b : c->batches) b->ctx = nullptr;       // a batch that outlives its context frees its own buffers
     for(void* p : c->allocs) if(p) (void)hipFree(p);
+    if(c->pair_over_slabs) (void)hipFree(c->pair_over_slabs);
     if(c->create_scratch) { if(c->create_scratch_pinned) (void)hipHostFree(c->create_scratch); else free(c->create_scratch); }
     for(hlala_ctx::KeptReads& kr : c->kept) { (void)hipFree(kr.store); (void)hipFree(kr.start); (void)hipFree(kr.length); }
     for(auto& kv : c->pool) (void)hipFree(kv.second);
@@ -656,7 +660,7 @@ static int batch_alloc_outputs(hlala_ctx* c, hlala_batch* b)
     AL(ext_firstlast, 4 * nc, true);
     AL(pair_status, np, true); AL(best_chain, nr, true); AL(n_comb, np, true); AL(pair_ll, np, true); AL(pair_mapq, np, true);
     AL(mate_mapq, nr, true); AL(strands_valid, np, true); AL(sel_mapq, nr * (size_t)B.stride, true);
-    AL(pair_deferred, np, true); AL(pair_multi, 4 * np, false); AL(counters, 32, true); AL(work_counter, WC_N, true); AL(retry_list, 16 * nc, false);
+    AL(pair_deferred, np, true); AL(pair_multi, 7 * np, false); AL(counters, 32, true); AL(work_counter, WC_N, true); AL(retry_list, 16 * nc, false);
     { DpItem* it = nullptr; rc = dev_alloc(c, b->allocs, 2 * nc, &it, false); if(rc) return rc; B.dp_items = it; }
     B.dp_nblk = (int)((nc + 255) / 256); if(B.dp_nblk < 1) B.dp_nblk = 1;
     B.dp_jf = c->jf_margin + 1;
@@ -1076,7 +1080,8 @@ static int extend_end(hlala_ctx* c, hlala_batch* b) { HIP_TRY(c, hipEventRecord(
 static int pair_begin(hlala_ctx* c, hlala_batch* b) { HIP_TRY(c, hipMemsetAsync(b->B.work_counter + 2, 0, sizeof(int), c->active)); HIP_TRY(c, hipEventRecord(b->ev[EV_PAIR_BEGIN], c->active)); return HLALA_OK; }
 // One pairing pass on `st`.  mode 0: every pair (a stage call); 1: all but the deferred pairs; 2: those (the side stream's pass, behind stitch_side).  k_pair_chains
 // finishes the pairs with one combination and lists the others, k_pair_multi<., false / true> runs the two lists (kernel_pair.hip); the main- and the side-stream pass
-// have their own work counter (2 / 37), lists, list counters and combination scratch.
+// have their own work counter (2 / 37), lists, list counters and combination scratch.  With the overflow class on (hlala_set_pair_overflow) k_pair_chains lists the
+// pairs that only a capacity keeps from these kernels in a third list of the pass, and k_pair_overflow runs it behind the general class, on the pass's own slabs.
 static int pair_pass(hlala_ctx* c, hlala_batch* b, hipStream_t st, int mode)
 {
     DevBatch& B = b->B;
@@ -1086,12 +1091,20 @@ static int pair_pass(hlala_ctx* c, hlala_batch* b, hipStream_t st, int mode)
     // (the lists' counters are among those the extension stage clears; a pairing stage called again on its own clears them here.  Not on the side stream: a fill
     //  kernel queued there waits 13-36 ms for a wave slot beside the persistent kernels -- profiles/r06_experiments.txt)
     if(mode == 0) HIP_TRY(c, hipMemsetAsync(B.work_counter + multiBase, 0, 4 * sizeof(int), st));
+    if(mode == 0) HIP_TRY(c, hipMemsetAsync(B.work_counter + WC_PAIR_OVER, 0, 8 * sizeof(int), st));          // (both passes': hlala_batch_get_pair_overflow sums them)
+    const int ovBase = WC_PAIR_OVER + 4 * pass;
+    int* ovList = c->pair_over_slabs ? multiList + (size_t)4 * (size_t)B.n_pairs : nullptr;          // (k_pair_chains: at that distance from the pass's lists, as ovBase from multiBase)
     const int g0 = mode == 2 ? (grid < c->pair_grid / 5 ? grid : c->pair_grid / 5) : grid, g1 = grid < c->pair_grid / 5 ? grid : c->pair_grid / 5;      // (the second pass and the general class hold a few thousand pairs at most)
-    const auto chains = B.unpaired ? k_pair_chains<true> : k_pair_chains<false>;
+    const auto chains = ovList ? (B.unpaired ? k_pair_chains<true, true> : k_pair_chains<false, true>) : (B.unpaired ? k_pair_chains<true, false> : k_pair_chains<false, false>);
     const auto multi = B.unpaired ? k_pair_multi<true, false> : k_pair_multi<false, false>, multiBig = B.unpaired ? k_pair_multi<true, true> : k_pair_multi<false, true>;
     hipLaunchKernelGGL(chains, dim3(lean), dim3(64), 0, st, c->dG, c->dT, b->dB, (const uint8_t*)B.pair_deferred, mode, counterIdx, multiList, multiBase);
     hipLaunchKernelGGL(multi, dim3(g0), dim3(64), 0, st, c->G, b->B, c->dG, c->dT, b->dB, (const int*)multiList, multiBase, scratch);
     hipLaunchKernelGGL(multiBig, dim3(g1), dim3(64), 0, st, c->G, b->B, c->dG, c->dT, b->dB, (const int*)multiList, multiBase, scratch);
+    if(ovList) {
+        const auto over = B.unpaired ? k_pair_overflow<true> : k_pair_overflow<false>;
+        hipLaunchKernelGGL(over, dim3(PAIR_OVER_WAVES), dim3(64), 0, st, c->dG, c->dT, b->dB, (const int*)ovList, ovBase,
+                           c->pair_over_slabs + (size_t)pass * PAIR_OVER_WAVES * (size_t)c->pair_over_slab_bytes, c->pair_over_slab_bytes);
+    }
     return check_launch(c, "k_pair_chains / k_pair_multi");
 }
 // second pairing pass, behind the side-stream classes and the second stitch pass: the deferred pairs
@@ -1193,6 +1206,50 @@ int hlala_set_tail_pool(hlala_ctx* c, int k)
     return HLALA_OK;
 }
 int hlala_flush(hlala_ctx* c) { return c ? flush_tail(c) : HLALA_E_ARG; }
+
+// The overflow class of the pairing stage.  The slabs belong to the context; the pairing passes of the main and of the side stream use one half each.
+int hlala_set_pair_overflow(hlala_ctx* c, int64_t scratch_bytes)
+{
+    if(!c) return HLALA_E_ARG;
+    if(scratch_bytes < 0) { c->err = "hlala_set_pair_overflow: scratch_bytes must not be negative"; return HLALA_E_ARG; }
+    DEV_GUARD(c);
+    STEP(flush_tail(c));
+    if(scratch_bytes == c->pair_over_scratch) return HLALA_OK;
+    // nothing queued may still use the slabs that go away
+    HIP_TRY(c, hipStreamSynchronize(c->stream)); HIP_TRY(c, hipStreamSynchronize(c->side));
+    if(c->pair_over_slabs) { (void)hipFree(c->pair_over_slabs); c->pair_over_slabs = nullptr; }
+    c->pair_over_scratch = 0; c->pair_over_slab_bytes = 0;
+    if(scratch_bytes == 0) return HLALA_OK;
+    const long long slab = (scratch_bytes / HLALA_PAIR_OVERFLOW_WAVES) & ~15ll;
+    char* p = nullptr;
+    if(device_malloc_retry(c->device, c, (void**)&p, (size_t)(slab > 0 ? slab : 16) * HLALA_PAIR_OVERFLOW_WAVES) != hipSuccess) { c->err = "hipMalloc(pair overflow slabs) failed"; return HLALA_E_DEVICE; }
+    c->pair_over_slabs = p; c->pair_over_scratch = scratch_bytes; c->pair_over_slab_bytes = slab;
+    return HLALA_OK;
+}
+int hlala_get_pair_overflow(hlala_ctx* c, int64_t* scratch_bytes, int64_t* slab_bytes)
+{
+    if(!c) return HLALA_E_ARG;
+    if(scratch_bytes) *scratch_bytes = c->pair_over_scratch;
+    if(slab_bytes) *slab_bytes = c->pair_over_slab_bytes;
+    return HLALA_OK;
+}
+int64_t hlala_pair_overflow_need(int64_t n1, int64_t n2, int32_t max_columns, int unpaired)
+{
+    if(n1 < 0) n1 = 0; if(n2 < 0) n2 = 0; if(max_columns < 0) max_columns = 0;
+    return pair_overflow_need(n1, n2, max_columns, unpaired != 0);
+}
+int hlala_batch_get_pair_overflow(hlala_ctx* c, hlala_batch* b, int64_t out[3])
+{
+    DEV_GUARD(c);
+    ReaderScope rscope_(c, b); if(rscope_.rc) return rscope_.rc;
+    if(!c || !b || !out) return HLALA_E_ARG;
+    out[0] = out[1] = out[2] = 0;
+    if(!b->outputs_ready || !(b->staged & 4)) return HLALA_OK;
+    int wc[8];
+    HIP_TRY(c, hipMemcpyAsync(wc, b->B.work_counter + WC_PAIR_OVER, sizeof(wc), hipMemcpyDeviceToHost, c->active)); HIP_TRY(c, hipStreamSynchronize(c->active));
+    for(int pass = 0; pass < 2; pass++) { out[0] += wc[4 * pass]; out[1] += wc[4 * pass + 2]; out[2] += wc[4 * pass + 3]; }
+    return HLALA_OK;
+}
 
 int hlala_align_batch(hlala_ctx* c, hlala_batch* b)
 {

@@ -459,6 +459,27 @@ __device__ __forceinline__ int pair_lists(const DB& B, PairListLds& L, const int
     return 0;
 }
 
+// Why pair_lists refused a pair (its rare path looks again: the common one keeps its registers): true when no chain is flagged, no list is empty and the number of
+// combinations fits an int -- a capacity of these kernels alone stands against the pair, and the overflow class (kernel_pair_overflow.hip) can take it.
+template <bool UNPAIRED, class DB>
+__device__ inline bool pair_capacity_only(const DB& B, const int* cLo, const int* cHi, const int lane)
+{
+    constexpr int NM = UNPAIRED ? 1 : 2;
+    long long comb = 1;
+    for(int m = 0; m < NM; m++) {
+        int cnt = 0;
+        for(int b0 = cLo[m]; b0 < cHi[m]; b0 += 64) {
+            const int c = b0 + lane; int st = 1;
+            if(c < cHi[m]) st = B.ext_status[c];
+            if(__ballot(st < 0)) return false;
+            cnt += __popcll(__ballot(st == HLALA_CHAIN_OK));
+        }
+        if(cnt < 1) return false;
+        comb *= cnt;
+    }
+    return comb <= 0x7FFFFFFFll;
+}
+
 // Round 6: the pairing stage is two kinds of pairs.  74 % of a Graph M batch's pairs have ONE combination: one insert-size term, mapQ 1, a constant per-position
 // quality -- 2.6 k cycles, no table.  The others run the posterior and the per-position pass (43 k cycles; LL table, Phred thresholds and the column tables: 6.3 KB of
 // LDS, and, compiled into one kernel with the first kind, 63 spilled registers for everybody).  k_pair_chains now finishes the first kind and LISTS the second
@@ -467,7 +488,10 @@ __device__ __forceinline__ int pair_lists(const DB& B, PairListLds& L, const int
 // UNPAIRED: one read per unit (processBAM::alignOneLongRead :3618-3838 selects the first maximum of the chains' log likelihoods;
 // assignMappingQualities_unpaired :3900-4059 is the paired computation with a single, neutral second mate).
 // multiBase: first of the four work counters of this pass's lists (count / fetched of class 0, count / fetched of class 1); multiList: [2][n_pairs] pair numbers.
-template <bool UNPAIRED>
+// OVER: the instances pair_pass launches while the overflow class is on -- a pair that only a capacity keeps from these kernels is listed at multiList[4 n_pairs ...], counted in
+// work_counter[multiBase + WC_PAIR_OVER - WC_PAIR_MULTI], and nothing else is written for it.  (A template argument, not a kernel argument: one more live scalar in
+// this kernel costs the instances of the default path two VGPRs and two spilled ones -- profiles/pair_overflow_resource_usage.txt; with OVER = false they are the code they were.)
+template <bool UNPAIRED, bool OVER = false>
 __global__ __launch_bounds__(64, PAIR_LEAN_WAVES) void k_pair_chains(const DevGraph* __restrict__ Gp, const DevTables* __restrict__ Tp, const DevBatch* __restrict__ Bp,
                                                    const uint8_t* __restrict__ deferPairs, const int deferMode, const int counterIdx,      // deferMode 1: skip deferred pairs, 2: only those
                                                    int* __restrict__ multiList, const int multiBase)
@@ -516,7 +540,9 @@ __global__ __launch_bounds__(64, PAIR_LEAN_WAVES) void k_pair_chains(const DevGr
         for(int m = 0; m < NM; m++) { cLo[m] = __builtin_amdgcn_readlane(hC[m], hq); cHi[m] = __builtin_amdgcn_readlane(hC[m + 1], hq); }
         int n1 = 0, n2 = 0, mxc = 0; PairChain cL[2];
         const int bad = pair_lists<UNPAIRED>(B, L, cLo, cHi, lane, n1, n2, mxc, cL);
-        if(bad) {
+        if(OVER && bad && pair_capacity_only<UNPAIRED>(B, cLo, cHi, lane)) {
+            if(lane == 0) { const int q = atomicAdd(&B.work_counter[multiBase + (WC_PAIR_OVER - WC_PAIR_MULTI)], 1); multiList[(size_t)4 * (size_t)B.n_pairs + q] = p; }
+        } else if(bad) {
             if(lane == 0) { B.pair_status[p] = -1; if(UNPAIRED) B.best_chain[p] = -1; else { B.best_chain[2 * p] = -1; B.best_chain[2 * p + 1] = -1; } B.n_comb[p] = 0; }
         } else if(n1 * n2 > 1) {
             // posterior over several combinations + per-position pass: k_pair_multi, from this pass's list of the pair's class

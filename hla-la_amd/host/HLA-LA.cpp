@@ -10,7 +10,7 @@
 // terminate), this program prints the message to stderr and exits with a non-zero status -- HLA-LA.pl treats any non-zero status as
 // failure (:567-570).  Extra, optional arguments of this program: --devices <gpu,gpu,...> (or --device <gpu>): the batches of the sample are
 // dealt round-robin to one context per listed GPU (a GPU may be listed twice: two contexts on it), results do not depend on the list;
-// --decodeSlots <samples that decode at one time, default CPUs / 16>, --tailPool <k: GPU batches per launch of the widest DP classes>, --decodeThreads <host threads of the BAM decoder, default all>, --gpuInflate 0|1 <BGZF blocks inflated on the first listed GPU, default 0>, --gpuParse 0|1 <the BAM records found, filtered and parsed there as well, default 0; 1 implies --gpuInflate 1>, --batchPairs <units per GPU batch>, --rngSeed <base of the end-cell draws>,
+// --decodeSlots <samples that decode at one time, default CPUs / 16>, --tailPool <k: GPU batches per launch of the widest DP classes>, --pairOverflow <MiB of device scratch for pairs beyond the pairing capacities, default 0: such pairs are refused>, --decodeThreads <host threads of the BAM decoder, default all>, --gpuInflate 0|1 <BGZF blocks inflated on the first listed GPU, default 0>, --gpuParse 0|1 <the BAM records found, filtered and parsed there as well, default 0; 1 implies --gpuInflate 1>, --batchPairs <units per GPU batch>, --rngSeed <base of the end-cell draws>,
 // --loci A,B,... (default: the reference's 17 loci, hla/HLATyper.cpp:42).  Several samples in one call (BASELINE config 4): comma-separated lists of
 // equal length in --sampleID, --outputDirectory, --FASTQ1, --FASTQ2 (--FASTQU); sample i runs on device i % #devices, all samples side by side.
 // Not rebuilt: the --BAM entry (the Perl driver never uses it: it extracts reads itself and passes FASTQ files), read simulation /
@@ -223,6 +223,9 @@ int action_HLA_one(const std::map<std::string, std::string>& arguments, const st
     // --tailPool k: the broad / large / in-memory DP classes of k consecutive GPU batches of the sample run in one launch per class (include/hlala_gpu.h: hlala_set_tail_pool);
     // k + 1 batches are in flight per device.  Default HLALA_HOST_TAIL_POOL_DEFAULT; 1 = every batch runs its own tail (rounds 2-5)
     const int tailPool = arguments.count("tailPool") ? std::atoi(arguments.at("tailPool").c_str()) : HLALA_HOST_TAIL_POOL_DEFAULT;
+    // --pairOverflow <MiB>: device scratch, per context, of the pairing stage's overflow class (include/hlala_gpu.h: hlala_set_pair_overflow); 0 (default): off
+    const int64_t pairOverflow = arguments.count("pairOverflow") ? (int64_t)std::atoll(arguments.at("pairOverflow").c_str()) << 20 : 0;
+    if(pairOverflow < 0) throw std::runtime_error("--pairOverflow must not be negative");
     const auto tStart = std::chrono::steady_clock::now();
     const int32_t batchPairs = arguments.count("batchPairs") ? (int32_t)std::atol(arguments.at("batchPairs").c_str()) : (longReads.length() ? 65536 : 1048576);
     const uint32_t rngSeed = arguments.count("rngSeed") ? (uint32_t)std::strtoul(arguments.at("rngSeed").c_str(), nullptr, 10) : 0u;
@@ -247,7 +250,7 @@ int action_HLA_one(const std::map<std::string, std::string>& arguments, const st
     const auto tOpen = std::chrono::steady_clock::now();
     const bool borrowed = turn && shared && !shared->ctx.empty();          // several samples: the call's contexts, taken when this sample's turn at the device comes
     BAMprocessor.openBAM(BAM_remapped, longReads.length() != 0, batchPairs, borrowed);
-    if(!borrowed) BAMprocessor.set_tail_pool(tailPool);
+    if(!borrowed) { BAMprocessor.set_tail_pool(tailPool); BAMprocessor.set_pair_overflow(pairOverflow); }
     turnGuard.end_decode();
     const double openSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - tOpen).count();
     std::cout << timestamp() << "Seed extraction: " << BAMprocessor.n_units << " complete units, BAM decoded in " << BAMprocessor.decode_seconds << " s on " << BAMprocessor.decode_threads
@@ -274,11 +277,12 @@ int action_HLA_one(const std::map<std::string, std::string>& arguments, const st
     std::cout << timestamp() << "Alignment of " << BAMprocessor.n_units << (longReads.length() ? " reads" : " read pairs") << " in " << BAMprocessor.n_batches() << " GPU batch(es) on " << BAMprocessor.n_devices() << " device context(s)\n" << std::flush;
     double alignSeconds = 0; int64_t chainErrors = 0;
     turnGuard.begin_device();          // (the device may still be aligning the sample before this one; this sample's decode ran beside it)
-    if(borrowed) { BAMprocessor.use_contexts(std::vector<hlala_ctx*>(1, const_cast<SharedGraph*>(shared)->context(turn->slot))); BAMprocessor.set_tail_pool(tailPool);
+    if(borrowed) { BAMprocessor.use_contexts(std::vector<hlala_ctx*>(1, const_cast<SharedGraph*>(shared)->context(turn->slot))); BAMprocessor.set_tail_pool(tailPool); BAMprocessor.set_pair_overflow(pairOverflow);
                    if(!longReads.length()) std::cout << "Insert size: mean " << BAMprocessor.IS_mean << ", sd " << BAMprocessor.IS_sd << "\n" << std::flush; }
     const auto tInfer = std::chrono::steady_clock::now();
     std::vector<hla::HLATyper::bestGuess> calls = HLAtyper.HLATypeInference(BAMprocessor, outputDirectory_for_HLA, loci, &alignSeconds, &chainErrors);
     const double inferSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - tInfer).count();
+    if(pairOverflow > 0) std::cout << "Pairs beyond the pairing capacities: " << HLAtyper.pair_overflow_counts[1] << " scored in the overflow class, " << HLAtyper.pair_overflow_counts[2] << " refused\n" << std::flush;
     const size_t pairs = longReads.length() ? 0 : (size_t)BAMprocessor.n_units, unpaired = longReads.length() ? (size_t)BAMprocessor.n_units : 0;
     std::cout << timestamp() << "Processed " << pairs << " protoSeeds (read pairs) / " << unpaired << " protoSeeds (unpaired long reads)\n" << std::flush;
     std::cout << "Speed: " << (alignSeconds > 0 ? (double)(pairs + unpaired) / alignSeconds : 0.0) << " protoSeeds (read pairs) per s" << "\n" << std::flush;      // :1894-1898

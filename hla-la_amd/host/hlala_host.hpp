@@ -451,6 +451,9 @@ public:
     // hlala_set_tail_pool on every context (1: off).  Memory: k + 1 batches' outputs live per device.
     void set_tail_pool(int k) { tail_pool_ = k < 1 ? 1 : k; for(hlala_ctx* c : ctxs_) if(c && hlala_set_tail_pool(c, tail_pool_) != HLALA_OK) throw std::runtime_error(std::string("hlala_set_tail_pool: ") + hlala_last_error(c)); }
     int tail_pool() const { return tail_pool_; }
+    // hlala_set_pair_overflow on every context (0: off): device scratch, per context, for the pairs beyond the pairing capacities
+    void set_pair_overflow(int64_t bytes) { pair_overflow_ = bytes < 0 ? 0 : bytes; for(hlala_ctx* c : ctxs_) if(c && hlala_set_pair_overflow(c, pair_overflow_) != HLALA_OK) throw std::runtime_error(std::string("hlala_set_pair_overflow: ") + hlala_last_error(c)); }
+    int64_t pair_overflow() const { return pair_overflow_; }
     bool uses_rccl() const { return comm_ && hlala_comm_uses_rccl(comm_); }          // the contexts sit on different GPUs and exchange over RCCL
     hlala_batch* batch() const { return live_.empty() ? nullptr : live_[0]; }
     const char* readID(int64_t unit) const { return hlala_seed_batch_name(seeds_, unit); }
@@ -476,7 +479,7 @@ private:
     std::shared_ptr<GraphDirectory> gdir_;
     std::string graphDir_; bool extended_; int max_columns_; uint32_t rng_seed_; std::vector<int> devices_; int threads_; bool gpu_inflate_ = false, gpu_parse_ = false;
     hlala_graph_file* graph_ = nullptr; hlala_contigs_file* contigs_ = nullptr; const std::vector<hlala_bam_interval>& intervals_;      // owned by gdir_
-    hlala_seed_batch* seeds_ = nullptr; std::vector<hlala_ctx*> ctxs_; hlala_comm* comm_ = nullptr; int tail_pool_ = 1; bool owns_ctx_ = true; std::string BAM_;
+    hlala_seed_batch* seeds_ = nullptr; std::vector<hlala_ctx*> ctxs_; hlala_comm* comm_ = nullptr; int tail_pool_ = 1; int64_t pair_overflow_ = 0; bool owns_ctx_ = true; std::string BAM_;
     int32_t batchPairs_ = 1; std::vector<hlala_batch*> live_; std::vector<char> aligned_;       // aligned_[bi]: hlala_align_batch has been queued for live_[bi]
 };
 }  // namespace mapper
@@ -534,6 +537,7 @@ public:
     // through the GPU batch by batch (processBAM::acquire); what the typing needs of a batch -- includeInHLA, the per-unit alignment
     // statistics and the exon positions of every locus -- is taken while the batch is resident and appended on the host.
     // align_seconds (optional) receives the time spent in alignment proper (the reference's "Speed:" line, processBAM.cpp:1894-1898).
+    int64_t pair_overflow_counts[3] = {0, 0, 0};      // of the last HLATypeInference: pairs listed for the overflow class of the pairing stage, scored there, refused for want of slab
     std::vector<bestGuess> HLATypeInference(mapper::processBAM& pB, const std::string& outputDirectory, const std::vector<std::string>& loci_for_HLAtyping,
                                             double* align_seconds = nullptr, int64_t* chain_errors = nullptr)
     {
@@ -570,7 +574,7 @@ public:
         struct LocusPart { std::vector<int32_t> read_pair, read_distance, cols, pos_off, pos_exon, pos_level, novel, geno_off; std::vector<double> wok, fok, rmapq; std::vector<uint8_t> mate, pmapq, geno, qual, rrev; int32_t ok = 0, broken = 0; size_t nR = 0, nP = 0, nC = 0; };
         const int32_t nB = pB.n_batches();
         std::vector<std::vector<LocusPart>> parts((size_t)nB, std::vector<LocusPart>(acc.size()));
-        std::vector<double> devAlign((size_t)nDev, 0.0); std::vector<int64_t> devErrors((size_t)nDev, 0); std::vector<std::string> devErr((size_t)nDev);
+        std::vector<double> devAlign((size_t)nDev, 0.0); std::vector<int64_t> devErrors((size_t)nDev, 0), devOver(3 * (size_t)nDev, 0); std::vector<std::string> devErr((size_t)nDev);
         for(int d = 0; d < nDev; d++) hlala_kmer_forget_reads(pB.batch_ctx(d));
         const auto tAll = std::chrono::steady_clock::now();
         auto device_walk = [&](int d) {
@@ -590,6 +594,7 @@ public:
                     hlala_batch_stats bs; dchk(hlala_batch_get_stats(cd, b, &bs), "hlala_batch_get_stats");          // (waits for this batch only)
                     devAlign[(size_t)d] += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
                     devErrors[(size_t)d] += bs.n_errors;
+                    if(pB.pair_overflow() > 0) { int64_t ov[3]; dchk(hlala_batch_get_pair_overflow(cd, b, ov), "hlala_batch_get_pair_overflow"); for(int k = 0; k < 3; k++) devOver[3 * (size_t)d + k] += ov[k]; }
                     dchk(hlala_postprocess_pairs(cd, b, include.data() + u0), "hlala_postprocess_pairs");
                     // the reads of the looked-at units stay on the device for the k-mer questions that follow the calls (HLATyper.cpp:999-1027 builds its index of
                     // read k-mers in this walk too): a few per cent of a batch, copied device to device -- no batch is uploaded a second time
@@ -626,6 +631,7 @@ public:
         auto tLap = tAll;
         timing = Timing();
         int64_t errors = 0; for(int64_t e : devErrors) errors += e;
+        for(int k = 0; k < 3; k++) { pair_overflow_counts[k] = 0; for(int d = 0; d < nDev; d++) pair_overflow_counts[k] += devOver[3 * (size_t)d + k]; }
         for(int32_t bi = 0; bi < nB; bi++) {
             const size_t u0 = (size_t)pB.batch_first_unit(bi);
             for(size_t li = 0; li < acc.size(); li++) {

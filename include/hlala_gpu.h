@@ -196,14 +196,20 @@ typedef struct {
  *
  * A pair (or single read) that stage C cannot score is REFUSED: pair_status = -1, best_chain = -1 for both mates, n_combinations = 0; its other
  * entries are not meaningful (n_cols comes back 0).  That is the case when
- *   - a record of the pair is flagged (status < 0 in hlala_chains_out: an HLALA_CHAIN_ERR_*), or a mate has no kept alignment;
- *   - a mate has more than 64 kept alignments (records that pass the strand / duplicate filters; the number of records is not limited);
- *   - the pair has more than 1024 combinations (kept alignments of mate 1 times those of mate 2);
- *   - the pair has several combinations and one of its chains has more than 512 columns (one combination: any length up to max_columns).
- * The reference has none of the three capacities.  hlala_batch_get_stats' n_errors counts flagged CHAINS: a pair refused for a capacity alone adds nothing to
- * it; count the refused pairs from pair_status. */
+ *   (a) a record of the pair is flagged (status < 0 in hlala_chains_out: an HLALA_CHAIN_ERR_*), or a mate has no kept alignment, or the number of
+ *       combinations does not fit 32 bits;
+ *   (b) a mate has more than 64 kept alignments (records that pass the strand / duplicate filters; the number of records is not limited);
+ *   (c) the pair has more than 1024 combinations (kept alignments of mate 1 times those of mate 2);
+ *   (d) the pair has several combinations and one of its chains has more than 512 columns (one combination: any length up to max_columns).
+ * The reference has none of the three capacities (b) - (d).
+ * Overflow class OFF (the default): all four cases are refused.
+ * Overflow class ON (hlala_set_pair_overflow): a pair that only (b), (c) or (d) stands against is scored like any other, by a kernel that works out of device
+ * scratch -- the same arithmetic in the same order, so it gets what the reference gives it --, unless it needs more scratch than one wave's share
+ * (hlala_pair_overflow_need > slab_bytes of hlala_get_pair_overflow): it is then refused as above and counted by hlala_batch_get_pair_overflow.  (a) stays refused.
+ * Pairs within the capacities are not touched by the setting.
+ * hlala_batch_get_stats' n_errors counts flagged CHAINS: a pair refused for a capacity alone adds nothing to it; count the refused pairs from pair_status. */
 typedef struct {
-    int32_t* pair_status;   /* [n] 0 ok, -1: refused (a flagged chain, an empty list, or a capacity: see above) */
+    int32_t* pair_status;   /* [n] 0 ok, -1: refused (a flagged chain, an empty list, or a capacity that the overflow class is not on for or has no scratch for: see above) */
     int32_t* best_chain;    /* [2n] absolute chain index selected for each mate              */
     int32_t* n_combinations;/* [n] read1_extendedChains.size()*read2_extendedChains.size()   */
     double*  pair_ll;       /* [n] combinations_max.first (processBAM.cpp:3538)              */
@@ -258,7 +264,9 @@ int  hlala_project_chains(hlala_ctx* ctx, hlala_batch* b);
 int  hlala_extend_chains(hlala_ctx* ctx, hlala_batch* b);
 /* Stage C -- the pairing loop of processBAM::alignOneReadPair (mapper/processBAM.cpp:3408-3546)
  * and processBAM::assignMappingQualities (:4062-4312).  Capacities: 64 kept alignments per mate, 1024 combinations per pair, 512 columns per chain
- * of a pair with several combinations; a pair beyond one of them is refused (hlala_pairs_out), the call itself succeeds.       */
+ * of a pair with several combinations.  Overflow class off (the default): a pair beyond one of them is refused (hlala_pairs_out), the call itself succeeds.
+ * Overflow class on (hlala_set_pair_overflow): such a pair is scored behind the others on the same stream, in every schedule (stage call, fused alignment,
+ * tail pool); it is refused only where its need exceeds the per-wave slab.                                                     */
 int  hlala_pair_chains(hlala_ctx* ctx, hlala_batch* b);
 /* A + B + C: processBAM::alignOneReadPair (mapper/processBAM.cpp:3129-3616) over the batch.
  * Asynchronous like the stage calls.  On a paired batch the few percent of DP calls with wide frontiers (allele-rich gene levels) and the
@@ -276,6 +284,24 @@ int  hlala_align_batch(hlala_ctx* ctx, hlala_batch* b);
  * counterpart: extensionAligner.cpp:335-1556 runs one DP call at a time on one thread.                                          */
 int  hlala_set_tail_pool(hlala_ctx* ctx, int k);
 int  hlala_flush(hlala_ctx* ctx);
+/* The overflow class of stage C: pairs beyond the three pairing capacities (hlala_pairs_out), scored out of device scratch instead of being refused.  Off by default.
+ * hlala_set_pair_overflow: scratch_bytes = 0 turns the class off and frees its scratch (behaviour is then exactly that of a context that never turned it on);
+ * a positive value turns it on with that much device scratch, split evenly over HLALA_PAIR_OVERFLOW_WAVES wavefronts -- half of them serve the pairing pass of
+ * the main stream, half that of the side stream --: slab_bytes = scratch_bytes / HLALA_PAIR_OVERFLOW_WAVES, rounded down to a multiple of 16.  Pending work of
+ * the context is flushed and finished first (as hlala_set_tail_pool does).  Negative: HLALA_E_ARG.  A failed allocation: HLALA_E_DEVICE, and the class is off.
+ * hlala_get_pair_overflow: the setting and the per-wave slab (either pointer may be NULL).
+ * hlala_pair_overflow_need: the slab bytes ONE pair needs -- a pure function, no context.  With n1, n2 the kept alignments of the mates (unpaired != 0: n2 is
+ * taken as 1 and there is no second list), S = max_columns, nc = n1 + n2 (unpaired: n1) and W = ceil(max(n1, n2) / 64):
+ *     need = 40 * nc  +  8 * n1 * n2  +  8 * S * W  +  11 * S
+ * (chain facts; combination table; the shared-by-chain-k masks of a selected chain's columns; ordinals and the compared chain's tables).  Negative arguments count
+ * as 0.  Every wave's slab has the same size: whether a pair fits depends on the pair and the setting alone.
+ * hlala_batch_get_pair_overflow: out[0] pairs listed for the class by the batch's last pairing, out[1] pairs scored there, out[2] pairs refused for want of slab;
+ * each summed over both passes; ordered behind the batch's work like the other getters.  All zero with the class off. */
+#define HLALA_PAIR_OVERFLOW_WAVES 64
+int  hlala_set_pair_overflow(hlala_ctx* ctx, int64_t scratch_bytes);
+int  hlala_get_pair_overflow(hlala_ctx* ctx, int64_t* scratch_bytes, int64_t* slab_bytes);
+int64_t hlala_pair_overflow_need(int64_t n1, int64_t n2, int32_t max_columns, int unpaired);
+int  hlala_batch_get_pair_overflow(hlala_ctx* ctx, hlala_batch* b, int64_t out[3]);
 
 /* Download results (synchronises the stream).  `stage` 0 = seed chains after stage A,
  * 1 = extended chains after stage B.                                                         */
