@@ -318,6 +318,13 @@ class SeedBatch:
         self.lib.hlala_seed_batch_transfer_bytes(self.h, b)
         return tuple(int(x) for x in b)
 
+    def crc_counts(self):
+        """(blocks whose CRC-32 was verified on the GPU, on the host, blocks the GPU reported as mismatching and the host checked again); all zero without SEEDS_VERIFY_CRC"""
+        cnt = (C.c_int64 * 3)()
+        self.lib.hlala_seed_batch_crc_counts.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        self.lib.hlala_seed_batch_crc_counts(self.h, cnt)
+        return tuple(int(x) for x in cnt)
+
     def inflate_counts(self):
         """(blocks inflated on the GPU, blocks the GPU rejected and the host engine ran again, blocks inflated on the host only)"""
         cnt = (C.c_int64 * 3)()
@@ -342,6 +349,7 @@ class SeedBatch:
 
 SEEDS_PACKED = 1          # HLALA_SEEDS_PACKED
 SEEDS_GPU_PARSE = 2       # HLALA_SEEDS_GPU_PARSE (Inflater.bam_open_seeds only): the record pass of every round on the GPU as well
+SEEDS_VERIFY_CRC = 4      # HLALA_SEEDS_VERIFY_CRC (bam_open_seeds and Inflater.bam_open_seeds): the CRC-32 of every BGZF block is compared with that of its inflated bytes
 
 
 def bam_open_seeds(lib, path, intervals, long_read_mode=False, threads=0, flags=0) -> SeedBatch:
@@ -396,7 +404,7 @@ def bam_scan_in(n_ref, ref_intervals, intervals, long_read_mode=False, hash_mask
 
 
 INFLATE_MIN_CHUNK, INFLATE_DEFAULT_CHUNK = 1 << 17, 32 << 20          # HLALA_INFLATE_MIN_CHUNK, HLALA_INFLATE_DEFAULT_CHUNK
-INFLATE_STATUS = ("ok", "reserved block type", "stored LEN != ~NLEN", "bad code lengths", "invalid symbol", "distance too far", "input exhausted", "output size")
+INFLATE_STATUS = ("ok", "reserved block type", "stored LEN != ~NLEN", "bad code lengths", "invalid symbol", "distance too far", "input exhausted", "output size", "crc mismatch")
 
 
 class Inflater:
@@ -409,6 +417,8 @@ class Inflater:
         lib.hlala_inflater_destroy.argtypes = [C.c_void_p]; lib.hlala_inflater_destroy.restype = None
         lib.hlala_inflater_last_error.argtypes = [C.c_void_p]; lib.hlala_inflater_last_error.restype = C.c_char_p
         lib.hlala_bgzf_inflate.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(BgzfBlock), C.c_int64, C.c_void_p, C.c_size_t, c_i32p, C.POINTER(InflateStats)]
+        lib.hlala_bgzf_inflate_crc.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(BgzfBlock), C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, c_i32p, C.POINTER(InflateStats), C.POINTER(C.c_double)]
+        self.ms_crc = 0.0          # summed device time of k_bgzf_crc32 in the last inflate() that asked for CRCs
         lib.hlala_bam_extract_seeds_gpu.argtypes = [C.c_void_p, C.c_char_p, C.c_int32, C.POINTER(BamInterval), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
         h = C.c_void_p()
         rc = lib.hlala_inflater_create(int(device), int(chunk_bytes), C.byref(h))
@@ -416,14 +426,26 @@ class Inflater:
             raise HlalaError(f"hlala_inflater_create failed ({rc}): {lib.hlala_inflater_last_error(None).decode(errors='replace')}")
         self.h = h
 
-    def inflate(self, comp, blocks, out):
-        """comp, out: contiguous uint8 arrays; blocks = [(coff, clen, isize, uoff)].  Writes the accepted blocks into `out`; returns (int32 status per block, InflateStats)."""
+    def inflate(self, comp, blocks, out, crc=None, want_crc=False):
+        """comp, out: contiguous uint8 arrays; blocks = [(coff, clen, isize, uoff)].  Writes the accepted blocks into `out`; returns (int32 status per block, InflateStats).
+        crc: the expected CRC-32 per block (hlala_bgzf_inflate_crc: a block whose bytes have another one comes back with status 8, "crc mismatch", and its bytes);
+        want_crc: the computed CRC-32 per block (uint32) is returned as a third value.  self.ms_crc: the device time of the CRC kernel in that call."""
         comp = np.ascontiguousarray(comp, np.uint8)
         assert out.dtype == np.uint8 and out.flags["C_CONTIGUOUS"] and out.flags["WRITEABLE"]
         arr = (BgzfBlock * max(1, len(blocks)))()
         for i, b in enumerate(blocks):
             arr[i] = BgzfBlock(*[int(x) for x in b])
         status = np.full(max(1, len(blocks)), -1, np.int32); st = InflateStats()
+        if crc is not None or want_crc:
+            expect = None if crc is None else np.ascontiguousarray(crc, np.uint32)
+            assert expect is None or expect.size == len(blocks)
+            got = np.zeros(max(1, len(blocks)), np.uint32); ms = C.c_double(0)
+            rc = self.lib.hlala_bgzf_inflate_crc(self.h, comp.ctypes.data, comp.size, arr, len(blocks), out.ctypes.data, out.size, None if expect is None or not len(blocks) else expect.ctypes.data,
+                                                 got.ctypes.data if want_crc else None, status.ctypes.data_as(c_i32p), C.byref(st), C.byref(ms))
+            if rc != 0:
+                raise HlalaError(f"hlala_bgzf_inflate_crc failed ({rc}): {self.lib.hlala_inflater_last_error(self.h).decode(errors='replace')}")
+            self.ms_crc = float(ms.value)
+            return (status[:len(blocks)], st, got[:len(blocks)]) if want_crc else (status[:len(blocks)], st)
         rc = self.lib.hlala_bgzf_inflate(self.h, comp.ctypes.data, comp.size, arr, len(blocks), out.ctypes.data, out.size, status.ctypes.data_as(c_i32p), C.byref(st))
         if rc != 0:
             raise HlalaError(f"hlala_bgzf_inflate failed ({rc}): {self.lib.hlala_inflater_last_error(self.h).decode(errors='replace')}")
@@ -839,6 +861,7 @@ EXPORTED_SYMBOLS = [
     "hlala_typer_open", "hlala_typer_close", "hlala_typer_last_error", "hlala_typer_n_levels", "hlala_typer_level_name", "hlala_typer_level_of", "hlala_typer_n_genes",
     "hlala_typer_gene", "hlala_typer_load_g_groups", "hlala_typer_g_translate", "hlala_typer_locus", "hlala_locus_free", "hlala_locus_get", "hlala_locus_cluster_id", "hlala_locus_type_cluster",
     "hlala_inflater_create", "hlala_inflater_destroy", "hlala_inflater_last_error", "hlala_bgzf_inflate", "hlala_bam_extract_seeds_gpu", "hlala_seed_batch_inflate_counts",
+    "hlala_bgzf_inflate_crc", "hlala_seed_batch_crc_counts",
     "hlala_bam_scan", "hlala_bam_scan_status_text", "hlala_seed_batch_parse_counts", "hlala_seed_batch_transfer_bytes",
     "hlala_locus_cluster_kmers", "hlala_type_locus", "hlala_kmer_presence", "hlala_kmer_keep_reads", "hlala_kmer_presence_kept", "hlala_kmer_forget_reads", "hlala_unit_alignment_stats", "hlala_typer_write_summary", "hlala_typer_begin_output", "hlala_locus_write_files", "hlala_locus_write_pairs_file", "hlala_typer_end_output",
 ]

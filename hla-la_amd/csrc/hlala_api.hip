@@ -30,6 +30,7 @@
 #include "kernel_kmer.hip"
 #include "kernel_dp_band.hip"
 #include "kernel_inflate.hip"
+#include "kernel_crc32.hip"
 #include "kernel_bamscan.hip"
 
 namespace hlala {
@@ -2341,6 +2342,8 @@ struct InflateSlot {
     uint8_t* hComp = nullptr; uint8_t* dComp = nullptr; uint8_t* hOut = nullptr; uint8_t* dOut = nullptr;
     hlala_bgzf_block* hDesc = nullptr; hlala_bgzf_block* dDesc = nullptr; int* hStatus = nullptr; int* dStatus = nullptr;
     int64_t first = 0, count = 0; size_t outBytes = 0; bool busy = false;
+    // hlala_bgzf_inflate_crc: expected and computed CRCs of the chunk's blocks and the event behind k_bgzf_crc32; allocated by the first call that asks for CRCs
+    uint32_t* hCrcIn = nullptr; uint32_t* dCrcIn = nullptr; uint32_t* hCrcOut = nullptr; uint32_t* dCrcOut = nullptr; hipEvent_t evCrc = nullptr; bool crc = false;
 };
 // device buffers of hlala_bam_scan: grown on demand, kept by the handle
 struct ScanBuf { void* p = nullptr; size_t cap = 0; };
@@ -2365,6 +2368,7 @@ extern "C" void hlala_inflater_destroy(hlala_inflater* f)
         for(hipEvent_t e : s.ev) if(e) (void)hipEventDestroy(e);
         if(s.hComp) (void)hipHostFree(s.hComp); if(s.hOut) (void)hipHostFree(s.hOut); if(s.hDesc) (void)hipHostFree(s.hDesc); if(s.hStatus) (void)hipHostFree(s.hStatus);
         if(s.dComp) (void)hipFree(s.dComp); if(s.dOut) (void)hipFree(s.dOut); if(s.dDesc) (void)hipFree(s.dDesc); if(s.dStatus) (void)hipFree(s.dStatus);
+        if(s.evCrc) (void)hipEventDestroy(s.evCrc); if(s.hCrcIn) (void)hipHostFree(s.hCrcIn); if(s.hCrcOut) (void)hipHostFree(s.hCrcOut); if(s.dCrcIn) (void)hipFree(s.dCrcIn); if(s.dCrcOut) (void)hipFree(s.dCrcOut);
     }
     for(ScanBuf& b : f->scan) if(b.p) (void)hipFree(b.p);
     for(hipEvent_t e : f->scanEv) if(e) (void)hipEventDestroy(e);
@@ -2404,8 +2408,11 @@ extern "C" int hlala_inflater_create(int32_t device, size_t chunk_bytes, hlala_i
 // `landed` (may be null) is told about every chunk, in ascending block order, once its accepted blocks stand in `out` and its statuses in `status`; a non-zero
 // answer ends the call (HLALA_E_STATE) after the chunks in flight have been drained.
 static int inflate_run(hlala_inflater* f, const uint8_t* comp, size_t comp_bytes, const hlala_bgzf_block* blocks, int64_t n, uint8_t* out, size_t out_bytes, int32_t* status,
-                       hlala_inflate_stats* stats, int (*landed)(void*, int64_t, int64_t), void* user, uint8_t* dOutBase = nullptr)
+                       hlala_inflate_stats* stats, int (*landed)(void*, int64_t, int64_t), void* user, uint8_t* dOutBase = nullptr,
+                       const uint32_t* crcExpect = nullptr, uint32_t* crcOut = nullptr, double* msCrc = nullptr)
 {
+    // crcExpect / crcOut (either non-null: k_bgzf_crc32 runs behind the inflate kernel of every chunk, on the chunk's stream, with the chunk's descriptors): a block
+    // whose CRC-32 is not crcExpect[i] comes back with HLALA_INFLATE_CRC_MISMATCH and its bytes; with both null nothing below differs from a call without them.
     // dOutBase (device memory of out_bytes bytes; `out` is not used then): the blocks' output stays on the device -- block i goes to dOutBase + blocks[i].uoff, straight
     // from the kernel; only the statuses come back.  The output ranges must follow one another without gaps (a chunk's kernel writes one contiguous range).
     if(!f) return HLALA_E_ARG;
@@ -2431,6 +2438,17 @@ static int inflate_run(hlala_inflater* f, const uint8_t* comp, size_t comp_bytes
     DevGuard g(f->device);
     hlala_inflate_stats st{}; st.n_blocks = n;
     int rc = HLALA_OK;
+    const bool wantCrc = crcExpect || crcOut;
+    double crcMs = 0;
+    if(msCrc) *msCrc = 0;
+    if(wantCrc) for(InflateSlot& s : f->slot) {
+        if(s.evCrc) continue;
+        const size_t nd = (size_t)f->maxBlocks * sizeof(uint32_t);
+        if((!s.hCrcIn && hipHostMalloc((void**)&s.hCrcIn, nd, hipHostMallocDefault) != hipSuccess) || (!s.hCrcOut && hipHostMalloc((void**)&s.hCrcOut, nd, hipHostMallocDefault) != hipSuccess) ||
+           (!s.dCrcIn && hipMalloc((void**)&s.dCrcIn, nd) != hipSuccess) || (!s.dCrcOut && hipMalloc((void**)&s.dCrcOut, nd) != hipSuccess) || hipEventCreate(&s.evCrc) != hipSuccess) {
+            (void)hipGetLastError(); f->err = "hlala_bgzf_inflate_crc: no memory for the CRC arrays"; return HLALA_E_DEVICE;      // (what was allocated is kept and freed with the handle)
+        }
+    }
     auto drain = [&](InflateSlot& s, bool deliver) {
         if(!s.busy) return;
         s.busy = false;
@@ -2439,13 +2457,16 @@ static int inflate_run(hlala_inflater* f, const uint8_t* comp, size_t comp_bytes
         float ms = 0;
         if(hipEventElapsedTime(&ms, s.ev[0], s.ev[1]) == hipSuccess) st.ms_h2d += ms;
         if(hipEventElapsedTime(&ms, s.ev[1], s.ev[2]) == hipSuccess) st.ms_kernel += ms;
-        if(hipEventElapsedTime(&ms, s.ev[2], s.ev[3]) == hipSuccess) st.ms_d2h += ms;
+        if(hipEventElapsedTime(&ms, s.crc ? s.evCrc : s.ev[2], s.ev[3]) == hipSuccess) st.ms_d2h += ms;
+        if(s.crc && hipEventElapsedTime(&ms, s.ev[2], s.evCrc) == hipSuccess) crcMs += ms;
         if(!deliver || rc != HLALA_OK) return;
         for(int64_t k = 0; k < s.count; k++) {
             const hlala_bgzf_block& b = blocks[s.first + k];
             const int v = s.hStatus[k];
             status[s.first + k] = v;
-            if(v == HLALA_INFLATE_OK) { st.n_ok++; if(b.isize && !dOutBase) memcpy(out + b.uoff, s.hOut + s.hDesc[k].uoff, b.isize); } else st.n_rejected++;
+            if(v == HLALA_INFLATE_OK) st.n_ok++; else st.n_rejected++;
+            if((v == HLALA_INFLATE_OK || v == HLALA_INFLATE_CRC_MISMATCH) && b.isize && !dOutBase) memcpy(out + b.uoff, s.hOut + s.hDesc[k].uoff, b.isize);
+            if(s.crc && crcOut) crcOut[s.first + k] = s.hCrcOut[k];
         }
         if(landed && landed(user, s.first, s.count) != 0) { f->err = "hlala_bgzf_inflate: ended by the caller"; rc = HLALA_E_STATE; }
     };
@@ -2461,16 +2482,25 @@ static int inflate_run(hlala_inflater* f, const uint8_t* comp, size_t comp_bytes
             if(ca + b.clen > f->chunk || ob + b.isize > f->outCap) break;
             if(b.clen) memcpy(s.hComp + ca, comp + b.coff, b.clen);
             hlala_bgzf_block& d = s.hDesc[cnt]; d.coff = ca; d.clen = b.clen; d.isize = b.isize; d.uoff = ob;
+            if(crcExpect) s.hCrcIn[cnt] = crcExpect[i + cnt];
             cb = ca + b.clen; ob += b.isize; cnt++;
         }
         // (cnt >= 1: a single block fits an empty chunk -- clen <= chunk was checked, isize <= 65536 < outCap)
-        s.first = i; s.count = cnt; s.outBytes = ob; i += cnt;
+        s.first = i; s.count = cnt; s.outBytes = ob; s.crc = wantCrc; i += cnt;
         hipError_t e = hipEventRecord(s.ev[0], s.stream);
         if(e == hipSuccess && cb) e = hipMemcpyAsync(s.dComp, s.hComp, cb, hipMemcpyHostToDevice, s.stream);
         if(e == hipSuccess) e = hipMemcpyAsync(s.dDesc, s.hDesc, (size_t)cnt * sizeof(hlala_bgzf_block), hipMemcpyHostToDevice, s.stream);
+        if(e == hipSuccess && crcExpect) e = hipMemcpyAsync(s.dCrcIn, s.hCrcIn, (size_t)cnt * sizeof(uint32_t), hipMemcpyHostToDevice, s.stream);
         if(e == hipSuccess) e = hipEventRecord(s.ev[1], s.stream);
         if(e == hipSuccess) { hipLaunchKernelGGL(k_bgzf_inflate, dim3((unsigned)cnt), dim3(64), 0, s.stream, (const uint8_t*)s.dComp, (const hlala_bgzf_block*)s.dDesc, (int)cnt, dOutBase ? dOutBase + blocks[s.first].uoff : s.dOut, s.dStatus); e = hipGetLastError(); }
         if(e == hipSuccess) e = hipEventRecord(s.ev[2], s.stream);
+        if(e == hipSuccess && wantCrc) {
+            hipLaunchKernelGGL(k_bgzf_crc32, dim3((unsigned)cnt), dim3(64), 0, s.stream, (const uint8_t*)(dOutBase ? dOutBase + blocks[s.first].uoff : s.dOut), (const hlala_bgzf_block*)s.dDesc, (int)cnt, s.dStatus,
+                               crcExpect ? (const uint32_t*)s.dCrcIn : (const uint32_t*)nullptr, s.dCrcOut);
+            e = hipGetLastError();
+            if(e == hipSuccess) e = hipEventRecord(s.evCrc, s.stream);
+            if(e == hipSuccess && crcOut) e = hipMemcpyAsync(s.hCrcOut, s.dCrcOut, (size_t)cnt * sizeof(uint32_t), hipMemcpyDeviceToHost, s.stream);
+        }
         if(e == hipSuccess && ob && !dOutBase) e = hipMemcpyAsync(s.hOut, s.dOut, ob, hipMemcpyDeviceToHost, s.stream);
         if(e == hipSuccess) e = hipMemcpyAsync(s.hStatus, s.dStatus, (size_t)cnt * sizeof(int), hipMemcpyDeviceToHost, s.stream);
         if(e == hipSuccess) e = hipEventRecord(s.ev[3], s.stream);
@@ -2481,6 +2511,7 @@ static int inflate_run(hlala_inflater* f, const uint8_t* comp, size_t comp_bytes
     for(int j = 0; j < 3; j++) drain(f->slot[(k + j) % 3], rc == HLALA_OK);
     st.ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tWall).count();
     if(stats) *stats = st;
+    if(msCrc) *msCrc = crcMs;
     return rc;
 }
 extern "C" int hlala_bgzf_inflate(hlala_inflater* f, const uint8_t* comp, size_t comp_bytes, const hlala_bgzf_block* blocks, int64_t n_blocks, uint8_t* out, size_t out_bytes,
@@ -2488,20 +2519,30 @@ extern "C" int hlala_bgzf_inflate(hlala_inflater* f, const uint8_t* comp, size_t
 {
     return inflate_run(f, comp, comp_bytes, blocks, n_blocks, out, out_bytes, status, stats, nullptr, nullptr);
 }
+extern "C" int hlala_bgzf_inflate_crc(hlala_inflater* f, const uint8_t* comp, size_t comp_bytes, const hlala_bgzf_block* blocks, int64_t n_blocks, uint8_t* out, size_t out_bytes,
+                                      const uint32_t* crc_expect, uint32_t* crc_out, int32_t* status, hlala_inflate_stats* stats, double* ms_crc)
+{
+    return inflate_run(f, comp, comp_bytes, blocks, n_blocks, out, out_bytes, status, stats, nullptr, nullptr, nullptr, crc_expect, crc_out, ms_crc);
+}
+static int bam_inflate_crc_hook(void* inflater, const uint8_t* comp, size_t comp_bytes, const hlala_bgzf_block* blocks, int64_t n, uint8_t* out, size_t out_bytes, int32_t* status,
+                                int (*landed)(void*, int64_t, int64_t), void* user, const uint32_t* crc_expect, std::string* err)
+{
+    hlala_inflater* f = (hlala_inflater*)inflater;
+    const int rc = inflate_run(f, comp, comp_bytes, blocks, n, out, out_bytes, status, nullptr, landed, user, nullptr, crc_expect);
+    if(rc != HLALA_OK && err) *err = f->err;
+    return rc;
+}
 static int bam_inflate_hook(void* inflater, const uint8_t* comp, size_t comp_bytes, const hlala_bgzf_block* blocks, int64_t n, uint8_t* out, size_t out_bytes, int32_t* status,
                             int (*landed)(void*, int64_t, int64_t), void* user, std::string* err)
 {
-    hlala_inflater* f = (hlala_inflater*)inflater;
-    const int rc = inflate_run(f, comp, comp_bytes, blocks, n, out, out_bytes, status, nullptr, landed, user);
-    if(rc != HLALA_OK && err) *err = f->err;
-    return rc;
+    return bam_inflate_crc_hook(inflater, comp, comp_bytes, blocks, n, out, out_bytes, status, landed, user, nullptr, err);
 }
 static int bam_scan_hook(void* inflater, hlala_host::bam_scan_round* R, std::string* err);      // (behind hlala_bam_scan, below)
 extern "C" int hlala_bam_extract_seeds_gpu(hlala_inflater* f, const char* path, int32_t n_intervals, const hlala_bam_interval* iv, int32_t long_read_mode, int32_t n_threads, int32_t flags,
                                            hlala_seed_batch** out)
 {
     static std::once_flag hookOnce;                  // (samples may decode on several threads)
-    std::call_once(hookOnce, []() { hlala_host::g_bam_inflate_hook = bam_inflate_hook; hlala_host::g_bam_scan_hook = bam_scan_hook; });
+    std::call_once(hookOnce, []() { hlala_host::g_bam_inflate_hook = bam_inflate_hook; hlala_host::g_bam_inflate_crc_hook = bam_inflate_crc_hook; hlala_host::g_bam_scan_hook = bam_scan_hook; });
     return hlala_host::bam_extract_seeds_impl(path, n_intervals, iv, long_read_mode, n_threads, flags, true, f, out);
 }
 
@@ -2637,7 +2678,7 @@ static int bam_scan_hook(void* inflater, hlala_host::bam_scan_round* R, std::str
     f->err.clear();
     auto out = [&](int rc) { if(rc != HLALA_OK && err) *err = f->err; return rc; };
     const size_t n = R->carry + R->seg_bytes;
-    R->n_gpu = R->n_retried = 0; R->fell_back = false; R->s_inflate = R->s_scan = 0; R->bytes_h2d = R->bytes_d2h = 0;
+    R->n_gpu = R->n_retried = R->n_crc_recheck = 0; R->fell_back = false; R->s_inflate = R->s_scan = 0; R->bytes_h2d = R->bytes_d2h = 0;
     if(n >= ((size_t)1 << 32)) { f->err = "a round of 2^32 bytes or more: lower HLALA_BAM_SEGMENT_BYTES"; return out(HLALA_E_CAPACITY); }
     if(R->carry > f->roundBytes) { f->err = "more bytes carried than the last round held"; return out(HLALA_E_STATE); }
     const auto t0 = std::chrono::steady_clock::now();
@@ -2661,14 +2702,15 @@ static int bam_scan_hook(void* inflater, hlala_host::bam_scan_round* R, std::str
     }
     f->roundBytes = n;
     std::vector<int32_t> status((size_t)R->n_blocks + 1, 0);
-    int rc = inflate_run(f, R->comp, R->comp_bytes, R->blocks, R->n_blocks, nullptr, R->seg_bytes, status.data(), nullptr, nullptr, nullptr, dData + R->carry);
+    int rc = inflate_run(f, R->comp, R->comp_bytes, R->blocks, R->n_blocks, nullptr, R->seg_bytes, status.data(), nullptr, nullptr, nullptr, dData + R->carry, R->crc_expect);      // (crc_expect: k_bgzf_crc32 on the round buffer, before the scan passes)
     if(rc != HLALA_OK) return out(rc);
     std::vector<uint8_t> tmp;
     for(int64_t k = 0; k < R->n_blocks; k++) {
         const hlala_bgzf_block& b = R->blocks[k];
         R->bytes_h2d += b.clen;
         if(status[(size_t)k] == HLALA_INFLATE_OK) { R->n_gpu++; continue; }
-        // the host engine's verdict stands; its bytes go into place before the scan
+        // the host engine's verdict stands (with crc_expect, host_inflate checks the CRC of what it inflated); its bytes go into place before the scan
+        if(status[(size_t)k] == HLALA_INFLATE_CRC_MISMATCH) R->n_crc_recheck++;
         tmp.resize(b.isize ? b.isize : 1);
         if(R->host_inflate(R->user, k, tmp.data()) != 0) { f->err = "the host engine rejected the block as well"; return out(HLALA_E_STATE); }
         if(b.isize && (e = hipMemcpy(dData + R->carry + b.uoff, tmp.data(), b.isize, hipMemcpyHostToDevice)) != hipSuccess) return failed("upload of a block inflated on the host");

@@ -114,7 +114,8 @@ struct Fail : std::runtime_error { using std::runtime_error::runtime_error; };
 // Both produce the same bytes; HLALA_BAM_ZLIB=1 keeps zlib (tests/test_bam.py decodes one file both ways).
 struct Inflater {
     typedef void* (*AllocFn)(void); typedef int (*RunFn)(void*, const void*, size_t, void*, size_t, size_t*); typedef void (*FreeFn)(void*);
-    static AllocFn ld_alloc; static RunFn ld_run; static FreeFn ld_free; static std::once_flag once;
+    typedef uint32_t (*CrcFn)(uint32_t, const void*, size_t);
+    static AllocFn ld_alloc; static RunFn ld_run; static FreeFn ld_free; static CrcFn ld_crc; static std::once_flag once;
     static void look()
     {
         if(getenv("HLALA_BAM_ZLIB")) return;
@@ -122,13 +123,17 @@ struct Inflater {
         if(!h) h = dlopen("libdeflate.so", RTLD_NOW | RTLD_LOCAL);
         if(!h) return;
         AllocFn a = (AllocFn)dlsym(h, "libdeflate_alloc_decompressor"); RunFn r = (RunFn)dlsym(h, "libdeflate_deflate_decompress"); FreeFn f = (FreeFn)dlsym(h, "libdeflate_free_decompressor");
-        if(a && r && f) { ld_alloc = a; ld_run = r; ld_free = f; }
+        if(a && r && f) { ld_alloc = a; ld_run = r; ld_free = f; ld_crc = (CrcFn)dlsym(h, "libdeflate_crc32"); }
     }
     void* d = nullptr;
     Inflater() { std::call_once(once, look); if(ld_alloc) d = ld_alloc(); }
     ~Inflater() { if(d) ld_free(d); }
     Inflater(const Inflater&) = delete; Inflater& operator=(const Inflater&) = delete;
     static const char* engine() { std::call_once(once, look); return ld_alloc ? "libdeflate" : "zlib"; }
+    // CRC-32 (RFC 1952) of a block's inflated bytes (HLALA_SEEDS_VERIFY_CRC): libdeflate's where its library was found, zlib's otherwise
+    static uint32_t crc(const uint8_t* p, size_t n) { std::call_once(once, look); return ld_crc ? ld_crc(0, p, n) : (uint32_t)crc32(crc32(0L, Z_NULL, 0), p, (uInt)n); }
+    // inflate and compare with the CRC the block carries
+    void run_checked(const uint8_t* in, size_t nin, uint8_t* out, size_t nout, uint32_t expect) { run(in, nin, out, nout); if(crc(out, nout) != expect) throw Fail("BGZF block CRC mismatch"); }
     void run(const uint8_t* in, size_t nin, uint8_t* out, size_t nout)
     {
         if(d) { size_t got = 0; if(ld_run(d, in, nin, out, nout, &got) != 0 || got != nout) throw Fail("BGZF inflate failed"); return; }
@@ -139,7 +144,7 @@ struct Inflater {
         if(rc != Z_STREAM_END || got != nout) throw Fail("BGZF inflate failed");
     }
 };
-Inflater::AllocFn Inflater::ld_alloc = nullptr; Inflater::RunFn Inflater::ld_run = nullptr; Inflater::FreeFn Inflater::ld_free = nullptr; std::once_flag Inflater::once;
+Inflater::AllocFn Inflater::ld_alloc = nullptr; Inflater::RunFn Inflater::ld_run = nullptr; Inflater::FreeFn Inflater::ld_free = nullptr; Inflater::CrcFn Inflater::ld_crc = nullptr; std::once_flag Inflater::once;
 
 uint32_t rd32(const uint8_t* p) { return p[0] | (p[1] << 8) | (p[2] << 16) | ((uint32_t)p[3] << 24); }
 
@@ -149,7 +154,7 @@ struct MappedFile {
     ~MappedFile() { if(p && n) munmap((void*)p, n); if(fd >= 0) close(fd); }
 };
 
-struct Block { size_t coff; uint32_t clen, isize; uint64_t uoff; };      // compressed payload at coff (clen bytes), uncompressed isize bytes at uoff of the stream
+struct Block { size_t coff; uint32_t clen, isize; uint64_t uoff; uint32_t crc; };      // compressed payload at coff (clen bytes), uncompressed isize bytes at uoff of the stream; crc: the CRC-32 field behind the payload
 
 // one kept alignment (per interval it falls into, as in the reference's loop :746-830)
 struct Rec {
@@ -233,6 +238,7 @@ struct hlala_seed_batch {
     int64_t n_units = 0; int32_t unpaired = 0; int64_t examined = 0, n_seeds = 0, n_incomplete = 0;
     double seconds[6] = {0, 0, 0, 0, 0, 0}; int32_t threads = 1;
     int64_t inflate_counts[3] = {0, 0, 0};      // blocks inflated on the GPU, rejected there and inflated again on the host, inflated on the host only
+    int64_t crc_counts[3] = {0, 0, 0};          // HLALA_SEEDS_VERIFY_CRC: blocks verified on the GPU, on the host, reported as mismatching by the GPU and checked again on the host
     int64_t parse_counts[3] = {0, 0, 0};        // records scanned on the GPU, rounds scanned there, rounds that fell back to the host's hop and parse
     int64_t transfer_bytes[2] = {0, 0};         // bytes the GPU paths of the decoder moved to the device and back
     bool pinned = false;
@@ -376,6 +382,7 @@ void (*g_seed_batch_pin_upto)(hlala_seed_batch*, int64_t) = nullptr;      // set
 bool& seed_batch_pinned_flag(hlala_seed_batch* S) { return S->pinned; }
 void (*g_seed_batch_unpin)(hlala_seed_batch*) = nullptr;       // set by the GPU library (hlala_seed_batch_pin): a pinned batch is unpinned before it is freed
 bam_inflate_hook_t g_bam_inflate_hook = nullptr;               // set by the GPU library (hlala_bam_extract_seeds_gpu)
+bam_inflate_crc_hook_t g_bam_inflate_crc_hook = nullptr;       // ... (HLALA_SEEDS_VERIFY_CRC)
 bam_scan_hook_t g_bam_scan_hook = nullptr;                     // ... (HLALA_SEEDS_GPU_PARSE)
 }  // namespace hlala_host
 
@@ -428,8 +435,8 @@ extern "C" int hlala_bam_extract_seeds_opt(const char* path, int32_t n_intervals
 namespace {
 // what the hook's `landed` call needs: the statuses of a round's blocks, and how to inflate a rejected block again on the host
 struct GpuRound {
-    const Block* blocks; const uint8_t* comp; uint8_t* out; uint64_t u0; std::vector<int32_t>* status; std::atomic<uint8_t>* blockDone; Inflater* host;
-    int64_t nGpu = 0, nRetried = 0; std::exception_ptr err;
+    const Block* blocks; const uint8_t* comp; uint8_t* out; uint64_t u0; std::vector<int32_t>* status; std::atomic<uint8_t>* blockDone; Inflater* host; bool verifyCrc;
+    int64_t nGpu = 0, nRetried = 0, nCrcRecheck = 0; std::exception_ptr err;
     int64_t bytesDown = 0;
     static int landed(void* user, int64_t first, int64_t count)
     {
@@ -437,7 +444,11 @@ struct GpuRound {
         try {
             for(int64_t k = first; k < first + count; k++) {
                 const Block& b = R.blocks[k];
-                if((*R.status)[(size_t)k] != 0) { R.host->run(R.comp + b.coff, b.clen, R.out + (size_t)(b.uoff - R.u0), b.isize); R.nRetried++; }      // the host engine's verdict stands (it throws what the host path throws)
+                if((*R.status)[(size_t)k] != 0) {                                          // the host engine's verdict stands (it throws what the host path throws)
+                    if((*R.status)[(size_t)k] == HLALA_INFLATE_CRC_MISMATCH) R.nCrcRecheck++;
+                    if(R.verifyCrc) R.host->run_checked(R.comp + b.coff, b.clen, R.out + (size_t)(b.uoff - R.u0), b.isize, b.crc); else R.host->run(R.comp + b.coff, b.clen, R.out + (size_t)(b.uoff - R.u0), b.isize);
+                    R.nRetried++;
+                }
                 else { R.nGpu++; R.bytesDown += b.isize; }
                 R.blockDone[(size_t)k].store(1, std::memory_order_release);
             }
@@ -447,12 +458,12 @@ struct GpuRound {
 };
 // what the record pass of a round (hlala_host::bam_scan_round) calls back: the host engine for a rejected block, and where its outputs go
 struct ScanRound {
-    const Block* blocks; const uint8_t* comp; Inflater* host; std::exception_ptr err;
+    const Block* blocks; const uint8_t* comp; Inflater* host; bool verifyCrc; std::exception_ptr err;
     std::vector<hlala_bam_rec> recs; std::unique_ptr<uint8_t, BigFree> compact, fallback;
     static int host_inflate(void* user, int64_t k, uint8_t* out)
     {
         ScanRound& R = *(ScanRound*)user;
-        try { const Block& b = R.blocks[k]; R.host->run(R.comp + b.coff, b.clen, out, b.isize); } catch(...) { R.err = std::current_exception(); return 1; }
+        try { const Block& b = R.blocks[k]; if(R.verifyCrc) R.host->run_checked(R.comp + b.coff, b.clen, out, b.isize, b.crc); else R.host->run(R.comp + b.coff, b.clen, out, b.isize); } catch(...) { R.err = std::current_exception(); return 1; }
         return 0;
     }
     static hlala_bam_rec* alloc_recs(void* user, int64_t n) { ScanRound& R = *(ScanRound*)user; try { R.recs.resize((size_t)n); } catch(...) { R.err = std::current_exception(); return nullptr; } return R.recs.data(); }
@@ -466,7 +477,8 @@ try {
     if(!path || !out || n_intervals < 0 || (n_intervals > 0 && !iv) || n_threads < 0) return HLALA_E_ARG;
     *out = nullptr; g_bam_error.clear();
     if(gpu && (!gpuInflater || !g_bam_inflate_hook)) { g_bam_error = "hlala_bam_extract_seeds_gpu: no inflater"; return HLALA_E_ARG; }
-    const bool gpuParse = (flags & HLALA_SEEDS_GPU_PARSE) != 0;
+    const bool gpuParse = (flags & HLALA_SEEDS_GPU_PARSE) != 0, verifyCrc = (flags & HLALA_SEEDS_VERIFY_CRC) != 0;
+    if(gpu && verifyCrc && !gpuParse && !g_bam_inflate_crc_hook) { g_bam_error = "HLALA_SEEDS_VERIFY_CRC: this library's GPU inflate has no CRC kernel"; return HLALA_E_ARG; }
     if(gpuParse && (!gpu || !g_bam_scan_hook)) { g_bam_error = "HLALA_SEEDS_GPU_PARSE needs hlala_bam_extract_seeds_gpu"; return HLALA_E_ARG; }
     int T = n_threads;
     // Default: at most 32 threads.  Measured on a 256-thread host (tools/gpu_decode_threads.sh, 8.4 M pairs, 2.6 GB of BAM): 5.2 s on 8 threads, 3.5 on 16, 2.85 on 32,
@@ -503,9 +515,10 @@ try {
             if(bsize < 0) throw Fail("BGZF block without BC field");
             if((size_t)bsize + 1 < 12 + xlen + 8) throw Fail("BGZF block size smaller than its own header");
             if(mf.n - o < (size_t)bsize + 1) throw Fail("truncated BGZF block");
-            Block b; b.coff = o + 12 + xlen; b.clen = (uint32_t)((size_t)bsize + 1 - 12 - xlen - 8); b.isize = rd32(h + bsize + 1 - 4); b.uoff = u;
+            Block b; b.coff = o + 12 + xlen; b.clen = (uint32_t)((size_t)bsize + 1 - 12 - xlen - 8); b.isize = rd32(h + bsize + 1 - 4); b.uoff = u; b.crc = rd32(h + bsize + 1 - 8);
             if(b.isize > (1u << 16)) throw Fail("BGZF block with more than 64 KiB of payload");
             if(b.isize) blocks.push_back(b);                              // (empty blocks: the end-of-file marker)
+            else if(verifyCrc) { if(b.crc != 0) throw Fail("BGZF block CRC mismatch"); S->crc_counts[1]++; }      // (no byte: CRC 0, checked here)
             u += b.isize; o += (size_t)bsize + 1;
         }
     }
@@ -547,7 +560,7 @@ try {
     if(gpuParse) {
         std::vector<uint8_t> hb; size_t nb = 0, o = 0;
         auto have = [&](size_t k) {
-            while(hb.size() - o < k && nb < blocks.size()) { const Block& b = blocks[nb++]; const size_t at = hb.size(); hb.resize(at + b.isize); inflaters[0].run(mf.p + b.coff, b.clen, hb.data() + at, b.isize); }
+            while(hb.size() - o < k && nb < blocks.size()) { const Block& b = blocks[nb++]; const size_t at = hb.size(); hb.resize(at + b.isize); if(verifyCrc) inflaters[0].run_checked(mf.p + b.coff, b.clen, hb.data() + at, b.isize, b.crc); else inflaters[0].run(mf.p + b.coff, b.clen, hb.data() + at, b.isize); }      // (checked here, counted with their round)
             return hb.size() - o >= k;
         };
         auto need = [&](size_t k) { if(!have(k)) throw Fail("truncated BAM header"); };
@@ -590,15 +603,17 @@ try {
             hlala_bam_scan_in sin; memset(&sin, 0, sizeof(sin));
             sin.n_ref = n_ref; sin.n_intervals = n_intervals; sin.ref_iv_off = csrOff.data(); sin.ref_iv = csrIv.data(); sin.iv_start = ivStart.data(); sin.iv_stop = ivStop.data(); sin.iv_contig = ivContig.data();
             sin.long_read_mode = long_read_mode ? 1 : 0; sin.max_rehops = scanMaxRehops; sin.hash_mask = hashMask; sin.first_seq = recSeq;
-            ScanRound U{blocks.data() + b0, mf.p, &inflaters[0]};
+            ScanRound U{blocks.data() + b0, mf.p, &inflaters[0], verifyCrc};
+            std::vector<uint32_t> crcExpect; if(verifyCrc) { crcExpect.resize(nBlk); for(size_t k = 0; k < nBlk; k++) crcExpect[k] = blocks[b0 + k].crc; }
             bam_scan_round R; memset((void*)&R, 0, sizeof(R));
-            R.comp = mf.p; R.comp_bytes = mf.n; R.blocks = desc.data(); R.n_blocks = (int64_t)nBlk; R.seg_bytes = segBytes; R.carry = carry; R.first = b0 == 0 ? firstRecord : 0; R.last = lastSegment ? 1 : 0; R.in = &sin;
+            R.comp = mf.p; R.comp_bytes = mf.n; R.blocks = desc.data(); R.n_blocks = (int64_t)nBlk; R.seg_bytes = segBytes; R.carry = carry; R.first = b0 == 0 ? firstRecord : 0; R.last = lastSegment ? 1 : 0; R.in = &sin; R.crc_expect = verifyCrc ? crcExpect.data() : nullptr;
             R.user = &U; R.host_inflate = ScanRound::host_inflate; R.alloc_recs = ScanRound::alloc_recs; R.alloc_compact = ScanRound::alloc_compact; R.alloc_fallback = ScanRound::alloc_fallback;
             std::string herr;
             const int rc = g_bam_scan_hook(gpuInflater, &R, &herr);
             if(U.err) std::rethrow_exception(U.err);
             if(rc != HLALA_OK) throw Fail("BAM record pass on the GPU failed: " + herr);
             S->inflate_counts[0] += R.n_gpu; S->inflate_counts[1] += R.n_retried; S->transfer_bytes[0] += R.bytes_h2d; S->transfer_bytes[1] += R.bytes_d2h;
+            if(verifyCrc) { S->crc_counts[0] += R.n_gpu; S->crc_counts[1] += R.n_retried; S->crc_counts[2] += R.n_crc_recheck; }
             sGpuInflate = R.s_inflate;
             if(!R.fell_back) {
                 if(R.stats.status != HLALA_BAMSCAN_OK) throw Fail(hlala_bam_scan_status_text(R.stats.status));
@@ -645,22 +660,27 @@ try {
         // GPU rejects is inflated again by the host engine as its chunk lands)
         auto inflateHost = [&](int64_t k, int t) {
             const Block& b = blocks[b0 + (size_t)k];
-            inflaters[(size_t)t].run(mf.p + b.coff, b.clen, bufp + carry + (size_t)(b.uoff - u0), b.isize);
+            uint8_t* to = bufp + carry + (size_t)(b.uoff - u0);
+            if(verifyCrc) inflaters[(size_t)t].run_checked(mf.p + b.coff, b.clen, to, b.isize, b.crc); else inflaters[(size_t)t].run(mf.p + b.coff, b.clen, to, b.isize);
             blockDone[(size_t)k].store(1, std::memory_order_release);
         };
         auto inflateGpu = [&](int64_t, int) {
             std::vector<hlala_bgzf_block> desc(nBlk); std::vector<int32_t> status(nBlk, 0);
+            std::vector<uint32_t> crcExpect; if(verifyCrc) { crcExpect.resize(nBlk); for(size_t k = 0; k < nBlk; k++) crcExpect[k] = blocks[b0 + k].crc; }
             for(size_t k = 0; k < nBlk; k++) { const Block& b = blocks[b0 + k]; desc[k].coff = b.coff; desc[k].clen = b.clen; desc[k].isize = b.isize; desc[k].uoff = b.uoff - u0; }
-            GpuRound R{blocks.data() + b0, mf.p, bufp + carry, u0, &status, blockDone.get(), &inflaters[0]};
+            GpuRound R{blocks.data() + b0, mf.p, bufp + carry, u0, &status, blockDone.get(), &inflaters[0], verifyCrc};
             std::string herr;
-            const int rc = g_bam_inflate_hook(gpuInflater, mf.p, mf.n, desc.data(), (int64_t)nBlk, bufp + carry, segBytes, status.data(), GpuRound::landed, &R, &herr);
+            const int rc = verifyCrc ? g_bam_inflate_crc_hook(gpuInflater, mf.p, mf.n, desc.data(), (int64_t)nBlk, bufp + carry, segBytes, status.data(), GpuRound::landed, &R, crcExpect.data(), &herr)
+                                     : g_bam_inflate_hook(gpuInflater, mf.p, mf.n, desc.data(), (int64_t)nBlk, bufp + carry, segBytes, status.data(), GpuRound::landed, &R, &herr);
             if(R.err) std::rethrow_exception(R.err);
             if(rc != HLALA_OK) throw Fail("BGZF inflate on the GPU failed: " + herr);
             S->inflate_counts[0] += R.nGpu; S->inflate_counts[1] += R.nRetried;
+            if(verifyCrc) { S->crc_counts[0] += R.nGpu; S->crc_counts[1] += R.nRetried; S->crc_counts[2] += R.nCrcRecheck; }
             for(size_t k = 0; k < nBlk; k++) S->transfer_bytes[0] += blocks[b0 + k].clen;
             S->transfer_bytes[1] += R.bytesDown;
         };
         if(!gpu) S->inflate_counts[2] += (int64_t)nBlk;
+        if(!gpu && verifyCrc) S->crc_counts[1] += (int64_t)nBlk;
         auto inflateItem = [&](int64_t k, int t) { if(gpu) inflateGpu(k, t); else inflateHost(k, t); };
         if(gpuParse && !scanned) {
             o = b0 == 0 ? firstRecord : 0;
@@ -991,6 +1011,12 @@ extern "C" int hlala_seed_batch_inflate_counts(const hlala_seed_batch* S, int64_
 {
     if(!S || !counts) return HLALA_E_ARG;
     for(int i = 0; i < 3; i++) counts[i] = S->inflate_counts[i];
+    return HLALA_OK;
+}
+extern "C" int hlala_seed_batch_crc_counts(const hlala_seed_batch* S, int64_t* counts)
+{
+    if(!S || !counts) return HLALA_E_ARG;
+    for(int i = 0; i < 3; i++) counts[i] = S->crc_counts[i];
     return HLALA_OK;
 }
 extern "C" int hlala_seed_batch_parse_counts(const hlala_seed_batch* S, int64_t* counts)

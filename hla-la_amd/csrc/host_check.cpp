@@ -5,6 +5,7 @@
 
 #include "flat_graph.hpp"
 #include "inflate_core.h"
+#include "crc32_core.h"
 #include "bam_scan_model.h"
 
 static thread_local std::string g_err;
@@ -86,6 +87,13 @@ int hlala_host_inflate_model(const uint8_t* comp, uint32_t clen, uint8_t* out, u
         }
         if(final) return produced == isize ? HLALA_INFLATE_OK : HLALA_INFLATE_OUTPUT_SIZE;
     }
+}
+// The CRC-32 split of the device kernel (kernel_crc32.hip; crc32_core.h) run serially, the 64 lanes in a loop: the CRC-32 (RFC 1952) of data[0, n).  Reads nothing else.
+uint32_t hlala_host_crc32_model(const uint8_t* data, uint32_t n)
+{
+    struct Tables { uint32_t v[hlala_crc32::CRC_TABLE_WORDS]; };
+    static const Tables tables = [] { Tables t; hlala_crc32::crc_build_tables(t.v); return t; }();
+    return hlala_crc32::crc_of_block_model(data, n, tables.v);
 }
 // The BAM record pass of the device (kernel_bamscan.hip) run serially over the same core (bam_scan_model.h): the arguments, the return codes and every output of
 // hlala_bam_scan, without a device.  hlala_host_last_error() says what HLALA_E_ARG objects to.

@@ -43,6 +43,10 @@ extern void (*g_seed_batch_unpin)(hlala_seed_batch*);
 typedef int (*bam_inflate_hook_t)(void* inflater, const uint8_t* comp, size_t comp_bytes, const hlala_bgzf_block* blocks, int64_t n, uint8_t* out, size_t out_bytes, int32_t* status,
                                   int (*landed)(void*, int64_t, int64_t), void* user, std::string* err);
 extern bam_inflate_hook_t g_bam_inflate_hook;
+// ... with HLALA_SEEDS_VERIFY_CRC: the same call plus the CRC-32 every block carries; a block whose inflated bytes have another one lands with HLALA_INFLATE_CRC_MISMATCH
+typedef int (*bam_inflate_crc_hook_t)(void* inflater, const uint8_t* comp, size_t comp_bytes, const hlala_bgzf_block* blocks, int64_t n, uint8_t* out, size_t out_bytes, int32_t* status,
+                                      int (*landed)(void*, int64_t, int64_t), void* user, const uint32_t* crc_expect /* [n] */, std::string* err);
+extern bam_inflate_crc_hook_t g_bam_inflate_crc_hook;
 // The record pass of a round on the GPU (HLALA_SEEDS_GPU_PARSE): the second hook of the GPU library.  The device keeps the round's buffer [carry | this round's blocks]:
 // the last `carry` bytes of the previous round's buffer move to its front (device to device), the blocks are inflated into it (a block the kernel rejects is
 // inflated by host_inflate and uploaded into place), then hlala_bam_scan's passes run on it.  Descriptors and compact bytes come back through alloc_recs /
@@ -50,13 +54,14 @@ extern bam_inflate_hook_t g_bam_inflate_hook;
 struct bam_scan_round {
     const uint8_t* comp; size_t comp_bytes; const hlala_bgzf_block* blocks; int64_t n_blocks;      // uoff: from the first block of the round, without gaps
     size_t seg_bytes, carry, first; int32_t last; const hlala_bam_scan_in* in;
+    const uint32_t* crc_expect;                                        // [n_blocks] or null (HLALA_SEEDS_VERIFY_CRC): checked on the device; host_inflate checks what it inflates itself
     void* user;
     int (*host_inflate)(void* user, int64_t k, uint8_t* out);          // block k by the host engine into out[0, isize); non-zero: it failed, the caller holds the exception
     hlala_bam_rec* (*alloc_recs)(void* user, int64_t n);
     uint8_t* (*alloc_compact)(void* user, size_t bytes);
     uint8_t* (*alloc_fallback)(void* user, size_t bytes);              // carry + seg_bytes
     // results
-    hlala_bam_scan_stats stats; int64_t n_gpu, n_retried; bool fell_back; double s_inflate, s_scan; int64_t bytes_h2d, bytes_d2h;
+    hlala_bam_scan_stats stats; int64_t n_gpu, n_retried, n_crc_recheck; bool fell_back; double s_inflate, s_scan; int64_t bytes_h2d, bytes_d2h;
 };
 typedef int (*bam_scan_hook_t)(void* inflater, bam_scan_round* R, std::string* err);
 extern bam_scan_hook_t g_bam_scan_hook;

@@ -465,7 +465,9 @@ const char* hlala_bam_inflate_engine(void);
 /* ------------------------------------------------------------------------------------------
  * BGZF inflate on the GPU (opt-in; the entry points above inflate on the host).  BGZF blocks are independent raw DEFLATE streams (RFC 1951) of at
  * most 64 KiB of payload: one wavefront decodes one block (csrc/kernel_inflate.hip; the serial part of the decoder is csrc/inflate_core.h, which the
- * host can run as well).  The CRC-32 of a block is not verified (the host engines do not verify it either).
+ * host can run as well).  The CRC-32 of a block is verified on request only: hlala_bgzf_inflate_crc, and HLALA_SEEDS_VERIFY_CRC in the decoders (one wavefront
+ * per block again, csrc/kernel_crc32.hip behind the inflate kernel; the split is csrc/crc32_core.h, which the host can run as well).  hlala_bgzf_inflate and
+ * the decoders without that flag do not look at it.
  *
  * An hlala_inflater is a light handle of its own, not an hlala_ctx: it needs no graph and can decode a sample while the contexts are still being
  * created.  It owns its streams, its page-locked staging buffers and its device buffers.  Without a GPU hlala_inflater_create fails with
@@ -482,6 +484,7 @@ const char* hlala_bam_inflate_engine(void);
 #define HLALA_INFLATE_FAR_DISTANCE     5   /* a match reaches before the first output byte of the block (there is no preset dictionary)      */
 #define HLALA_INFLATE_INPUT_EXHAUSTED  6   /* the stream wants bits beyond its last byte                                                      */
 #define HLALA_INFLATE_OUTPUT_SIZE      7   /* the stream does not produce exactly isize bytes                                                 */
+#define HLALA_INFLATE_CRC_MISMATCH     8   /* inflated to isize bytes whose CRC-32 is not the expected one (hlala_bgzf_inflate_crc only)      */
 /* smallest and default number of compressed bytes staged per launch (chunk_bytes of hlala_inflater_create; smaller non-zero values are HLALA_E_ARG) */
 #define HLALA_INFLATE_MIN_CHUNK      ((size_t)1 << 17)
 #define HLALA_INFLATE_DEFAULT_CHUNK  ((size_t)32 << 20)
@@ -499,6 +502,13 @@ const char* hlala_inflater_last_error(const hlala_inflater* inf);
  * rejected block holds unspecified bytes, nothing else of out is written.  Returns HLALA_OK whenever the call itself worked. */
 int  hlala_bgzf_inflate(hlala_inflater* inf, const uint8_t* comp, size_t comp_bytes, const hlala_bgzf_block* blocks, int64_t n_blocks,
                         uint8_t* out, size_t out_bytes, int32_t* status /* [n_blocks] */, hlala_inflate_stats* stats /* or NULL */);
+/* hlala_bgzf_inflate plus the CRC-32 (RFC 1952) of every accepted block's inflated bytes, computed on the device by k_bgzf_crc32 behind the inflate kernel of every
+ * chunk.  crc_expect[i] (may be NULL): a block whose CRC differs gets status HLALA_INFLATE_CRC_MISMATCH; its bytes are delivered all the same and it counts in
+ * n_rejected.  crc_out[i] (may be NULL) receives the CRC of an accepted block (0 for isize = 0) and 0 for a block the inflate kernel rejected, whose status stays.
+ * With both NULL nothing extra is launched: the call is hlala_bgzf_inflate. */
+int  hlala_bgzf_inflate_crc(hlala_inflater* inf, const uint8_t* comp, size_t comp_bytes, const hlala_bgzf_block* blocks, int64_t n_blocks,
+                            uint8_t* out, size_t out_bytes, const uint32_t* crc_expect /* [n_blocks] or NULL */, uint32_t* crc_out /* [n_blocks] or NULL */,
+                            int32_t* status, hlala_inflate_stats* stats /* or NULL */, double* ms_crc /* summed device time of k_bgzf_crc32, or NULL */);
 /* The sample of hlala_bam_extract_seeds_opt, the BGZF blocks inflated by `inf`: one thread feeds the GPU round by round while the calling thread walks the record
  * lengths behind the chunks that have landed (with n_threads = 1 there is no second thread: the round is inflated first and walked afterwards); n_threads parse, group
  * and sort as before.  A block the GPU rejects is inflated again by the host engine, whose
@@ -507,6 +517,13 @@ int  hlala_bam_extract_seeds_gpu(hlala_inflater* inf, const char* bam_path, int3
                                  int32_t long_read_mode, int32_t n_threads, int32_t flags, hlala_seed_batch** out);
 /* counts[3]: blocks inflated on the GPU, blocks the GPU rejected and the host engine ran again, blocks inflated on the host only */
 int  hlala_seed_batch_inflate_counts(const hlala_seed_batch* s, int64_t* counts);
+/* Flag of hlala_bam_extract_seeds_opt and hlala_bam_extract_seeds_gpu: the CRC-32 that every BGZF block carries behind its payload is compared with that of the
+ * inflated bytes.  Host inflate: on the host, by the thread that inflated the block.  GPU inflate, with or without HLALA_SEEDS_GPU_PARSE: by k_bgzf_crc32 before the
+ * statuses come down; a block the host engine redid is checked on the host, and so is a block the GPU reports as mismatching -- the host engine's verdict stands.
+ * Empty blocks (the end-of-file marker) are checked on the host.  A mismatch ends the call with the text "BGZF block CRC mismatch" on every path. */
+#define HLALA_SEEDS_VERIFY_CRC 4
+/* counts[3]: blocks verified on the GPU, verified on the host, reported as mismatching by the GPU and checked again on the host (all zero without the flag) */
+int  hlala_seed_batch_crc_counts(const hlala_seed_batch* s, int64_t* counts);
 
 /* ------------------------------------------------------------------------------------------
  * BAM record pass on the GPU (opt-in): record boundaries, the filters / CIGAR / AS tag / name hash of the host decoder's parse phase, and compaction of
@@ -913,7 +930,9 @@ int  hlala_abi_sizeof(const char* struct_name);
  * 4 = hlala_batch_stats ends with n_dp_band / n_dp_band_failed / n_dp_jump_free_failed / ms_dp_band (round 5);
  * 5 = ... with n_dp_band2 / n_dp_band2_failed / ms_dp_band2, hlala_set_tail_pool / hlala_flush / hlala_comm_* exist (round 6);
  * 6 = hlala_inflater_* / hlala_bgzf_inflate / hlala_bam_extract_seeds_gpu / hlala_seed_batch_inflate_counts exist (additive);
- * 7 = hlala_bam_scan / hlala_bam_scan_status_text and their structs, HLALA_SEEDS_GPU_PARSE, hlala_seed_batch_parse_counts / _transfer_bytes exist (additive).  A caller compares
+ * 7 = hlala_bam_scan / hlala_bam_scan_status_text and their structs, HLALA_SEEDS_GPU_PARSE, hlala_seed_batch_parse_counts / _transfer_bytes exist (additive).
+ * Symbols that are purely additive no longer change it (hlala_set_pair_overflow; hlala_bgzf_inflate_crc, HLALA_SEEDS_VERIFY_CRC, hlala_seed_batch_crc_counts): a caller
+ * detects them by the presence of the symbol.  A caller compares
  * hlala_abi_version() with the HLALA_ABI_VERSION it was compiled against and refuses to run on a mismatch (hla-la_amd/__init__.py and
  * hla-la_amd/host/hlala_host.hpp do). */
 #define HLALA_ABI_VERSION 7

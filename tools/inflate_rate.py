@@ -9,7 +9,10 @@ of hlala_seed_batch_timing; for the GPU path also the blocks by who inflated the
 upload, kernel, download, wall; blocks/s and inflated GB/s).  The third path, hlala_bam_extract_seeds_gpu with HLALA_SEEDS_GPU_PARSE, runs in the same alternation;
 every run also prints the bytes that crossed PCIe each way (hlala_seed_batch_transfer_bytes) and, for the third path, records / rounds / rounds that fell back.  Last,
 hlala_bam_scan alone on the first --scan-mb MiB of the inflated file at slices of 4, 16 and 64 KiB: device time per pass (median and range over --runs calls), re-hops,
-and the share of the kept records that is tags (what compaction saves).  There is no threshold: the yardstick is the host decoder on the same file and box."""
+and the share of the kept records that is tags (what compaction saves).  There is no threshold: the yardstick is the host decoder on the same file and box.
+--verify-crc (its output is meant for profiles/bgzf_crc.txt): every decoder runs with and without HLALA_SEEDS_VERIFY_CRC, alternating in the same call -- six decodes per
+round --, and hlala_bgzf_inflate_crc on all blocks reports the summed device time of k_bgzf_crc32 beside that of k_bgzf_inflate over the same chunks.  The cost of the flag
+is read against the flag-off runs of the same call; on the host decoder it is the cost of the host's own CRC pass on the threads of that run."""
 import argparse
 import os
 import sys
@@ -83,6 +86,7 @@ def main():
     ap.add_argument("--chunk-mb", type=int, default=0, help="compressed MiB staged per launch (0 = the library's default)")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--scan-mb", type=int, default=256, help="inflated MiB handed to hlala_bam_scan alone (below 4096)")
+    ap.add_argument("--verify-crc", action="store_true", help="every decoder with and without HLALA_SEEDS_VERIFY_CRC in the same alternation; k_bgzf_crc32's device time beside the inflate kernel's")
     ap.add_argument("--bam", default="", help="use this BAM (reference names PRG_<n>) instead of generating one; needs --levels of the world it was made from")
     ap.add_argument("--no-gpu", action="store_true", help="host engine only (a box without a GPU: checks the generator and the host figures)")
     args = ap.parse_args()
@@ -122,8 +126,11 @@ def main():
 
     def run(label, opener, timed):
         t = time.time(); S = opener(); wall = time.time() - t
-        tm = S.timing(); cnt = S.inflate_counts(); pc = S.parse_counts(); tb = S.transfer_bytes(); units = S.n_units; S.close()
-        if timed:
+        tm = S.timing(); cnt = S.inflate_counts(); pc = S.parse_counts(); tb = S.transfer_bytes(); cc = S.crc_counts(); units = S.n_units; S.close()
+        if timed and args.verify_crc:
+            print("%-13s wall %.3f s  %s  threads %d  units %d  blocks gpu/retried/host %d/%d/%d  CRC verified gpu/host/rechecked %d/%d/%d" % (
+                label, wall, "  ".join("%s %.3f" % (k, tm[k]) for k in keys), tm["threads"], units, cnt[0], cnt[1], cnt[2], cc[0], cc[1], cc[2]))
+        elif timed:
             print("%-9s wall %.3f s  %s  threads %d  units %d  blocks gpu/retried/host %d/%d/%d  records on the GPU %d in %d rounds, %d rounds fell back  PCIe up %.3f GB, down %.3f GB" % (
                 label, wall, "  ".join("%s %.3f" % (k, tm[k]) for k in keys), tm["threads"], units, cnt[0], cnt[1], cnt[2], pc[0], pc[1], pc[2], tb[0] / 1e9, tb[1] / 1e9))
         return tm["inflate"], tm["inflate"] + tm["parse"], wall
@@ -131,18 +138,32 @@ def main():
     gpu = (lambda: inf.bam_open_seeds(bam, intervals, threads=args.threads, flags=P.SEEDS_PACKED)) if inf else None      # noqa: E731
     gpu_parse = (lambda: inf.bam_open_seeds(bam, intervals, threads=args.threads, flags=P.SEEDS_PACKED | P.SEEDS_GPU_PARSE)) if inf else None      # noqa: E731
     res = {"host": [], "gpu": [], "gpu+parse": []}
+    order = ["host", "gpu", "gpu+parse"]
+    openers = {"host": host, "gpu": gpu, "gpu+parse": gpu_parse}
+    if args.verify_crc:
+        V = P.SEEDS_PACKED | P.SEEDS_VERIFY_CRC
+        openers["host+crc"] = lambda: P.bam_open_seeds(lib, bam, intervals, threads=args.threads, flags=V)                 # noqa: E731
+        openers["gpu+crc"] = (lambda: inf.bam_open_seeds(bam, intervals, threads=args.threads, flags=V)) if inf else None      # noqa: E731
+        openers["gpu+parse+crc"] = (lambda: inf.bam_open_seeds(bam, intervals, threads=args.threads, flags=V | P.SEEDS_GPU_PARSE)) if inf else None      # noqa: E731
+        order = ["host", "host+crc", "gpu", "gpu+crc", "gpu+parse", "gpu+parse+crc"]
+        res = {k: [] for k in order}
     for i in range(args.runs + 1):
-        res["host"].append(run("host", host, i > 0))
-        if gpu:
-            res["gpu"].append(run("gpu", gpu, i > 0))
-            res["gpu+parse"].append(run("gpu+parse", gpu_parse, i > 0))
-    for k in ("host", "gpu", "gpu+parse"):
+        for k in order:
+            if openers[k]:
+                res[k].append(run(k, openers[k], i > 0))
+    for k in order:
         if len(res[k]) > 1:
             v = [x[0] for x in res[k][1:]]
             print("inflate phase, %s: median %.3f s (%.2f GB/s inflated) of %s" % (k, float(np.median(v)), n_inflated / 1e9 / float(np.median(v)), ["%.3f" % x for x in v]))
             for j, what in ((1, "inflate + parse phases"), (2, "decode, wall")):
                 v = [x[j] for x in res[k][1:]]
                 print("%s, %s: median %.3f s, range %.3f .. %.3f of %d runs" % (what, k, float(np.median(v)), min(v), max(v), len(v)))
+    if args.verify_crc:
+        for k in ("host", "gpu", "gpu+parse"):
+            if len(res[k]) > 1 and len(res[k + "+crc"]) > 1:
+                for j, what in ((0, "inflate phase"), (2, "decode, wall")):
+                    a = float(np.median([x[j] for x in res[k][1:]])); b = float(np.median([x[j] for x in res[k + "+crc"][1:]]))
+                    print("cost of HLALA_SEEDS_VERIFY_CRC, %s, %s: %+.3f s (median %.3f with against %.3f without; %.3f GB inflated)" % (k, what, b - a, b, a, n_inflated / 1e9))
     if inf:
         # the kernel and its copies alone: every block of the file in one call, into one pageable buffer
         out = np.empty(n_inflated, np.uint8); desc = []; u = 0
@@ -154,7 +175,21 @@ def main():
         print("hlala_bgzf_inflate, all blocks in one call (second call): upload %.1f ms, kernel %.1f ms, download %.1f ms (device times summed over the chunks; they overlap), "
               "wall %.1f ms: %.0f blocks/s, %.2f GB/s inflated" % (st.ms_h2d, st.ms_kernel, st.ms_d2h, st.ms_wall, st.n_blocks / (st.ms_wall / 1e3), n_inflated / 1e9 / (st.ms_wall / 1e3)))
         print("kernel alone: %.2f GB/s inflated; download alone: %.2f GB/s" % (n_inflated / 1e9 / (st.ms_kernel / 1e3), n_inflated / 1e9 / max(1e-9, st.ms_d2h / 1e3)))
-        scan_alone(P, inf, out, intervals, args)
+        if args.verify_crc:
+            # the same call with the CRC kernel behind the inflate kernel of every chunk; expected values from the file
+            expect = np.array([int.from_bytes(raw[off + clen_:off + clen_ + 4].tobytes(), "little") for off, clen_, _ in blocks], np.uint32)
+            tk = []; tc = []; tw = []
+            for i in range(args.runs + 1):
+                status, st, got = inf.inflate(raw, desc, out, crc=expect, want_crc=True)
+                assert int((status != 0).sum()) == 0 and np.array_equal(got, expect), "the GPU reports CRC mismatches on a valid file"
+                if i:
+                    tk.append(st.ms_kernel); tc.append(inf.ms_crc); tw.append(st.ms_wall)
+            med = lambda v: "%.1f (%.1f .. %.1f)" % (float(np.median(v)), min(v), max(v))      # noqa: E731
+            print("hlala_bgzf_inflate_crc, all blocks in one call, ms summed over the chunks, median (min .. max) of %d calls after one warm-up: k_bgzf_inflate %s, k_bgzf_crc32 %s, wall %s" % (
+                args.runs, med(tk), med(tc), med(tw)))
+            print("k_bgzf_crc32 alone: %.1f GB/s inflated, %.3f of the inflate kernel's device time" % (n_inflated / 1e9 / (float(np.median(tc)) / 1e3), float(np.median(tc)) / float(np.median(tk))))
+        if args.scan_mb > 0:
+            scan_alone(P, inf, out, intervals, args)
         inf.close()
     if tmp:
         import shutil
