@@ -325,6 +325,13 @@ class SeedBatch:
         self.lib.hlala_seed_batch_crc_counts(self.h, cnt)
         return tuple(int(x) for x in cnt)
 
+    def group_counts(self):
+        """(records grouped on the GPU, collided hash runs the host regrouped, 1 if the whole sample was grouped by the host instead); all zero without SEEDS_GPU_GROUP"""
+        cnt = (C.c_int64 * 3)()
+        self.lib.hlala_seed_batch_group_counts.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        self.lib.hlala_seed_batch_group_counts(self.h, cnt)
+        return tuple(int(x) for x in cnt)
+
     def inflate_counts(self):
         """(blocks inflated on the GPU, blocks the GPU rejected and the host engine ran again, blocks inflated on the host only)"""
         cnt = (C.c_int64 * 3)()
@@ -350,6 +357,7 @@ class SeedBatch:
 SEEDS_PACKED = 1          # HLALA_SEEDS_PACKED
 SEEDS_GPU_PARSE = 2       # HLALA_SEEDS_GPU_PARSE (Inflater.bam_open_seeds only): the record pass of every round on the GPU as well
 SEEDS_VERIFY_CRC = 4      # HLALA_SEEDS_VERIFY_CRC (bam_open_seeds and Inflater.bam_open_seeds): the CRC-32 of every BGZF block is compared with that of its inflated bytes
+SEEDS_GPU_GROUP = 8       # HLALA_SEEDS_GPU_GROUP (with SEEDS_GPU_PARSE only): the records are grouped by read name on the GPU as well
 
 
 def bam_open_seeds(lib, path, intervals, long_read_mode=False, threads=0, flags=0) -> SeedBatch:
@@ -381,6 +389,14 @@ class BamScanIn(C.Structure):
 class BamScanStats(C.Structure):
     _fields_ = [(k, C.c_int64) for k in ("n_records", "n_kept", "n_recs", "examined", "consumed", "compact_bytes")] + [("status", C.c_int32), ("pad", C.c_int32), ("status_record", C.c_int64),
                ("n_slices", C.c_int64), ("n_rehops", C.c_int64)] + [(k, C.c_double) for k in ("ms_h2d", "ms_guess", "ms_link", "ms_starts", "ms_parse", "ms_scan", "ms_emit", "ms_d2h", "ms_wall")]
+
+
+class BamGroupStats(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("n_recs", "n_runs", "n_collided_runs", "n_units_complete", "n_units_incomplete")] + \
+               [(k, C.c_double) for k in ("ms_h2d", "ms_append", "ms_sort", "ms_mark", "ms_fold", "ms_emit", "ms_d2h", "ms_wall")]
+
+
+GROUP_START, GROUP_COLLIDED, GROUP_COMPLETE = 1, 2, 4          # flag[] of hlala_bam_group
 
 
 # hlala_bam_rec
@@ -468,6 +484,29 @@ class Inflater:
             return rc, recs, comp, st
         ok = rc == 0 and st.status == 0
         return rc, recs[:(st.n_recs if ok else 0) * BAM_REC_DTYPE.itemsize].view(BAM_REC_DTYPE), comp[:st.compact_bytes if ok else 0], st
+
+    def bam_group(self, recs, data, long_read_mode=False, rounds=None, n=None, n_bytes=None):
+        """hlala_bam_group (rounds: hlala_bam_group_rounds, the descriptors appended on the device in calls of these sizes).  recs: a BAM_REC_DTYPE array in ascending order,
+        data: the bytes the names lie in (at rec_off + 32).  Returns (return code, perm, flag, BamGroupStats); HLALA_E_ARG (-1) is returned, not raised (last_error() says why).
+        n / n_bytes: the sizes handed in, where they are to differ from the arrays' (tests)."""
+        recs = np.ascontiguousarray(recs, BAM_REC_DTYPE); data = np.ascontiguousarray(data, np.uint8)
+        n = recs.size if n is None else int(n); nb = data.size if n_bytes is None else int(n_bytes)
+        perm = np.zeros(max(1, recs.size), np.uint32); flag = np.zeros(max(1, recs.size), np.uint8); st = BamGroupStats()
+        rp, dp = (recs.ctypes.data if recs.size else None), (data.ctypes.data if data.size else None)
+        if rounds is None:
+            self.lib.hlala_bam_group.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(BamGroupStats)]
+            rc = self.lib.hlala_bam_group(self.h, rp, n, dp, nb, int(bool(long_read_mode)), perm.ctypes.data, flag.ctypes.data, C.byref(st))
+        else:
+            rr = np.ascontiguousarray(rounds, np.int64)
+            self.lib.hlala_bam_group_rounds.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(BamGroupStats)]
+            rc = self.lib.hlala_bam_group_rounds(self.h, rp, n, dp, nb, rr.ctypes.data, rr.size, int(bool(long_read_mode)), perm.ctypes.data, flag.ctypes.data, C.byref(st))
+        if rc not in (0, -1):
+            raise HlalaError(f"hlala_bam_group failed ({rc}): {self.last_error()}")
+        k = recs.size if rc == 0 else 0
+        return rc, perm[:k], flag[:k], st
+
+    def last_error(self):
+        return self.lib.hlala_inflater_last_error(self.h).decode(errors="replace")
 
     def bam_open_seeds(self, path, intervals, long_read_mode=False, threads=0, flags=0) -> SeedBatch:
         """hlala_bam_extract_seeds_gpu: the sample of bam_open_seeds, its blocks inflated by this handle (SeedBatch.inflate_counts says how many)"""
@@ -863,6 +902,7 @@ EXPORTED_SYMBOLS = [
     "hlala_inflater_create", "hlala_inflater_destroy", "hlala_inflater_last_error", "hlala_bgzf_inflate", "hlala_bam_extract_seeds_gpu", "hlala_seed_batch_inflate_counts",
     "hlala_bgzf_inflate_crc", "hlala_seed_batch_crc_counts",
     "hlala_bam_scan", "hlala_bam_scan_status_text", "hlala_seed_batch_parse_counts", "hlala_seed_batch_transfer_bytes",
+    "hlala_bam_group", "hlala_bam_group_rounds", "hlala_seed_batch_group_counts",
     "hlala_locus_cluster_kmers", "hlala_type_locus", "hlala_kmer_presence", "hlala_kmer_keep_reads", "hlala_kmer_presence_kept", "hlala_kmer_forget_reads", "hlala_unit_alignment_stats", "hlala_typer_write_summary", "hlala_typer_begin_output", "hlala_locus_write_files", "hlala_locus_write_pairs_file", "hlala_typer_end_output",
 ]
 

@@ -32,6 +32,7 @@
 #include "kernel_inflate.hip"
 #include "kernel_crc32.hip"
 #include "kernel_bamscan.hip"
+#include "kernel_bamgroup.hip"
 
 namespace hlala {
 size_t proj_slab_bytes_host(int stride, int maxNodesPerLevel) { return proj_slab_bytes(stride, maxNodesPerLevel); }
@@ -2349,11 +2350,21 @@ struct InflateSlot {
 struct ScanBuf { void* p = nullptr; size_t cap = 0; };
 enum { SCAN_DATA, SCAN_CARRY, SCAN_SLICES, SCAN_TOTALS, SCAN_INTERVALS, SCAN_RECORDS, SCAN_OFFSETS, SCAN_RECS, SCAN_COMPACT, SCAN_NBUF };
 constexpr int SCAN_NEV = 11;
+// device state of the grouping stage (hlala_bam_group; HLALA_SEEDS_GPU_GROUP): the sample-long arrays k_grp_append fills round by round (hash, meta, name offsets, name arena: they
+// grow geometrically, by device-to-device copy), the scratch of the passes behind them, how many descriptors and name bytes they hold
+enum { GRP_HASH, GRP_META, GRP_NAMEOFF, GRP_NAMES, GRP_LEN, GRP_OFF, GRP_CUB, GRP_KEYS, GRP_VAL_IN, GRP_VAL_OUT, GRP_START, GRP_RUNOFF, GRP_NEQ, GRP_WORD, GRP_FLAG, GRP_COUNTS, GRP_IN_RECS, GRP_IN_BYTES, GRP_NBUF };
+constexpr int GRP_NEV = 8;
+struct GroupState {
+    ScanBuf buf[GRP_NBUF]; hipEvent_t ev[GRP_NEV]{}; bool evReady = false;
+    int64_t n = 0; uint64_t nameBytes = 0; double msAppend = 0;
+    bool ok = true;                 // false: a round could not be appended (allocation, 2^31 descriptors): the sample is not grouped here
+};
 struct hlala_inflater {
     int device = 0; size_t chunk = 0, outCap = 0; int64_t maxBlocks = 0;
     InflateSlot slot[3];
     ScanBuf scan[SCAN_NBUF]; hipEvent_t scanEv[SCAN_NEV]{}; bool scanEvReady = false;
     size_t roundBytes = 0;          // bytes of the decoder's last round in scan[SCAN_DATA] (hlala_host::bam_scan_round: their tail is the next round's carry)
+    GroupState grp;
     std::string err;
 };
 static thread_local std::string g_inflater_create_error;
@@ -2372,6 +2383,8 @@ extern "C" void hlala_inflater_destroy(hlala_inflater* f)
     }
     for(ScanBuf& b : f->scan) if(b.p) (void)hipFree(b.p);
     for(hipEvent_t e : f->scanEv) if(e) (void)hipEventDestroy(e);
+    for(ScanBuf& b : f->grp.buf) if(b.p) (void)hipFree(b.p);
+    for(hipEvent_t e : f->grp.ev) if(e) (void)hipEventDestroy(e);
     delete f;
 }
 extern "C" int hlala_inflater_create(int32_t device, size_t chunk_bytes, hlala_inflater** out)
@@ -2538,11 +2551,12 @@ static int bam_inflate_hook(void* inflater, const uint8_t* comp, size_t comp_byt
     return bam_inflate_crc_hook(inflater, comp, comp_bytes, blocks, n, out, out_bytes, status, landed, user, nullptr, err);
 }
 static int bam_scan_hook(void* inflater, hlala_host::bam_scan_round* R, std::string* err);      // (behind hlala_bam_scan, below)
+static int bam_group_hook(void* inflater, int64_t n, int32_t long_read_mode, uint32_t* perm, uint8_t* flag, hlala_bam_group_stats* stats, bool* available, std::string* err);      // (behind hlala_bam_group, below)
 extern "C" int hlala_bam_extract_seeds_gpu(hlala_inflater* f, const char* path, int32_t n_intervals, const hlala_bam_interval* iv, int32_t long_read_mode, int32_t n_threads, int32_t flags,
                                            hlala_seed_batch** out)
 {
     static std::once_flag hookOnce;                  // (samples may decode on several threads)
-    std::call_once(hookOnce, []() { hlala_host::g_bam_inflate_hook = bam_inflate_hook; hlala_host::g_bam_inflate_crc_hook = bam_inflate_crc_hook; hlala_host::g_bam_scan_hook = bam_scan_hook; });
+    std::call_once(hookOnce, []() { hlala_host::g_bam_inflate_hook = bam_inflate_hook; hlala_host::g_bam_inflate_crc_hook = bam_inflate_crc_hook; hlala_host::g_bam_scan_hook = bam_scan_hook; hlala_host::g_bam_group_hook = bam_group_hook; });
     return hlala_host::bam_extract_seeds_impl(path, n_intervals, iv, long_read_mode, n_threads, flags, true, f, out);
 }
 
@@ -2670,6 +2684,8 @@ extern "C" int hlala_bam_scan(hlala_inflater* f, const uint8_t* data, size_t n, 
     uint8_t none = 0;
     return scan_run(f, n ? data : &none, n, first, last, in, sink, stats);
 }
+static void group_reset(hlala_inflater* f);
+static int group_append(hlala_inflater* f, const hlala_bam_rec* dRecs, int64_t n, const uint8_t* dBytes, size_t nBytes);
 // One round of the decoder with HLALA_SEEDS_GPU_PARSE (hlala_host::bam_scan_round): carry to the front, inflate into the device round buffer, the record pass on it.
 static int bam_scan_hook(void* inflater, hlala_host::bam_scan_round* R, std::string* err)
 {
@@ -2729,7 +2745,197 @@ static int bam_scan_hook(void* inflater, hlala_host::bam_scan_round* R, std::str
         if(n && (e = hipMemcpy(fb, dData, n, hipMemcpyDeviceToHost)) != hipSuccess) return failed("download of the round");
         R->fell_back = true; R->bytes_d2h += (int64_t)n;
     }
+    // HLALA_SEEDS_GPU_GROUP: the round's descriptors and names join the sample-long arrays while both still stand in the scan's device buffers
+    R->group_appended = false;
+    if(R->group) {
+        if(R->group_first) group_reset(f);
+        if(R->stats.status == HLALA_BAMSCAN_OK && f->grp.ok) {
+            rc = R->stats.n_recs ? group_append(f, (const hlala_bam_rec*)f->scan[SCAN_RECS].p, R->stats.n_recs, (const uint8_t*)f->scan[SCAN_COMPACT].p, (size_t)R->stats.compact_bytes) : HLALA_OK;
+            if(rc != HLALA_OK) return out(rc);
+            R->group_appended = f->grp.ok;
+        } else f->grp.ok = false;
+    }
     R->s_scan = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
+    return HLALA_OK;
+}
+
+// ---- grouping by read name (include/hlala_gpu.h; kernel_bamgroup.hip).  Append per round on the scan's stream; after the last round one stretch of that stream: sort, mark,
+// run ids, fold, emit, download.  The host looks at the device twice per round (how many name bytes the round brings: the arena may have to grow) and once at the end.
+static void group_reset(hlala_inflater* f) { f->grp.n = 0; f->grp.nameBytes = 0; f->grp.msAppend = 0; f->grp.ok = true; }
+// `keep` bytes of the old buffer survive (device to device); the stream is idle when the old buffer is freed
+static hipError_t group_grow(hlala_inflater* f, int which, size_t bytes, size_t keep, hipStream_t st)
+{
+    ScanBuf& b = f->grp.buf[which];
+    if(bytes <= b.cap) return hipSuccess;
+    const size_t want = keep ? 2 * bytes + 256 : bytes + bytes / 4 + 256;
+    void* p = nullptr;
+    hipError_t r = hipMalloc(&p, want);
+    if(r != hipSuccess) return r;
+    if(keep && b.p) { r = hipMemcpyAsync(p, b.p, keep, hipMemcpyDeviceToDevice, st); if(r == hipSuccess) r = hipStreamSynchronize(st); if(r != hipSuccess) { (void)hipFree(p); return r; } }
+    if(b.p) (void)hipFree(b.p);
+    b.p = p; b.cap = want;
+    return hipSuccess;
+}
+static hipError_t group_events(hlala_inflater* f)
+{
+    if(f->grp.evReady) return hipSuccess;
+    for(hipEvent_t& ev : f->grp.ev) if(!ev) { const hipError_t e = hipEventCreate(&ev); if(e != hipSuccess) return e; }
+    f->grp.evReady = true;
+    return hipSuccess;
+}
+// n (> 0) descriptors in device memory, their names in dBytes[0, nBytes), appended.  An allocation that fails is no error of the call: grp.ok = false, the caller decides.
+static int group_append(hlala_inflater* f, const hlala_bam_rec* dRecs, int64_t n, const uint8_t* dBytes, size_t nBytes)
+{
+    GroupState& G = f->grp;
+    if(G.n + n >= ((int64_t)1 << 31)) { G.ok = false; return HLALA_OK; }
+    DevGuard g(f->device);
+    hipStream_t st = f->slot[0].stream;
+    hipError_t e = hipSuccess;
+    auto failed = [&](const char* what) { f->err = std::string("BAM grouping: ") + what + ": " + hipGetErrorString(e); (void)hipStreamSynchronize(st); (void)hipGetLastError(); return HLALA_E_DEVICE; };
+    auto no_memory = [&]() { (void)hipGetLastError(); G.ok = false; return HLALA_OK; };
+    if((e = group_events(f)) != hipSuccess) return failed("hipEventCreate");
+    const u32 N = (u32)n, nb = (N + 63u) / 64u, nb1 = (N + 64u) / 64u;
+    size_t cubBytes = 0;
+    if((e = group_grow(f, GRP_LEN, ((size_t)N + 1) * 8, 0, st)) != hipSuccess || (e = group_grow(f, GRP_OFF, ((size_t)N + 1) * 8, 0, st)) != hipSuccess) return no_memory();
+    u64* dLen = (u64*)G.buf[GRP_LEN].p; u64* dOff = (u64*)G.buf[GRP_OFF].p;
+    if((e = hipcub::DeviceScan::ExclusiveSum(nullptr, cubBytes, dLen, dOff, (int)N, st)) != hipSuccess) return failed("hipcub::DeviceScan::ExclusiveSum");
+    if((e = group_grow(f, GRP_CUB, cubBytes + 16, 0, st)) != hipSuccess) return no_memory();
+    e = hipEventRecord(G.ev[0], st);
+    if(e == hipSuccess) { hipLaunchKernelGGL(k_grp_len, dim3(nb1), dim3(64), 0, st, dRecs, N, dLen); e = hipGetLastError(); }
+    if(e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(G.buf[GRP_CUB].p, cubBytes, dLen, dOff, (int)N, st);
+    u64 last[2] = {0, 0};
+    if(e == hipSuccess) e = hipMemcpyAsync(&last[0], dOff + (N - 1), 8, hipMemcpyDeviceToHost, st);
+    if(e == hipSuccess) e = hipMemcpyAsync(&last[1], dLen + (N - 1), 8, hipMemcpyDeviceToHost, st);
+    if(e == hipSuccess) e = hipStreamSynchronize(st);
+    if(e != hipSuccess) return failed("k_grp_len / the scan of the name lengths");
+    const u64 roundNames = last[0] + last[1];
+    if(roundNames > (u64)N * 65535u) { f->err = "BAM grouping: more name bytes than the descriptors can hold"; return HLALA_E_DEVICE; }      // (cannot happen)
+    const size_t have = (size_t)G.n, total = have + (size_t)N;
+    if((e = group_grow(f, GRP_HASH, total * 8, have * 8, st)) != hipSuccess || (e = group_grow(f, GRP_META, total * 4, have * 4, st)) != hipSuccess ||
+       (e = group_grow(f, GRP_NAMEOFF, total * 8, have * 8, st)) != hipSuccess || (e = group_grow(f, GRP_NAMES, (size_t)(G.nameBytes + roundNames) + 1, (size_t)G.nameBytes, st)) != hipSuccess) return no_memory();
+    hipLaunchKernelGGL(k_grp_append, dim3(nb), dim3(64), 0, st, dRecs, N, dBytes, (u64)nBytes, (const u64*)dOff, (u64)G.nameBytes, (u64*)G.buf[GRP_HASH].p + have, (u32*)G.buf[GRP_META].p + have,
+                       (u64*)G.buf[GRP_NAMEOFF].p + have, (uint8_t*)G.buf[GRP_NAMES].p, (u64)(G.nameBytes + roundNames));
+    e = hipGetLastError();
+    if(e == hipSuccess) e = hipEventRecord(G.ev[1], st);
+    if(e == hipSuccess) e = hipStreamSynchronize(st);
+    if(e != hipSuccess) return failed("k_grp_append");
+    { float t = 0; if(hipEventElapsedTime(&t, G.ev[0], G.ev[1]) == hipSuccess) G.msAppend += (double)t; }
+    G.n = (int64_t)total; G.nameBytes += roundNames;
+    return HLALA_OK;
+}
+// the passes over the G.n (> 0) appended descriptors; perm / flag are host memory.  *noMemory: a device allocation failed, nothing ran.
+static int group_finish(hlala_inflater* f, int32_t long_read_mode, uint32_t* perm, uint8_t* flag, hlala_bam_group_stats* stats, bool* noMemory)
+{
+    GroupState& G = f->grp;
+    *noMemory = false;
+    DevGuard g(f->device);
+    hipStream_t st = f->slot[0].stream;
+    hipError_t e = hipSuccess;
+    auto failed = [&](const char* what) { f->err = std::string("BAM grouping: ") + what + ": " + hipGetErrorString(e); (void)hipStreamSynchronize(st); (void)hipGetLastError(); return HLALA_E_DEVICE; };
+    if((e = group_events(f)) != hipSuccess) return failed("hipEventCreate");
+    const u32 N = (u32)G.n, nb = (N + 63u) / 64u, nb1 = (N + 64u) / 64u;
+    const u64* dHash = (const u64*)G.buf[GRP_HASH].p; const u32* dMeta = (const u32*)G.buf[GRP_META].p; const u64* dNameOff = (const u64*)G.buf[GRP_NAMEOFF].p; const uint8_t* dNames = (const uint8_t*)G.buf[GRP_NAMES].p;
+    size_t cubSort = 0, cubScan = 0;
+    if((e = hipcub::DeviceRadixSort::SortPairs(nullptr, cubSort, dHash, (u64*)nullptr, (const u32*)nullptr, (u32*)nullptr, (int)N, 0, 64, st)) != hipSuccess) return failed("hipcub::DeviceRadixSort::SortPairs");
+    if((e = hipcub::DeviceScan::ExclusiveSum(nullptr, cubScan, (u32*)nullptr, (u32*)nullptr, (int)N, st)) != hipSuccess) return failed("hipcub::DeviceScan::ExclusiveSum");
+    if((e = group_grow(f, GRP_CUB, std::max(cubSort, cubScan) + 16, 0, st)) != hipSuccess || (e = group_grow(f, GRP_KEYS, (size_t)N * 8, 0, st)) != hipSuccess ||
+       (e = group_grow(f, GRP_VAL_IN, (size_t)N * 4, 0, st)) != hipSuccess || (e = group_grow(f, GRP_VAL_OUT, (size_t)N * 4, 0, st)) != hipSuccess ||
+       (e = group_grow(f, GRP_START, ((size_t)N + 1) * 4, 0, st)) != hipSuccess || (e = group_grow(f, GRP_RUNOFF, ((size_t)N + 1) * 4, 0, st)) != hipSuccess ||
+       (e = group_grow(f, GRP_NEQ, (size_t)N, 0, st)) != hipSuccess || (e = group_grow(f, GRP_WORD, (size_t)N * 4, 0, st)) != hipSuccess || (e = group_grow(f, GRP_FLAG, (size_t)N, 0, st)) != hipSuccess ||
+       (e = group_grow(f, GRP_COUNTS, 3 * 8, 0, st)) != hipSuccess) { (void)hipGetLastError(); *noMemory = true; return HLALA_OK; }
+    u64* dKeys = (u64*)G.buf[GRP_KEYS].p; u32* dVin = (u32*)G.buf[GRP_VAL_IN].p; u32* dPerm = (u32*)G.buf[GRP_VAL_OUT].p; u32* dStart = (u32*)G.buf[GRP_START].p; u32* dRunOff = (u32*)G.buf[GRP_RUNOFF].p;
+    uint8_t* dNeq = (uint8_t*)G.buf[GRP_NEQ].p; u32* dWord = (u32*)G.buf[GRP_WORD].p; uint8_t* dFlag = (uint8_t*)G.buf[GRP_FLAG].p; unsigned long long* dCounts = (unsigned long long*)G.buf[GRP_COUNTS].p;
+    hipEvent_t* ev = G.ev;
+    auto ms = [&](int a, int b) { float t = 0; return hipEventElapsedTime(&t, ev[a], ev[b]) == hipSuccess ? (double)t : 0.0; };
+    e = hipEventRecord(ev[2], st);
+    if(e == hipSuccess) { hipLaunchKernelGGL(k_grp_iota, dim3(nb), dim3(64), 0, st, N, dVin); e = hipGetLastError(); }
+    if(e == hipSuccess) e = hipcub::DeviceRadixSort::SortPairs(G.buf[GRP_CUB].p, cubSort, dHash, dKeys, (const u32*)dVin, dPerm, (int)N, 0, 64, st);
+    if(e == hipSuccess) e = hipEventRecord(ev[3], st);
+    if(e == hipSuccess) { hipLaunchKernelGGL(k_grp_mark, dim3(nb1), dim3(64), 0, st, N, (const u64*)dKeys, (const u32*)dPerm, dMeta, dNameOff, dNames, (u64)G.nameBytes, dStart, dNeq); e = hipGetLastError(); }
+    if(e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(G.buf[GRP_CUB].p, cubScan, dStart, dRunOff, (int)N, st);
+    if(e == hipSuccess) e = hipEventRecord(ev[4], st);
+    if(e == hipSuccess) e = hipMemsetAsync(dWord, 0, (size_t)N * 4, st);
+    if(e == hipSuccess) e = hipMemsetAsync(dCounts, 0, 3 * 8, st);
+    if(e == hipSuccess) { hipLaunchKernelGGL(k_grp_fold, dim3(nb), dim3(64), 0, st, N, (const u32*)dPerm, dMeta, (const u32*)dStart, (const u32*)dRunOff, (const uint8_t*)dNeq, dWord); e = hipGetLastError(); }
+    if(e == hipSuccess) e = hipEventRecord(ev[5], st);
+    if(e == hipSuccess) { hipLaunchKernelGGL(k_grp_emit, dim3(nb), dim3(64), 0, st, N, (const u32*)dStart, (const u32*)dRunOff, (const u32*)dWord, (int)(long_read_mode ? 1 : 0), dFlag, dCounts); e = hipGetLastError(); }
+    if(e == hipSuccess) e = hipEventRecord(ev[6], st);
+    unsigned long long hCounts[3] = {0, 0, 0}; u32 lastRun[2] = {0, 0};
+    if(e == hipSuccess) e = hipMemcpyAsync(perm, dPerm, (size_t)N * 4, hipMemcpyDeviceToHost, st);
+    if(e == hipSuccess) e = hipMemcpyAsync(flag, dFlag, (size_t)N, hipMemcpyDeviceToHost, st);
+    if(e == hipSuccess) e = hipMemcpyAsync(hCounts, dCounts, sizeof(hCounts), hipMemcpyDeviceToHost, st);
+    if(e == hipSuccess) e = hipMemcpyAsync(&lastRun[0], dRunOff + (N - 1), 4, hipMemcpyDeviceToHost, st);
+    if(e == hipSuccess) e = hipMemcpyAsync(&lastRun[1], dStart + (N - 1), 4, hipMemcpyDeviceToHost, st);
+    if(e == hipSuccess) e = hipEventRecord(ev[7], st);
+    if(e == hipSuccess) e = hipStreamSynchronize(st);
+    if(e != hipSuccess) return failed("sort / k_grp_mark / k_grp_fold / k_grp_emit / download");
+    stats->n_recs = G.n; stats->n_runs = (int64_t)lastRun[0] + lastRun[1]; stats->n_collided_runs = (int64_t)hCounts[0]; stats->n_units_complete = (int64_t)hCounts[1]; stats->n_units_incomplete = (int64_t)hCounts[2];
+    stats->ms_append = G.msAppend; stats->ms_sort = ms(2, 3); stats->ms_mark = ms(3, 4); stats->ms_fold = ms(4, 5); stats->ms_emit = ms(5, 6); stats->ms_d2h = ms(6, 7);
+    return HLALA_OK;
+}
+extern "C" int hlala_bam_group_rounds(hlala_inflater* f, const hlala_bam_rec* recs, int64_t n, const uint8_t* bytes, size_t n_bytes, const int64_t* round_recs, int32_t n_rounds,
+                                      int32_t long_read_mode, uint32_t* perm, uint8_t* flag, hlala_bam_group_stats* stats)
+{
+    if(!f) { int ndev = 0; if(hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return HLALA_E_DEVICE; } return HLALA_E_ARG; }
+    f->err.clear();
+    const char* bad = hlala_bamgroup::grp_check_args(recs, n, bytes, n_bytes, perm, flag, stats);
+    if(!bad) bad = hlala_bamgroup::grp_check_rounds(round_recs, n_rounds, n);
+    if(bad) { f->err = std::string("hlala_bam_group: ") + bad; return HLALA_E_ARG; }
+    const auto tWall = std::chrono::steady_clock::now();
+    memset(stats, 0, sizeof(*stats));
+    group_reset(f);
+    if(n == 0) return HLALA_OK;
+    DevGuard g(f->device);
+    hipStream_t st = f->slot[0].stream;
+    hipError_t e = hipSuccess;
+    auto failed = [&](const char* what) { f->err = std::string("hlala_bam_group: ") + what + ": " + hipGetErrorString(e); (void)hipStreamSynchronize(st); (void)hipGetLastError(); return HLALA_E_DEVICE; };
+    if((e = group_events(f)) != hipSuccess) return failed("hipEventCreate");
+    if((e = group_grow(f, GRP_IN_RECS, (size_t)n * sizeof(hlala_bam_rec), 0, st)) != hipSuccess || (e = group_grow(f, GRP_IN_BYTES, n_bytes ? n_bytes : 1, 0, st)) != hipSuccess) return failed("hipMalloc");
+    const hlala_bam_rec* dRecs = (const hlala_bam_rec*)f->grp.buf[GRP_IN_RECS].p; const uint8_t* dBytes = (const uint8_t*)f->grp.buf[GRP_IN_BYTES].p;
+    e = hipEventRecord(f->grp.ev[2], st);
+    if(e == hipSuccess) e = hipMemcpyAsync((void*)dRecs, recs, (size_t)n * sizeof(hlala_bam_rec), hipMemcpyHostToDevice, st);
+    if(e == hipSuccess && n_bytes) e = hipMemcpyAsync((void*)dBytes, bytes, n_bytes, hipMemcpyHostToDevice, st);
+    if(e == hipSuccess) e = hipEventRecord(f->grp.ev[3], st);
+    if(e == hipSuccess) e = hipStreamSynchronize(st);
+    if(e != hipSuccess) return failed("upload");
+    float tUp = 0; (void)hipEventElapsedTime(&tUp, f->grp.ev[2], f->grp.ev[3]);
+    int64_t at = 0;
+    for(int32_t k = 0; k < n_rounds; k++) {
+        if(round_recs[k] == 0) continue;
+        const int rc = group_append(f, dRecs + at, round_recs[k], dBytes, n_bytes);
+        if(rc != HLALA_OK) return rc;
+        if(!f->grp.ok) { f->err = "hlala_bam_group: no device memory for the sample-long arrays"; return HLALA_E_DEVICE; }
+        at += round_recs[k];
+    }
+    bool noMemory = false;
+    const int rc = group_finish(f, long_read_mode, perm, flag, stats, &noMemory);
+    if(rc != HLALA_OK) return rc;
+    if(noMemory) { f->err = "hlala_bam_group: no device memory for the passes"; return HLALA_E_DEVICE; }
+    stats->ms_h2d = (double)tUp;
+    stats->ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tWall).count();
+    return HLALA_OK;
+}
+extern "C" int hlala_bam_group(hlala_inflater* f, const hlala_bam_rec* recs, int64_t n, const uint8_t* bytes, size_t n_bytes, int32_t long_read_mode, uint32_t* perm, uint8_t* flag,
+                               hlala_bam_group_stats* stats)
+{
+    const int64_t one = n;
+    return hlala_bam_group_rounds(f, recs, n, bytes, n_bytes, &one, n > 0 ? 1 : 0, long_read_mode, perm, flag, stats);
+}
+// The decoder's group phase with HLALA_SEEDS_GPU_GROUP: the passes over what the scan hook has appended round by round.
+static int bam_group_hook(void* inflater, int64_t n, int32_t long_read_mode, uint32_t* perm, uint8_t* flag, hlala_bam_group_stats* stats, bool* available, std::string* err)
+{
+    hlala_inflater* f = (hlala_inflater*)inflater;
+    if(!f || !stats || !available || n < 0 || (n && (!perm || !flag))) return HLALA_E_ARG;
+    f->err.clear();
+    memset(stats, 0, sizeof(*stats));
+    *available = f->grp.ok && f->grp.n == n;
+    if(!*available || n == 0) return HLALA_OK;
+    const auto tWall = std::chrono::steady_clock::now();
+    bool noMemory = false;
+    const int rc = group_finish(f, long_read_mode, perm, flag, stats, &noMemory);
+    if(rc != HLALA_OK) { if(err) *err = f->err; return rc; }
+    if(noMemory) *available = false;
+    stats->ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tWall).count();
     return HLALA_OK;
 }
 
@@ -2739,7 +2945,7 @@ extern "C" int hlala_abi_sizeof(const char* name)
     const std::string n(name);
 #define SZ(t) if(n == #t) return (int)sizeof(t);
     SZ(hlala_graph_desc) SZ(hlala_contigs_desc) SZ(hlala_params) SZ(hlala_graph_info) SZ(hlala_batch_in) SZ(hlala_seeds_in)
-    SZ(hlala_chains_out) SZ(hlala_pairs_out) SZ(hlala_batch_stats) SZ(hlala_exon_in) SZ(hlala_call_out) SZ(hlala_locus_desc) SZ(hlala_exon_positions_out) SZ(hlala_filter_params) SZ(hlala_filter_stats) SZ(hlala_insert_size_out) SZ(hlala_locus_info) SZ(hlala_locus_report_in) SZ(hlala_locus_report_out) SZ(hlala_unit_stats_out) SZ(hlala_pairs_packed_out) SZ(hlala_bgzf_block) SZ(hlala_inflate_stats) SZ(hlala_bam_rec) SZ(hlala_bam_scan_in) SZ(hlala_bam_scan_stats)
+    SZ(hlala_chains_out) SZ(hlala_pairs_out) SZ(hlala_batch_stats) SZ(hlala_exon_in) SZ(hlala_call_out) SZ(hlala_locus_desc) SZ(hlala_exon_positions_out) SZ(hlala_filter_params) SZ(hlala_filter_stats) SZ(hlala_insert_size_out) SZ(hlala_locus_info) SZ(hlala_locus_report_in) SZ(hlala_locus_report_out) SZ(hlala_unit_stats_out) SZ(hlala_pairs_packed_out) SZ(hlala_bgzf_block) SZ(hlala_inflate_stats) SZ(hlala_bam_rec) SZ(hlala_bam_scan_in) SZ(hlala_bam_scan_stats) SZ(hlala_bam_group_stats)
 #undef SZ
     return -1;
 }

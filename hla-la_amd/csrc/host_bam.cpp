@@ -241,6 +241,7 @@ struct hlala_seed_batch {
     int64_t crc_counts[3] = {0, 0, 0};          // HLALA_SEEDS_VERIFY_CRC: blocks verified on the GPU, on the host, reported as mismatching by the GPU and checked again on the host
     int64_t parse_counts[3] = {0, 0, 0};        // records scanned on the GPU, rounds scanned there, rounds that fell back to the host's hop and parse
     int64_t transfer_bytes[2] = {0, 0};         // bytes the GPU paths of the decoder moved to the device and back
+    int64_t group_counts[3] = {0, 0, 0};        // HLALA_SEEDS_GPU_GROUP: records grouped on the GPU, collided runs the host regrouped, 1 = the whole sample was grouped by the host instead
     bool pinned = false;
     // page-locking window by window (hlala_seed_batch_pin(S, 2)): per bulk array the bytes locked so far, and the regions to unlock
     bool pin_lazy = false; std::mutex pin_mu; std::vector<size_t> pin_cursor; std::vector<std::pair<void*, size_t>> pin_regions;
@@ -384,6 +385,7 @@ void (*g_seed_batch_unpin)(hlala_seed_batch*) = nullptr;       // set by the GPU
 bam_inflate_hook_t g_bam_inflate_hook = nullptr;               // set by the GPU library (hlala_bam_extract_seeds_gpu)
 bam_inflate_crc_hook_t g_bam_inflate_crc_hook = nullptr;       // ... (HLALA_SEEDS_VERIFY_CRC)
 bam_scan_hook_t g_bam_scan_hook = nullptr;                     // ... (HLALA_SEEDS_GPU_PARSE)
+bam_group_hook_t g_bam_group_hook = nullptr;                   // ... (HLALA_SEEDS_GPU_GROUP)
 }  // namespace hlala_host
 
 // (host code: no device involved)
@@ -457,16 +459,25 @@ struct GpuRound {
     }
 };
 // what the record pass of a round (hlala_host::bam_scan_round) calls back: the host engine for a rejected block, and where its outputs go
+// a round's descriptors as they come back from the device: not cleared, on huge pages where the kernel grants them (a vector of 48 bytes per descriptor is cleared
+// on one thread before the download overwrites it, and unmapped page by page when it goes)
+struct DescBuf {
+    std::unique_ptr<uint8_t, BigFree> p; size_t n = 0;
+    void alloc(size_t k) { p.reset(big_alloc(k * sizeof(hlala_bam_rec))); n = k; }
+    size_t size() const { return n; }
+    hlala_bam_rec* data() { return (hlala_bam_rec*)p.get(); }
+    const hlala_bam_rec& operator[](size_t i) const { return ((const hlala_bam_rec*)p.get())[i]; }
+};
 struct ScanRound {
     const Block* blocks; const uint8_t* comp; Inflater* host; bool verifyCrc; std::exception_ptr err;
-    std::vector<hlala_bam_rec> recs; std::unique_ptr<uint8_t, BigFree> compact, fallback;
+    DescBuf recs; std::unique_ptr<uint8_t, BigFree> compact, fallback;
     static int host_inflate(void* user, int64_t k, uint8_t* out)
     {
         ScanRound& R = *(ScanRound*)user;
         try { const Block& b = R.blocks[k]; if(R.verifyCrc) R.host->run_checked(R.comp + b.coff, b.clen, out, b.isize, b.crc); else R.host->run(R.comp + b.coff, b.clen, out, b.isize); } catch(...) { R.err = std::current_exception(); return 1; }
         return 0;
     }
-    static hlala_bam_rec* alloc_recs(void* user, int64_t n) { ScanRound& R = *(ScanRound*)user; try { R.recs.resize((size_t)n); } catch(...) { R.err = std::current_exception(); return nullptr; } return R.recs.data(); }
+    static hlala_bam_rec* alloc_recs(void* user, int64_t n) { ScanRound& R = *(ScanRound*)user; try { R.recs.alloc((size_t)n); } catch(...) { R.err = std::current_exception(); return nullptr; } return R.recs.data(); }
     static uint8_t* alloc_compact(void* user, size_t n) { ScanRound& R = *(ScanRound*)user; try { R.compact.reset(big_alloc(n)); } catch(...) { R.err = std::current_exception(); return nullptr; } return R.compact.get(); }
     static uint8_t* alloc_fallback(void* user, size_t n) { ScanRound& R = *(ScanRound*)user; try { R.fallback.reset(big_alloc(n)); } catch(...) { R.err = std::current_exception(); return nullptr; } return R.fallback.get(); }
 };
@@ -480,6 +491,8 @@ try {
     const bool gpuParse = (flags & HLALA_SEEDS_GPU_PARSE) != 0, verifyCrc = (flags & HLALA_SEEDS_VERIFY_CRC) != 0;
     if(gpu && verifyCrc && !gpuParse && !g_bam_inflate_crc_hook) { g_bam_error = "HLALA_SEEDS_VERIFY_CRC: this library's GPU inflate has no CRC kernel"; return HLALA_E_ARG; }
     if(gpuParse && (!gpu || !g_bam_scan_hook)) { g_bam_error = "HLALA_SEEDS_GPU_PARSE needs hlala_bam_extract_seeds_gpu"; return HLALA_E_ARG; }
+    const bool gpuGroup = (flags & HLALA_SEEDS_GPU_GROUP) != 0;
+    if(gpuGroup && (!gpuParse || !g_bam_group_hook)) { g_bam_error = "HLALA_SEEDS_GPU_GROUP needs HLALA_SEEDS_GPU_PARSE"; return HLALA_E_ARG; }
     int T = n_threads;
     // Default: at most 32 threads.  Measured on a 256-thread host (tools/gpu_decode_threads.sh, 8.4 M pairs, 2.6 GB of BAM): 5.2 s on 8 threads, 3.5 on 16, 2.85 on 32,
     // 3.0 on 64, 3.3-3.7 on 128 -- the phases are passes over ~12 GB of inflated records bound by memory latency and by the first touch of their
@@ -585,6 +598,25 @@ try {
         // (tests: HLALA_BAM_SCAN_MAX_REHOPS=k caps the re-hops of a round's k_bam_link; 0 makes any wrong guess a fall-back to the host's hop and parse)
         if(const char* e = getenv("HLALA_BAM_SCAN_MAX_REHOPS")) { const int k = atoi(e); scanMaxRehops = k <= 0 ? -1 : k; }
     }
+    auto to_rec = [](const hlala_bam_rec& x, const uint8_t* cb) {
+        Rec r; r.hash = x.hash; r.order = x.order; r.rec = cb + x.rec_off; r.contig = x.contig; r.pos = x.pos; r.as = x.as; r.l_seq = x.l_seq;
+        r.n_cigar = x.n_cigar; r.nameLen = x.nameLen; r.which = x.which; r.flags = x.flags; r.l_read_name = x.l_read_name; r.pad1 = 0;
+        return r;
+    };
+    // the descriptors of a round become records of the 256 name partitions
+    auto scatter = [&](const DescBuf& D, const uint8_t* cb) {
+        const int64_t DCH = 8192, nDT = ((int64_t)D.size() + DCH - 1) / DCH;
+        parallel_for(nDT, T, [&](int64_t task, int t) {
+            Arena& A = arenas[(size_t)t];
+            const size_t a = (size_t)(task * DCH), z = std::min(D.size(), a + (size_t)DCH);
+            for(size_t i = a; i < z; i++) A.part[(size_t)(D[i].hash >> 56)].push_back(to_rec(D[i], cb));
+        });
+    };
+    // HLALA_SEEDS_GPU_GROUP: the rounds' descriptors are kept as they came (the device has appended them to its own arrays); should the device be unable to group the
+    // sample after all, they are scattered then, and the host groups as ever
+    struct KeptRound { DescBuf recs; const uint8_t* cb; };
+    std::vector<KeptRound> kept; bool groupOnGpu = gpuGroup;
+    auto give_up_gpu_group = [&]() { groupOnGpu = false; for(KeptRound& k : kept) scatter(k.recs, k.cb); std::vector<KeptRound>().swap(kept); };
     for(size_t b0 = 0; b0 < blocks.size();) {
         size_t b1 = b0; size_t segBytes = 0;
         while(b1 < blocks.size() && (segBytes == 0 || segBytes + blocks[b1].isize <= SEG_BYTES)) { segBytes += blocks[b1].isize; b1++; }
@@ -608,6 +640,7 @@ try {
             bam_scan_round R; memset((void*)&R, 0, sizeof(R));
             R.comp = mf.p; R.comp_bytes = mf.n; R.blocks = desc.data(); R.n_blocks = (int64_t)nBlk; R.seg_bytes = segBytes; R.carry = carry; R.first = b0 == 0 ? firstRecord : 0; R.last = lastSegment ? 1 : 0; R.in = &sin; R.crc_expect = verifyCrc ? crcExpect.data() : nullptr;
             R.user = &U; R.host_inflate = ScanRound::host_inflate; R.alloc_recs = ScanRound::alloc_recs; R.alloc_compact = ScanRound::alloc_compact; R.alloc_fallback = ScanRound::alloc_fallback;
+            R.group = groupOnGpu ? 1 : 0; R.group_first = b0 == 0 ? 1 : 0;
             std::string herr;
             const int rc = g_bam_scan_hook(gpuInflater, &R, &herr);
             if(U.err) std::rethrow_exception(U.err);
@@ -619,18 +652,12 @@ try {
                 if(R.stats.status != HLALA_BAMSCAN_OK) throw Fail(hlala_bam_scan_status_text(R.stats.status));
                 const uint8_t* cb = U.compact.get();
                 if(U.compact) W->inflated.emplace_back(std::move(U.compact));                       // the compact buffer takes the place of the round's buffer: the Recs point into it
-                const std::vector<hlala_bam_rec>& D = U.recs;
-                const int64_t DCH = 8192, nDT = ((int64_t)D.size() + DCH - 1) / DCH;
-                parallel_for(nDT, T, [&](int64_t task, int t) {
-                    Arena& A = arenas[(size_t)t];
-                    const size_t a = (size_t)(task * DCH), z = std::min(D.size(), a + (size_t)DCH);
-                    for(size_t i = a; i < z; i++) {
-                        const hlala_bam_rec& x = D[i];
-                        Rec r; r.hash = x.hash; r.order = x.order; r.rec = cb + x.rec_off; r.contig = x.contig; r.pos = x.pos; r.as = x.as; r.l_seq = x.l_seq;
-                        r.n_cigar = x.n_cigar; r.nameLen = x.nameLen; r.which = x.which; r.flags = x.flags; r.l_read_name = x.l_read_name; r.pad1 = 0;
-                        A.part[(size_t)(x.hash >> 56)].push_back(r);
-                    }
-                });
+                if(groupOnGpu) {
+                    bool keep = R.group_appended;
+                    for(size_t i = 0; keep && i < U.recs.size(); i++) keep = U.recs[i].nameLen != 0;       // (a name without a byte: hlala_bam_group takes none; the host does)
+                    if(keep) kept.push_back(KeptRound{std::move(U.recs), cb}); else give_up_gpu_group();
+                }
+                if(!groupOnGpu) scatter(U.recs, cb);
                 arenas[0].examined += R.stats.examined;
                 recSeq += (uint64_t)R.stats.n_records;
                 scanned = true; scanConsumed = (size_t)R.stats.consumed;
@@ -638,6 +665,7 @@ try {
             } else {
                 // more wrong guesses than one wavefront should mend: this round's bytes have come back, the host hops and parses them as ever
                 S->parse_counts[2]++;
+                if(groupOnGpu) give_up_gpu_group();
                 W->inflated.emplace_back(std::move(U.fallback));
                 bufp = W->inflated.back().get();
             }
@@ -821,8 +849,86 @@ try {
     // Sorted by (hash, file order) on 24-byte integer keys; the NAMES are looked at once per record afterwards, in sorted order and prefetched (they lie in the
     // inflated file, a cache miss each: inside the sort's comparator they cost several misses per record).  Different names with one 64-bit hash -- never seen,
     // possible -- put the run they share into (name, file order) order, as before.
+    // HLALA_SEEDS_GPU_GROUP: the device sorts the descriptors it has collected by hash, compares every name with its neighbour's and says per run whether it is clean and
+    // complete (hlala_bam_group).  The host gathers the records through perm -- the partitions laid end to end, their bounds where the top byte of the hash changes --
+    // and builds its units by walking flag: no name is compared and no primary looked for in a clean run.  A collided run is put into (name, file order) order and
+    // split as below.
+    bool groupedOnGpu = false;
+    if(gpuGroup) {
+        size_t nDesc = 0; for(const KeptRound& k : kept) nDesc += k.recs.size();
+        double tHook = 0;
+        Buf<uint32_t> gperm; Buf<uint8_t> gflag;                       // (not cleared: the device's answer fills them)
+        if(groupOnGpu && nDesc >= ((size_t)1 << 31)) groupOnGpu = false;
+        if(groupOnGpu) {
+            gperm.alloc(nDesc); gflag.alloc(nDesc);
+            hlala_bam_group_stats gs; bool available = false; std::string herr;
+            const int rc = g_bam_group_hook(gpuInflater, (int64_t)nDesc, long_read_mode ? 1 : 0, gperm.data(), gflag.data(), &gs, &available, &herr);
+            if(rc != HLALA_OK) throw Fail("BAM grouping on the GPU failed: " + herr);
+            tHook = since(tPhase);
+            if(!available) groupOnGpu = false;
+            else if(getenv("HLALA_BAM_DEBUG")) fprintf(stderr, "bam-debug: grouping on the GPU: %lld records, %lld runs (%lld collided); append %.3f, sort %.3f, mark %.3f, fold %.3f, emit %.3f, download %.3f ms\n",
+                                                       (long long)gs.n_recs, (long long)gs.n_runs, (long long)gs.n_collided_runs, gs.ms_append, gs.ms_sort, gs.ms_mark, gs.ms_fold, gs.ms_emit, gs.ms_d2h);
+        }
+        if(!groupOnGpu) { give_up_gpu_group(); S->group_counts[2] = 1; }
+        else {
+            groupedOnGpu = true; S->group_counts[0] = (int64_t)nDesc;
+            std::vector<size_t> roundStart(kept.size() + 1, 0);
+            for(size_t k = 0; k < kept.size(); k++) roundStart[k + 1] = roundStart[k] + kept[k].recs.size();
+            auto desc_at = [&](uint32_t g, const uint8_t** cb) -> const hlala_bam_rec& {
+                if((size_t)g >= nDesc) throw Fail("BAM grouping on the GPU: a descriptor index beyond the sample");
+                const size_t k = (size_t)(std::upper_bound(roundStart.begin(), roundStart.end(), (size_t)g) - roundStart.begin()) - 1;
+                *cb = kept[k].cb; return kept[k].recs[(size_t)g - roundStart[k]];
+            };
+            std::vector<size_t> partStart(NPART + 1, nDesc);
+            for(int p = 0; p <= NPART; p++) {           // the first sorted record whose partition is p or beyond
+                size_t lo = 0, hi = nDesc;
+                while(lo < hi) { const size_t mid = (lo + hi) / 2; const uint8_t* cb; if((int)(desc_at(gperm[mid], &cb).hash >> 56) >= p) hi = mid; else lo = mid + 1; }
+                partStart[(size_t)p] = lo;
+            }
+            std::vector<int64_t> pCollided(NPART, 0);
+            parallel_for(NPART, T, [&](int64_t p, int) {
+                // the partition's records: one gather through perm (its pages are first touched here, by the thread that fills them)
+                std::vector<Rec>& R = precs[(size_t)p]; std::vector<Unit>& U = punits[(size_t)p];
+                const size_t base = partStart[(size_t)p], n = partStart[(size_t)p + 1] - base;
+                R.reserve(n);
+                for(size_t i = 0; i < n; i++) {
+                    if(i + 8 < n && (size_t)gperm[base + i + 8] < nDesc) { const uint8_t* cb8; __builtin_prefetch(&desc_at(gperm[base + i + 8], &cb8)); }
+                    const uint8_t* cb; const hlala_bam_rec& x = desc_at(gperm[base + i], &cb);
+                    if((int64_t)(x.hash >> 56) != p) throw Fail("BAM grouping on the GPU: records out of hash order");
+                    R.push_back(to_rec(x, cb));
+                }
+                auto same_name = [&](const Rec& a, const Rec& b) { return a.nameLen == b.nameLen && memcmp(rec_name(a), rec_name(b), a.nameLen) == 0; };
+                auto unit_of = [&](size_t i, size_t j, bool known, bool complete) {
+                    if(!known) { bool prim[2] = {false, false}; for(size_t k = i; k < j; k++) if(R[k].flags & 2) prim[R[k].which & 1] = true; complete = long_read_mode ? prim[0] : (prim[0] && prim[1]); }
+                    if(complete) { Unit u; u.name = rec_name(R[i]); u.nameLen = R[i].nameLen; u.part = (uint32_t)p; u.first = (uint32_t)i; u.count = (uint32_t)(j - i); U.push_back(u); }
+                    else pIncomplete[(size_t)p]++;
+                };
+                for(size_t i = 0; i < n;) {
+                    const uint8_t f = gflag[base + i];
+                    if(!(f & 1)) throw Fail("BAM grouping on the GPU: a run without a first record");
+                    size_t j = i + 1;
+                    while(j < n && !(gflag[base + j] & 1)) j++;
+                    if(f & 2) {
+                        pCollided[(size_t)p]++;
+                        std::sort(R.begin() + (ptrdiff_t)i, R.begin() + (ptrdiff_t)j, [&](const Rec& a, const Rec& b) {
+                            if(!same_name(a, b)) { const size_t m = a.nameLen < b.nameLen ? a.nameLen : b.nameLen; const int c = memcmp(rec_name(a), rec_name(b), m); return c != 0 ? c < 0 : a.nameLen < b.nameLen; }
+                            return a.order < b.order;
+                        });
+                        for(size_t a = i; a < j;) { size_t z = a + 1; while(z < j && same_name(R[z], R[z - 1])) z++; unit_of(a, z, false, false); a = z; }
+                    } else unit_of(i, j, true, (f & 4) != 0);
+                    i = j;
+                }
+            });
+            // (the descriptors, 48 bytes each, go with the working memory, which is released on a thread of its own once the sample is filled: unmapping them here costs
+            // more than gathering them did)
+            for(KeptRound& k : kept) if(k.recs.p) W->inflated.emplace_back(std::move(k.recs.p));
+            std::vector<KeptRound>().swap(kept);
+            for(int p = 0; p < NPART; p++) S->group_counts[1] += pCollided[(size_t)p];
+            if(getenv("HLALA_BAM_DEBUG")) fprintf(stderr, "bam-debug: grouping on the GPU: the hook and its buffers %.3f s of the group phase so far %.3f s (the rest: partition bounds, gather, units)\n", tHook, since(tPhase));
+        }
+    }
     struct Key { uint64_t hash, order; uint32_t idx; };
-    parallel_for(NPART, T, [&](int64_t p, int) {
+    if(!groupedOnGpu) parallel_for(NPART, T, [&](int64_t p, int) {
         std::vector<Rec>& R = precs[(size_t)p];
         size_t n = 0; for(const Arena& a : arenas) n += a.part[(size_t)p].size();
         if(n > 0xFFFFFFFFull) throw Fail("BAM too large: more than 2^32 records in one name partition");
@@ -1023,6 +1129,12 @@ extern "C" int hlala_seed_batch_parse_counts(const hlala_seed_batch* S, int64_t*
 {
     if(!S || !counts) return HLALA_E_ARG;
     for(int i = 0; i < 3; i++) counts[i] = S->parse_counts[i];
+    return HLALA_OK;
+}
+extern "C" int hlala_seed_batch_group_counts(const hlala_seed_batch* S, int64_t* counts)
+{
+    if(!S || !counts) return HLALA_E_ARG;
+    for(int i = 0; i < 3; i++) counts[i] = S->group_counts[i];
     return HLALA_OK;
 }
 extern "C" int hlala_seed_batch_transfer_bytes(const hlala_seed_batch* S, int64_t* bytes)

@@ -7,6 +7,7 @@
 #include "inflate_core.h"
 #include "crc32_core.h"
 #include "bam_scan_model.h"
+#include "bam_group_model.h"
 
 static thread_local std::string g_err;
 
@@ -103,6 +104,15 @@ int hlala_host_bam_scan_model(const uint8_t* data, size_t n, size_t first, int32
     const char* why = nullptr;
     const int rc = hlala_bamscan::scan_model(data, n, first, last, in, recs, cap_recs, compact, cap_compact, stats, &why);
     g_err = why ? std::string("hlala_host_bam_scan_model: ") + why : std::string();
+    return rc;
+}
+// The grouping passes of the device (kernel_bamgroup.hip) run serially over the same core (bam_group_model.h): the arguments, the return codes and every output of
+// hlala_bam_group but the device times, without a device.
+int hlala_host_bam_group_model(const hlala_bam_rec* recs, int64_t n, const uint8_t* bytes, size_t n_bytes, int32_t long_read_mode, uint32_t* perm, uint8_t* flag, hlala_bam_group_stats* stats)
+{
+    const char* why = nullptr;
+    const int rc = hlala_bamgroup::group_model(recs, n, bytes, n_bytes, long_read_mode, perm, flag, stats, &why);
+    g_err = why ? std::string("hlala_host_bam_group_model: ") + why : std::string();
     return rc;
 }
 }

@@ -60,11 +60,17 @@ struct bam_scan_round {
     hlala_bam_rec* (*alloc_recs)(void* user, int64_t n);
     uint8_t* (*alloc_compact)(void* user, size_t bytes);
     uint8_t* (*alloc_fallback)(void* user, size_t bytes);              // carry + seg_bytes
+    int32_t group, group_first;                                        // HLALA_SEEDS_GPU_GROUP: the round's descriptors are appended to the sample-long device arrays behind k_bam_emit (group_first: a new sample)
     // results
+    bool group_appended;                                               // false: they could not be (a device allocation failed, or the round fell back): the host groups the sample itself
     hlala_bam_scan_stats stats; int64_t n_gpu, n_retried, n_crc_recheck; bool fell_back; double s_inflate, s_scan; int64_t bytes_h2d, bytes_d2h;
 };
 typedef int (*bam_scan_hook_t)(void* inflater, bam_scan_round* R, std::string* err);
 extern bam_scan_hook_t g_bam_scan_hook;
+// The group phase on the GPU (HLALA_SEEDS_GPU_GROUP): the third hook.  After the last round: perm[n] / flag[n] of hlala_bam_group over the n descriptors the scan hook has
+// appended (in the order of the rounds).  *available = false (with HLALA_OK): the device holds another count or could not allocate -- the host groups the sample itself.
+typedef int (*bam_group_hook_t)(void* inflater, int64_t n, int32_t long_read_mode, uint32_t* perm, uint8_t* flag, hlala_bam_group_stats* stats, bool* available, std::string* err);
+extern bam_group_hook_t g_bam_group_hook;
 // hlala_bam_extract_seeds_opt (gpu = false) and hlala_bam_extract_seeds_gpu (gpu = true: the hook above inflates with `inflater`)
 int bam_extract_seeds_impl(const char* path, int32_t n_intervals, const hlala_bam_interval* iv, int32_t long_read_mode, int32_t n_threads, int32_t flags, bool gpu, void* inflater, hlala_seed_batch** out);
 

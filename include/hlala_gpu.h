@@ -594,6 +594,34 @@ int  hlala_seed_batch_parse_counts(const hlala_seed_batch* s, int64_t* counts);
  * bytes and the rounds that fell back) */
 int  hlala_seed_batch_transfer_bytes(const hlala_seed_batch* s, int64_t* bytes);
 
+/* ------------------------------------------------------------------------------------------
+ * Grouping BAM records by read name on the GPU (opt-in): the fourth stage of the GPU decode (csrc/kernel_bamgroup.hip; the rules are csrc/bam_group_core.h, which
+ * the host runs as a model).  The descriptors of a sample are put into (hash, order) order by a STABLE radix sort on the hash alone (they arrive in ascending
+ * order); a run is a maximal stretch of equal hashes; it is clean when every record has the name of its predecessor in the run, else collided; a clean run is one
+ * unit, complete when a primary record (flags & 2) exists for mate 0 and, unless long_read_mode, for mate 1.  k_grp_append copies hashes, flags and names into
+ * sample-long device arrays round by round; hipcub sorts; k_grp_mark, an exclusive sum, k_grp_fold and k_grp_emit do the rest, a lane per record.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct {
+    int64_t n_recs, n_runs, n_collided_runs, n_units_complete, n_units_incomplete;   /* the last two over clean runs only */
+    double ms_h2d, ms_append, ms_sort, ms_mark, ms_fold, ms_emit, ms_d2h, ms_wall;
+} hlala_bam_group_stats;
+/* recs[n] in ascending order, names at bytes[rec_off + 32 .. + nameLen).  perm[n]: descriptor indices in (hash, order) order.
+ * flag[n], of the sorted record i: 1 = first of its run, 2 = (on a run's first record) the run is collided, 4 = (on a clean run's first record) the unit is complete.
+ * Checked before anything is uploaded (HLALA_E_ARG; hlala_inflater_last_error says which): n >= 2^31, a name that leaves the byte buffer, nameLen 0, a mate
+ * other than 0 / 1, descriptors that are not in ascending order.  HLALA_E_DEVICE without a GPU (no inflater exists then). */
+int  hlala_bam_group(hlala_inflater* inf, const hlala_bam_rec* recs, int64_t n, const uint8_t* bytes, size_t n_bytes,
+                     int32_t long_read_mode, uint32_t* perm, uint8_t* flag, hlala_bam_group_stats* stats);
+/* ... appended to the device arrays in n_rounds calls of k_grp_append, round k holding the next round_recs[k] descriptors (their sum is n), as the decoder does it */
+int  hlala_bam_group_rounds(hlala_inflater* inf, const hlala_bam_rec* recs, int64_t n, const uint8_t* bytes, size_t n_bytes, const int64_t* round_recs, int32_t n_rounds,
+                            int32_t long_read_mode, uint32_t* perm, uint8_t* flag, hlala_bam_group_stats* stats);
+/* Flag of hlala_bam_extract_seeds_gpu (HLALA_E_ARG without HLALA_SEEDS_GPU_PARSE): the decoder's group phase on the device as well.  A round's descriptors are kept
+ * as they arrive instead of being scattered into the name partitions; after the last round the host gathers them through perm and builds its units by walking flag.
+ * Collided runs go to the host's own re-sort by (name, order).  The whole sample is grouped by the host as without the flag where a round fell back to the host's
+ * parse, the sample has 2^31 descriptors or more, a name is empty, or the sample-long device arrays cannot be allocated.  The sample is the same to the byte. */
+#define HLALA_SEEDS_GPU_GROUP 8
+/* counts[3]: records grouped on the GPU, collided runs the host regrouped, 1 if the whole sample was grouped by the host instead */
+int  hlala_seed_batch_group_counts(const hlala_seed_batch* s, int64_t* counts);
+
 /* Page-locked host memory for the buffers a caller hands to hlala_batch_create / hlala_batch_get_pairs_packed / the getters: transfers from and
  * to such buffers are true DMA (asynchronous, full PCIe rate); pageable buffers work everywhere, at about a third of the rate.  hlala_host_register
  * pins an existing allocation in place (e.g. the arrays of a seed batch: hlala_seed_batch_pin), hlala_host_unregister undoes it.  */
@@ -931,7 +959,8 @@ int  hlala_abi_sizeof(const char* struct_name);
  * 5 = ... with n_dp_band2 / n_dp_band2_failed / ms_dp_band2, hlala_set_tail_pool / hlala_flush / hlala_comm_* exist (round 6);
  * 6 = hlala_inflater_* / hlala_bgzf_inflate / hlala_bam_extract_seeds_gpu / hlala_seed_batch_inflate_counts exist (additive);
  * 7 = hlala_bam_scan / hlala_bam_scan_status_text and their structs, HLALA_SEEDS_GPU_PARSE, hlala_seed_batch_parse_counts / _transfer_bytes exist (additive).
- * Symbols that are purely additive no longer change it (hlala_set_pair_overflow; hlala_bgzf_inflate_crc, HLALA_SEEDS_VERIFY_CRC, hlala_seed_batch_crc_counts): a caller
+ * Symbols that are purely additive no longer change it (hlala_set_pair_overflow; hlala_bgzf_inflate_crc, HLALA_SEEDS_VERIFY_CRC, hlala_seed_batch_crc_counts;
+ * hlala_bam_group / _rounds, HLALA_SEEDS_GPU_GROUP, hlala_seed_batch_group_counts): a caller
  * detects them by the presence of the symbol.  A caller compares
  * hlala_abi_version() with the HLALA_ABI_VERSION it was compiled against and refuses to run on a mismatch (hla-la_amd/__init__.py and
  * hla-la_amd/host/hlala_host.hpp do). */

@@ -12,7 +12,9 @@ hlala_bam_scan alone on the first --scan-mb MiB of the inflated file at slices o
 and the share of the kept records that is tags (what compaction saves).  There is no threshold: the yardstick is the host decoder on the same file and box.
 --verify-crc (its output is meant for profiles/bgzf_crc.txt): every decoder runs with and without HLALA_SEEDS_VERIFY_CRC, alternating in the same call -- six decodes per
 round --, and hlala_bgzf_inflate_crc on all blocks reports the summed device time of k_bgzf_crc32 beside that of k_bgzf_inflate over the same chunks.  The cost of the flag
-is read against the flag-off runs of the same call; on the host decoder it is the cost of the host's own CRC pass on the threads of that run."""
+is read against the flag-off runs of the same call; on the host decoder it is the cost of the host's own CRC pass on the threads of that run.
+The fourth path (its output is meant for profiles/bam_group_gpu.txt): HLALA_SEEDS_GPU_PARSE | HLALA_SEEDS_GPU_GROUP in the same alternation; its group phase and wall clock are
+read against the third path's of the same call, and hlala_bam_group alone on the descriptors of the first --scan-mb MiB reports the device time per pass."""
 import argparse
 import os
 import sys
@@ -70,10 +72,29 @@ def scan_alone(P, inf, inflated, intervals, args):
         print("    ms per pass, median (min .. max) of %d calls: %s" % (args.runs, "  ".join("%s %.2f (%.2f .. %.2f)" % (k, float(np.median(t[k])), min(t[k]), max(t[k])) for k in passes)))
         dev = sum(float(np.median(t[k])) for k in ("guess", "link", "starts", "parse", "scan", "emit"))
         print("    the six passes: %.2f ms = %.2f GB/s of inflated bytes; consumed %.3f GB" % (dev, n / 1e9 / (dev / 1e3), st.consumed / 1e9))
+    kept = (recs, comp) if st.status == 0 else None
     if st.status == 0 and st.n_kept:
         print("share of the scanned bytes that comes back as compact bytes: %.3f (all records are examined; %.3f of them are kept; what is dropped of a kept record is its length field and its tags)" % (
             nc / max(1, st.consumed - o), st.n_kept / max(1, st.n_records)))
         print("    -> with records of one kind, length field + tags are about %.3f of a kept record" % (1.0 - (nc / max(1, st.consumed - o)) / (st.n_kept / max(1, st.n_records))))
+    return kept
+
+
+def group_alone(P, inf, recs, comp, args):
+    """hlala_bam_group on the descriptors and compact bytes hlala_bam_scan has just returned (host memory: the upload is part of the call and timed on its own)"""
+    passes = ("h2d", "append", "sort", "mark", "fold", "emit", "d2h", "wall")
+    t = {k: [] for k in passes}
+    for i in range(args.runs + 1):
+        rc, perm, flag, st = inf.bam_group(recs, comp)
+        assert rc == 0, inf.last_error()
+        if i:
+            for k in passes:
+                t[k].append(getattr(st, "ms_" + k))
+    print("hlala_bam_group alone: %d descriptors (%.3f GB of compact bytes uploaded with them), %d runs, %d collided, %d complete and %d incomplete units" % (
+        st.n_recs, comp.size / 1e9, st.n_runs, st.n_collided_runs, st.n_units_complete, st.n_units_incomplete))
+    print("    ms per pass, median (min .. max) of %d calls: %s" % (args.runs, "  ".join("%s %.3f (%.3f .. %.3f)" % (k, float(np.median(t[k])), min(t[k]), max(t[k])) for k in passes)))
+    dev = sum(float(np.median(t[k])) for k in ("append", "sort", "mark", "fold", "emit"))
+    print("    append + sort + mark + fold + emit: %.3f ms = %.1f M descriptors/s" % (dev, st.n_recs / 1e6 / max(1e-9, dev / 1e3)))
 
 
 def main():
@@ -126,20 +147,21 @@ def main():
 
     def run(label, opener, timed):
         t = time.time(); S = opener(); wall = time.time() - t
-        tm = S.timing(); cnt = S.inflate_counts(); pc = S.parse_counts(); tb = S.transfer_bytes(); cc = S.crc_counts(); units = S.n_units; S.close()
+        tm = S.timing(); cnt = S.inflate_counts(); pc = S.parse_counts(); tb = S.transfer_bytes(); cc = S.crc_counts(); gc = S.group_counts(); units = S.n_units; S.close()
         if timed and args.verify_crc:
             print("%-13s wall %.3f s  %s  threads %d  units %d  blocks gpu/retried/host %d/%d/%d  CRC verified gpu/host/rechecked %d/%d/%d" % (
                 label, wall, "  ".join("%s %.3f" % (k, tm[k]) for k in keys), tm["threads"], units, cnt[0], cnt[1], cnt[2], cc[0], cc[1], cc[2]))
         elif timed:
-            print("%-9s wall %.3f s  %s  threads %d  units %d  blocks gpu/retried/host %d/%d/%d  records on the GPU %d in %d rounds, %d rounds fell back  PCIe up %.3f GB, down %.3f GB" % (
-                label, wall, "  ".join("%s %.3f" % (k, tm[k]) for k in keys), tm["threads"], units, cnt[0], cnt[1], cnt[2], pc[0], pc[1], pc[2], tb[0] / 1e9, tb[1] / 1e9))
-        return tm["inflate"], tm["inflate"] + tm["parse"], wall
+            print("%-15s wall %.3f s  %s  threads %d  units %d  blocks gpu/retried/host %d/%d/%d  records on the GPU %d in %d rounds, %d rounds fell back  PCIe up %.3f GB, down %.3f GB  grouped on the GPU %d, runs regrouped %d, by the host %d" % (
+                label, wall, "  ".join("%s %.3f" % (k, tm[k]) for k in keys), tm["threads"], units, cnt[0], cnt[1], cnt[2], pc[0], pc[1], pc[2], tb[0] / 1e9, tb[1] / 1e9, gc[0], gc[1], gc[2]))
+        return tm["inflate"], tm["inflate"] + tm["parse"], wall, tm["group"]
     host = lambda: P.bam_open_seeds(lib, bam, intervals, threads=args.threads, flags=P.SEEDS_PACKED)                 # noqa: E731
     gpu = (lambda: inf.bam_open_seeds(bam, intervals, threads=args.threads, flags=P.SEEDS_PACKED)) if inf else None      # noqa: E731
     gpu_parse = (lambda: inf.bam_open_seeds(bam, intervals, threads=args.threads, flags=P.SEEDS_PACKED | P.SEEDS_GPU_PARSE)) if inf else None      # noqa: E731
-    res = {"host": [], "gpu": [], "gpu+parse": []}
-    order = ["host", "gpu", "gpu+parse"]
-    openers = {"host": host, "gpu": gpu, "gpu+parse": gpu_parse}
+    gpu_group = (lambda: inf.bam_open_seeds(bam, intervals, threads=args.threads, flags=P.SEEDS_PACKED | P.SEEDS_GPU_PARSE | P.SEEDS_GPU_GROUP)) if inf else None      # noqa: E731
+    res = {"host": [], "gpu": [], "gpu+parse": [], "gpu+parse+group": []}
+    order = ["host", "gpu", "gpu+parse", "gpu+parse+group"]
+    openers = {"host": host, "gpu": gpu, "gpu+parse": gpu_parse, "gpu+parse+group": gpu_group}
     if args.verify_crc:
         V = P.SEEDS_PACKED | P.SEEDS_VERIFY_CRC
         openers["host+crc"] = lambda: P.bam_open_seeds(lib, bam, intervals, threads=args.threads, flags=V)                 # noqa: E731
@@ -155,9 +177,13 @@ def main():
         if len(res[k]) > 1:
             v = [x[0] for x in res[k][1:]]
             print("inflate phase, %s: median %.3f s (%.2f GB/s inflated) of %s" % (k, float(np.median(v)), n_inflated / 1e9 / float(np.median(v)), ["%.3f" % x for x in v]))
-            for j, what in ((1, "inflate + parse phases"), (2, "decode, wall")):
+            for j, what in ((1, "inflate + parse phases"), (3, "group phase"), (2, "decode, wall")):
                 v = [x[j] for x in res[k][1:]]
                 print("%s, %s: median %.3f s, range %.3f .. %.3f of %d runs" % (what, k, float(np.median(v)), min(v), max(v), len(v)))
+    if len(res.get("gpu+parse", [])) > 1 and len(res.get("gpu+parse+group", [])) > 1:
+        for j, what in ((3, "group phase"), (2, "decode, wall")):
+            a = float(np.median([x[j] for x in res["gpu+parse"][1:]])); b = float(np.median([x[j] for x in res["gpu+parse+group"][1:]]))
+            print("HLALA_SEEDS_GPU_GROUP against gpu+parse, %s: %+.3f s (median %.3f with against %.3f without)" % (what, b - a, b, a))
     if args.verify_crc:
         for k in ("host", "gpu", "gpu+parse"):
             if len(res[k]) > 1 and len(res[k + "+crc"]) > 1:
@@ -189,7 +215,9 @@ def main():
                 args.runs, med(tk), med(tc), med(tw)))
             print("k_bgzf_crc32 alone: %.1f GB/s inflated, %.3f of the inflate kernel's device time" % (n_inflated / 1e9 / (float(np.median(tc)) / 1e3), float(np.median(tc)) / float(np.median(tk))))
         if args.scan_mb > 0:
-            scan_alone(P, inf, out, intervals, args)
+            kept = scan_alone(P, inf, out, intervals, args)
+            if kept is not None and len(kept[0]):
+                group_alone(P, inf, kept[0], kept[1], args)
         inf.close()
     if tmp:
         import shutil
