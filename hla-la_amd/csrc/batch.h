@@ -65,7 +65,7 @@ template <template <class> class Ptr> struct DevBatchT {
     Ptr<u64> counters;                  // [32]
     Ptr<int> work_counter;              // [WC_N] dynamic work distribution: [0] stage A, [2] stage C, [7] chains stitched, [8]/[9] left / right DP items,
                                     //      [1]/[10] left / right items fetched, [12..35] retry lists (count, fetched) per tier 1..6 and direction
-    Ptr<int> retry_list;                // [16*n_chains] DP items that outgrew a capacity class: (tier 1..6) x (left, right) x n_chains; rows 14 / 15: the fail-over lists of the band kernels and the
+    Ptr<int> retry_list;                // [16*n_chains] DP items that outgrew a capacity class: (tier 1..6) x (left, right) x n_chains, the long calls from the front of a row and the short ones from its back (retry_entry); rows 14 / 15: the fail-over lists of the band kernels and the
                                     //      jump-free instantiation (WC_FO_COUNT)
     Ptr<int> pair_multi;                // [2 passes][2 classes][n_pairs] pairs with several combinations, listed by k_pair_chains for k_pair_multi (kernel_pair.hip; counts in work_counter[WC_PAIR_MULTI ...]);
                                     //      and, 4 n_pairs behind the lists of its pass ([4 n_pairs ...] main, [6 n_pairs ...] side stream), the pairs beyond the capacities, listed for
@@ -88,12 +88,13 @@ template <template <class> class Ptr> struct DevBatchT {
     //      chain_order[k] -- rows are in position order -- and chain_row is the inverse (-1: no row).  null: row = chain number (batches made from seeds, no position order).
     Ptr<int> chain_row;                 // [n_chains]
     int n_rows;
-    Ptr<int> dp_blk;                    // [DPL_N * dp_nblk + 1] items per block of k_dp_items and list (band left / right, jump-free left / right, general left / right); after the scan: where they start
-    Ptr<int> dp_list;                   // [2*n_chains] the ten dense lists of the first DP classes: slots of dp_items in position order (k_dp_lists)
+    Ptr<int> dp_blk;                    // [DPL_N * dp_nblk + 1] items per block of k_dp_items and list (band left / right; jump-free and general: left long / left short / right long / right short); after the scan: where they start
+    Ptr<int> dp_list;                   // [2*n_chains] the fourteen dense lists of the first DP classes: slots of dp_items in position order (k_dp_lists)
     int dp_nblk;                    // blocks of k_dp_items
     int dp_band;                    // > 0: calls whose reach (read bases left + dp_band - 1 levels) stays inside a linear run of the graph go to the band kernel's lists (kernel_dp_band.hip); 0: HLALA_DP_BAND=0
     int dp_band_risky;              // tests (HLALA_DP_BAND_RISKY=1): a call is listed for the band kernel as soon as the linear run covers its read bases -- many then walk past it and exercise the fail-over
     int dp_jf;                      // > 0: calls that meet no gap-path jump go to the lists of the jump-free instantiations, reach = read bases left + dp_jf - 1 levels (HLALA_DP_JF_MARGIN + 1)
+    int dp_long;                    // > 0: a call with at least this many read bases left is LONG -- drawn before the short calls of its list (dpl_list, retry_long_counter); 0: no call is (HLALA_DP_LONG_BASES)
     Ptr<void> dp_items;                 // [2*n_chains] DpItem (kernel_dp.hip)
     Ptr<int> dbg;                       // non-null with HLALA_DEBUG=1: kernels add phase clocks to counters[16..31]
 };
@@ -120,10 +121,20 @@ template <class BT> __device__ __forceinline__ int ordered_chains(const BT& B) {
 // first column slot of a chain's rows in seed_* / ext_* (only chains that passed the filters have rows: callers look at the chain's status first)
 template <class BT> __device__ __forceinline__ size_t row_base(const BT& B, int c) { return (size_t)(B.chain_row ? B.chain_row[c] : c) * (size_t)B.stride; }
 
-// ---- the first DP classes' dense item lists (k_dp_items / k_dp_lists): list k occupies dp_list[dp_blk[k * dp_nblk] .. dp_blk[(k + 1) * dp_nblk]); k + 1: the right extensions
-enum { DPL_BAND16 = 0, DPL_BAND32 = 2, DPL_BAND64 = 4, DPL_JF = 6, DPL_GEN = 8, DPL_N = 10 };
-// the list an item is put on, by the class k_dp_items gives it (0 general, 1 jump-free, 2 / 3 / 4 band kernel with 16 / 32 / 64 lanes per call); + 1 for a right extension
-__host__ __device__ inline int dpl_of_class(int cls) { return cls == 0 ? DPL_GEN : (cls == 1 ? DPL_JF : (cls == 2 ? DPL_BAND16 : (cls == 3 ? DPL_BAND32 : DPL_BAND64))); }
+// ---- the first DP classes' dense item lists (k_dp_items / k_dp_lists): list k occupies dp_list[dp_blk[k * dp_nblk] .. dp_blk[(k + 1) * dp_nblk]).  A band list: k + 1 = the right
+// extensions.  The jump-free and the general class have FOUR lists each -- left long, left short, right long, right short --: the two lists of a direction are one contiguous
+// segment under one fetch counter, [dp_blk[k * dp_nblk], dp_blk[(k + 2) * dp_nblk]), in which the long calls (B.dp_long) come first.  A persistent kernel ends on its slowest
+// call: a call of 150 bases runs seven times the trips of the typical one and must not be among the last ones drawn.
+enum { DPL_BAND16 = 0, DPL_BAND32 = 2, DPL_BAND64 = 4, DPL_JF = 6, DPL_GEN = 10, DPL_N = 14 };
+// the list an item is put on, by the class k_dp_items gives it (0 general, 1 jump-free, 2 / 3 / 4 band kernel with 16 / 32 / 64 lanes per call), its direction (1: right) and whether it is long
+__host__ __device__ inline int dpl_list(int cls, int dir, bool isLong)
+{
+    if(cls >= 2) return (cls == 2 ? DPL_BAND16 : (cls == 3 ? DPL_BAND32 : DPL_BAND64)) + dir;
+    return (cls == 1 ? DPL_JF : DPL_GEN) + 2 * dir + (isLong ? 0 : 1);
+}
+// read bases a call can consume: what lies before the seed for a left extension, behind it for a right one
+__host__ __device__ inline int dp_bases_left(int dir, int seqLen, int start_seq) { return dir ? seqLen - start_seq : start_seq; }
+__host__ __device__ inline bool dp_is_long(int dpLong, int dir, int seqLen, int start_seq) { return dpLong > 0 && dp_bases_left(dir, seqLen, start_seq) >= dpLong; }
 // ---- B.work_counter (WC_N ints): [0] stage A, [1] / [10] left / right general items fetched, [2] stage C, [4] / [5] jump-free items fetched, [6] jump-free calls (statistics),
 // [7] chains stitched, [8] / [9] left / right DP calls, [12..35] retry lists of tiers 1..6 (count, fetched) x (left, right), [36] / [37] second stitch / pairing pass,
 // [40..47] round 6: the lists of the pairs with several combinations (k_pair_chains -> k_pair_multi): per pass (main / side stream) count and fetched of class 0, of class 1; round 5: items fetched by the three band kernels (left, right each), the fail-over list's counts and fetch counters, band calls that
@@ -131,10 +142,19 @@ __host__ __device__ inline int dpl_of_class(int cls) { return cls == 0 ? DPL_GEN
 // many iterations, too many tied end cells)
 // [72..79] the overflow lists of the pairing passes (k_pair_chains -> k_pair_overflow, kernel_pair_overflow.hip): per pass (main / side stream) pairs listed, fetched,
 // scored, refused for want of slab
-// [80..87] unused: [72..87] counted the calls of the two-track band kernels of round 6, which were removed; WC_N stays 88 so that the debug export
-// (include/hlala_gpu.h: HLALA_DEBUG_WC_N) keeps its size
+// [80..87] unused: [72..87] counted the calls of the two-track band kernels of round 6, which were removed; the debug export (include/hlala_gpu.h: HLALA_DEBUG_WC_N) stays at
+// these 88
+// [88..99] the LONG calls on the retry lists of tiers 1..6 x (left, right).  A row of retry_list is filled from both ends: a long call takes entry q of
+// work_counter[WC_RETRY_LONG + ...] from the front, a short one entry n_chains - 1 - q of the row's old counter ([12 + 4(k-1) + 2p], which with B.dp_long = 0 counts every call,
+// as it always did) from the back; the class that draws the row takes the long ones first (retry_entry).  A row holds a direction's items at most once each: the ends never meet.
 enum { WC_PAIR_MULTI = 40, WC_PAIR_OVER = 72, WC_BAND_FETCH = 48, WC_FO_COUNT = 54, WC_FO_FETCH = 56, WC_BAND_FAILED = 58, WC_BAND_CALLS = 59, WC_JF_FAILED = 60, WC_BAND_WHY = 62, WC_BAND_TIED = 68,
-       WC_N = 88 };
+       WC_RETRY_LONG = 88, WC_N = 100 };
+// counters of the retry list of tier k = 1..6 and direction p: the short calls pushed (from the back), the fetch counter of the whole row, the long calls pushed (from the front)
+__host__ __device__ inline int wc_retry_short(int tier, int dir) { return 12 + 4 * (tier - 1) + 2 * dir; }
+__host__ __device__ inline int wc_retry_fetch(int tier, int dir) { return 13 + 4 * (tier - 1) + 2 * dir; }
+__host__ __device__ inline int wc_retry_long(int tier, int dir) { return WC_RETRY_LONG + 2 * (tier - 1) + dir; }
+// where the w-th draw of a retry row with nLong long calls lies: the long calls from the front, then the short ones from the back
+__host__ __device__ inline int retry_entry(int w, int nLong, int nChains) { return w < nLong ? w : nChains - 1 - (w - nLong); }
 // the fail-over list of the first classes: calls the band kernel (kernel_dp_band.hip) or the jump-free instantiation could not finish; k_dp<DpTiny, 0> draws it after
 // its own lists.  Entries (slots of dp_items) at retry_list[(14 + direction) * n_chains ...], counts in work_counter[WC_FO_COUNT + direction].
 // ---- capacities of the band kernels (kernel_dp_band.hip): read bases a call may have left for the instantiation with 16 / 32 / 64 lanes per call; k_dp_items lists a call

@@ -87,6 +87,8 @@ struct hlala_ctx {
     std::mutex pool_mu;              // the pool and block_bytes: this context's thread, and any thread that meets an out-of-memory error on the device (device_malloc_retry)
     std::set<struct hlala_batch*> batches;     // live batches: detached (not dangling) if the context is destroyed first
     // DP scratch slabs: one per DpTiny group (4 per wave), one per DpSmall / DpLarge wave (same pool, same layout size)
+    int dp_long_bases = 48;  // read bases left from which a DP call is long: drawn first from its list, so that the persistent DP kernels do not end on it (batch.h: dpl_list, retry_entry); HLALA_DP_LONG_BASES, 0: list order as without
+                             // (resident step at 0 / 16 / 32 / 48: 183.46 / 181.03 / 180.39 / 179.95 ms, profiles/dp_long_first.txt)
     int jf_margin = 16;      // (measured 4 / 8 / 16 / 48: 16-lane + 32-lane class 105.6 / 104.1 / 103.4 / 104.1 ms -- a tight bound sends more calls to the cheap instantiation and more of them on to the 32-lane class) levels beyond the read bases left that a jump-free call is taken to reach (kernel_dp.hip: k_dp_items)
     int stitch_by_row = 1;     // k_stitch_chains draws column rows (position order, only chains that hold one) instead of chain numbers (HLALA_STITCH_BY_ROW=0; 6.9 -> 6.65 ms)
     int stitch_draw = 12;      // chains per draw of k_stitch_chains (8: 9.1 ms per million pairs, the rate of the draws themselves; 12 / 16: 6.7 / 6.6 ms; 64: 15 ms -- kernel_dp.hip)
@@ -511,6 +513,7 @@ int hlala_create(hlala_ctx** out, int device, void* stream, const hlala_graph_de
     if(const char* e = getenv("HLALA_POOL_CAP_GB")) { const long g = atol(e); if(g >= 0 && g <= 1024) c->pool_cap = (size_t)g << 30; }
     if(const char* e = getenv("HLALA_DP_BAND_MARGIN")) { const int m = atoi(e); if(m >= 0 && m <= 24) c->band_margin = m; }
     if(const char* e = getenv("HLALA_DP_JF_MARGIN")) { const int m = atoi(e); if(m >= 0 && m <= 200) c->jf_margin = m; }      // (A/B: levels beyond the read bases left that a jump-free call may reach)
+    if(const char* e = getenv("HLALA_DP_LONG_BASES")) { const int m = atoi(e); if(m >= 0 && m <= 4096) c->dp_long_bases = m; }
     c->stitch_grid = cus * 20;        // k_stitch_chains: five waves per SIMD (92 VGPRs, nothing spilled)
     if(const char* e = getenv("HLALA_STITCH_BY_ROW")) c->stitch_by_row = atoi(e) != 0;
     // The table of DP classes: blocks, bytes per slab, then one pool per slab layout.  The 64-lane and the wide class have slabs of one size (the larger layout of the two),
@@ -665,7 +668,7 @@ static int batch_alloc_outputs(hlala_ctx* c, hlala_batch* b)
     AL(pair_deferred, np, true); AL(pair_multi, 7 * np, false); AL(counters, 32, true); AL(work_counter, WC_N, true); AL(retry_list, 16 * nc, false);
     { DpItem* it = nullptr; rc = dev_alloc(c, b->allocs, 2 * nc, &it, false); if(rc) return rc; B.dp_items = it; }
     B.dp_nblk = (int)((nc + 255) / 256); if(B.dp_nblk < 1) B.dp_nblk = 1;
-    B.dp_jf = c->jf_margin + 1;
+    B.dp_jf = c->jf_margin + 1; B.dp_long = c->dp_long_bases;
     B.dp_band = c->band_grid > 0 ? c->band_margin + 1 : 0;
     B.dp_band_risky = c->band_risky ? 1 : 0;
     AL(dp_blk, (size_t)DPL_N * B.dp_nblk + 1, false); AL(dp_list, 2 * nc, false);
@@ -1000,7 +1003,7 @@ static int dp_prepare(hlala_ctx* c, hlala_batch* b)
     DpItem* items = (DpItem*)B.dp_items;
     HIP_TRY(c, hipMemsetAsync(B.dp_alias_head, 0xFF, (size_t)2 * B.n_chains * sizeof(int), c->active));       // -1: k_dp_items links the duplicates of a DP to it
     HIP_TRY(c, hipMemsetAsync(B.dp_alias_next, 0xFF, (size_t)2 * B.n_chains * sizeof(int), c->active));
-    // items, then the ten dense lists of the first classes (three band lists, jump-free, general; left / right each) in position order: counts per block, their scan, the slots
+    // items, then the fourteen dense lists of the first classes (three band lists, left / right each; jump-free and general, long / short per direction) in position order: counts per block, their scan, the slots
     HIP_TRY(c, hipMemsetAsync(B.dp_blk, 0, ((size_t)DPL_N * B.dp_nblk + 1) * sizeof(int), c->active));
     hipLaunchKernelGGL(k_dp_items, dim3(B.dp_nblk), dim3(256), 0, c->active, c->G, b->B, items);
     STEP(check_launch(c, "k_dp_items"));
@@ -1739,9 +1742,10 @@ int hlala_batch_get_stats(hlala_ctx* c, hlala_batch* b, hlala_batch_stats* out)
           (void)hipEventElapsedTime(&out->ms_dp_jump_free, b->ev[EV_DP_CLASS_BEGIN], b->ev[EV_DP_JUMP_FREE_END]);
           if(b->band_used) (void)hipEventElapsedTime(&out->ms_dp_band, b->ev[EV_DP_BAND_BEGIN], b->ev[EV_DP_BAND_END]);
           if(b->side_used) (void)hipEventElapsedTime(&out->ms_side, b->ev[EV_SIDE_BEGIN], b->ev[EV_SIDE_END]); } }
-    { int wc[WC_N]; HIP_TRY(c, hipMemcpyAsync(wc, b->B.work_counter, sizeof(wc), hipMemcpyDeviceToHost, c->active)); HIP_TRY(c, hipStreamSynchronize(c->active)); out->n_chains_retried = 0; for(int k = 1; k <= 6; k++) out->n_chains_retried += wc[12 + 4 * (k - 1)] + wc[14 + 4 * (k - 1)]; out->n_dp_retried_large = wc[28] + wc[30];
+    { int wc[WC_N]; HIP_TRY(c, hipMemcpyAsync(wc, b->B.work_counter, sizeof(wc), hipMemcpyDeviceToHost, c->active)); HIP_TRY(c, hipStreamSynchronize(c->active)); out->n_chains_retried = 0; for(int k = 1; k <= 6; k++) out->n_dp_class[k] = wc[wc_retry_short(k, 0)] + wc[wc_retry_short(k, 1)] + wc[wc_retry_long(k, 0)] + wc[wc_retry_long(k, 1)];          // (short and long calls of a retry row: batch.h)
+      for(int k = 1; k <= 6; k++) out->n_chains_retried += out->n_dp_class[k]; out->n_dp_retried_large = out->n_dp_class[5];
       out->n_dp_band = b->band_used ? wc[WC_BAND_CALLS] : 0; out->n_dp_band_failed = b->band_used ? wc[WC_BAND_FAILED] : 0; out->n_dp_jump_free_failed = wc[WC_JF_FAILED];
-      out->n_dp_class[0] = wc[8] + wc[9] - out->n_dp_band + out->n_dp_band_failed; out->n_dp_jump_free = wc[6]; for(int k = 1; k <= 6; k++) out->n_dp_class[k] = wc[12 + 4 * (k - 1)] + wc[14 + 4 * (k - 1)]; }
+      out->n_dp_class[0] = wc[8] + wc[9] - out->n_dp_band + out->n_dp_band_failed; out->n_dp_jump_free = wc[6]; }
     if(b->staged & 4) (void)hipEventElapsedTime(&out->ms_pair, b->ev[EV_PAIR_BEGIN], b->ev[EV_PAIR_END]);
     out->n_chains_extended = (int64_t)cnt[CNT_CHAINS_EXT]; out->n_dp_calls = (int64_t)cnt[CNT_DP_CALLS];
     out->n_dp_iterations = (int64_t)cnt[CNT_DP_ITERS]; out->n_dp_cells = (int64_t)cnt[CNT_DP_CELLS];
@@ -1917,11 +1921,11 @@ extern "C" int hlala_debug_memory(hlala_ctx* c, hlala_batch* b, unsigned long lo
 // the batch's work counters (diagnostics: item counts of the lists, fail-over reasons of the band kernel -- batch.h)
 extern "C" int hlala_debug_work_counters(hlala_ctx* c, hlala_batch* b, int* out, int capacity)
 {
-    static_assert(WC_N == HLALA_DEBUG_WC_N && WC_BAND_FETCH == HLALA_DEBUG_WC_BAND_FETCH && WC_BAND_WHY == HLALA_DEBUG_WC_BAND_WHY && WC_BAND_TIED == HLALA_DEBUG_WC_BAND_TIED, "include/hlala_gpu.h: debug section");
+    static_assert(WC_N >= HLALA_DEBUG_WC_N && WC_BAND_FETCH == HLALA_DEBUG_WC_BAND_FETCH && WC_BAND_WHY == HLALA_DEBUG_WC_BAND_WHY && WC_BAND_TIED == HLALA_DEBUG_WC_BAND_TIED, "include/hlala_gpu.h: debug section");
     DEV_GUARD(c);
     ReaderScope rscope_(c, b); if(rscope_.rc) return rscope_.rc;
     if(!c || !b || !out || capacity < 0) return HLALA_E_ARG;
-    const int n = capacity < WC_N ? capacity : WC_N;          // (a caller built against an older header gets the counters it has room for)
+    const int n = capacity < HLALA_DEBUG_WC_N ? capacity : HLALA_DEBUG_WC_N;          // (a caller built against an older header gets the counters it has room for; the counters behind the exported ones are the kernels' own)
     if(!b->outputs_ready) { memset(out, 0, (size_t)n * sizeof(int)); return HLALA_OK; }
     HIP_TRY(c, hipStreamSynchronize(c->active));
     HIP_TRY(c, hipMemcpyAsync(out, b->B.work_counter, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, c->active)); HIP_TRY(c, hipStreamSynchronize(c->active));

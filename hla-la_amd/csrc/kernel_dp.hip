@@ -1596,7 +1596,7 @@ __global__ void k_dp_items(const DevGraph G, const DevBatch B, DpItem* items)
         if(needL) { sl[0] = make_int4(itL.item, itL.rOff, itL.seqLen, itL.start_seq); sl[1] = make_int4(itL.startLevel, itL.startNode, clsL, runL); } else sl[0] = make_int4(-1, 0, 0, 0);
         if(needR) { sr[0] = make_int4(itR.item, itR.rOff, itR.seqLen, itR.start_seq); sr[1] = make_int4(itR.startLevel, itR.startNode, clsR, runR); } else sr[0] = make_int4(-1, 0, 0, 0);
     }
-    // ---- how many items of each of the ten lists (three band lists, jump-free, general; left / right each) this block holds: k_order_scan turns the counts of all
+    // ---- how many items of each of the fourteen lists (three band lists, left / right each; jump-free and general, long / short per direction: batch.h) this block holds: k_order_scan turns the counts of all
     // blocks into the blocks' places in the dense lists, k_dp_lists writes the slot numbers there -- in position order, nothing is left to the atomics.
     // work_counter[8] / [9]: left / right DP calls of the batch, [6]: the jump-free ones among them, [WC_BAND_CALLS]: the band ones (statistics)
     __shared__ int blkCnt[DPL_N];
@@ -1606,7 +1606,7 @@ __global__ void k_dp_items(const DevGraph G, const DevBatch B, DpItem* items)
     nShared = wave_sum_i32(nShared);
     if(lane == 0 && nShared) atomicAdd(&B.counters[CNT_DP_SHARED], (u64)nShared);
     const u64 mL = __ballot(needL), mR = __ballot(needR);
-    const int kL = needL ? dpl_of_class(clsL) : -1, kR = needR ? dpl_of_class(clsR) + 1 : -1;
+    const int kL = needL ? dpl_list(clsL, 0, dp_is_long(B.dp_long, 0, itL.seqLen, itL.start_seq)) : -1, kR = needR ? dpl_list(clsR, 1, dp_is_long(B.dp_long, 1, itR.seqLen, itR.start_seq)) : -1;
     const u64 mJL = __ballot(needL && clsL == 1), mJR = __ballot(needR && clsR == 1), mBL = __ballot(needL && clsL >= 2), mBR = __ballot(needR && clsR >= 2);
     if(lane == 0) {
         if(mL) atomicAdd(&B.work_counter[8], __popcll(mL));
@@ -1616,16 +1616,16 @@ __global__ void k_dp_items(const DevGraph G, const DevBatch B, DpItem* items)
     }
 #pragma unroll
     for(int k = 0; k < DPL_N; k++) {
-        const u64 mk = __ballot((k & 1) ? kR == k : kL == k);
+        const u64 mk = __ballot(kL == k || kR == k);          // (a list holds one direction: at most one of the two)
         if(lane == 0 && mk) atomicAdd(&blkCnt[k], __popcll(mk));
     }
     __syncthreads();
     if(threadIdx.x < DPL_N) B.dp_blk[(size_t)threadIdx.x * gridDim.x + blockIdx.x] = blkCnt[threadIdx.x];
 }
 
-// The ten dense item lists of the first DP classes: list k (DPL_BAND16 / DPL_BAND32 / DPL_BAND64 / DPL_JF / DPL_GEN, + 1 for the right extensions) occupies
-// dp_list[dp_blk[k * nBlk] .. dp_blk[(k + 1) * nBlk]) -- dp_blk after its exclusive scan: entry k * nBlk + b = where block b's items of list k start --, its
-// entries are the slots of k_dp_items' item arrays in position order.  Same grid as k_dp_items.
+// The fourteen dense item lists of the first DP classes: list k (dpl_list, batch.h: DPL_BAND16 / DPL_BAND32 / DPL_BAND64 + direction, DPL_JF / DPL_GEN + 2 * direction
+// + long or short) occupies dp_list[dp_blk[k * nBlk] .. dp_blk[(k + 1) * nBlk]) -- dp_blk after its exclusive scan: entry k * nBlk + b = where block b's items of list k
+// start --, its entries are the slots of k_dp_items' item arrays in position order.  Same grid as k_dp_items.
 __global__ void k_dp_lists(const DevBatch B, const DpItem* __restrict__ items)
 {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1633,14 +1633,15 @@ __global__ void k_dp_lists(const DevBatch B, const DpItem* __restrict__ items)
     int kL = -1, kR = -1;             // list of the left / right item of this slot
     if(t < nOrd) {
         const int4* sl = (const int4*)(items + t); const int4* sr = (const int4*)(items + (size_t)B.n_chains + t);
-        if(sl[0].x >= 0) kL = dpl_of_class(sl[1].z);
-        if(sr[0].x >= 0) kR = dpl_of_class(sr[1].z) + 1;
+        const int4 a = sl[0], b = sr[0];          // (item, rOff, seqLen, start_seq)
+        if(a.x >= 0) kL = dpl_list(sl[1].z, 0, dp_is_long(B.dp_long, 0, a.z, a.w));
+        if(b.x >= 0) kR = dpl_list(sr[1].z, 1, dp_is_long(B.dp_long, 1, b.z, b.w));
     }
     __shared__ int waveCnt[DPL_N][4];      // [list][wave of the block]
     const int lane = lane_id(), wv = (int)(threadIdx.x >> 6);
     u64 m[DPL_N];
 #pragma unroll
-    for(int k = 0; k < DPL_N; k++) m[k] = __ballot((k & 1) ? kR == k : kL == k);
+    for(int k = 0; k < DPL_N; k++) m[k] = __ballot(kL == k || kR == k);
     if(lane == 0) {
 #pragma unroll
         for(int k = 0; k < DPL_N; k++) waveCnt[k][wv] = (int)__popcll(m[k]);
@@ -1649,12 +1650,11 @@ __global__ void k_dp_lists(const DevBatch B, const DpItem* __restrict__ items)
     const u64 below = (1ull << lane) - 1ull;
 #pragma unroll
     for(int k = 0; k < DPL_N; k++) {
-        const bool mine = (k & 1) ? kR == k : kL == k;
-        if(mine) {
+        if(kL == k || kR == k) {
             int before = 0;
             for(int w2 = 0; w2 < wv; w2++) before += waveCnt[k][w2];
             const int pos = B.dp_blk[(size_t)k * gridDim.x + blockIdx.x] + before + (int)__popcll(m[k] & below);
-            B.dp_list[pos] = (k & 1) ? B.n_chains + t : t;
+            B.dp_list[pos] = kR == k ? B.n_chains + t : t;
         }
     }
 }
@@ -1749,18 +1749,24 @@ __device__ __forceinline__ void dp_class_run(const DG& G, const DB& B, const DpI
         const int dirPass = pass & 1;
         const bool foPass = pass >= 2;
         // work_counter: [8]/[9] left / right item counts, [1]/[10] their fetch counters;
-        // retry list of tier k = 1..6 and direction p: count [12 + 4(k-1) + 2p], fetched [13 + 4(k-1) + 2p], entries retry_list[(2(k-1) + p) n_chains ...]
+        // retry list of tier k = 1..6 and direction p (batch.h: wc_retry_short / wc_retry_fetch / wc_retry_long): entries retry_list[(2(k-1) + p) n_chains ...], the long
+        // calls from the front of the row and the short ones from its back
+        constexpr int RT = TIER > 0 ? TIER : 1;
         int* fetchCounter = foPass ? &B.work_counter[WC_FO_FETCH + dirPass]
-                          : &B.work_counter[TIER == 0 ? (C::JF ? 4 + dirPass : (dirPass ? 10 : 1)) : 13 + 4 * (TIER - 1) + 2 * dirPass];        // [4]/[5]: the jump-free lists
-        // (TIER 0 draws from the dense lists of k_dp_lists -- jump-free or general, left or right --, the later tiers from the retry lists)
-        const int seg = (C::JF ? DPL_JF : DPL_GEN) + dirPass;
+                          : &B.work_counter[TIER == 0 ? (C::JF ? 4 + dirPass : (dirPass ? 10 : 1)) : wc_retry_fetch(RT, dirPass)];        // [4]/[5]: the jump-free lists
+        // (TIER 0 draws from the dense lists of k_dp_lists -- jump-free or general, left or right: the long list and the short list behind it as one segment --, the later
+        //  tiers from the retry lists)
+        const int seg = (C::JF ? DPL_JF : DPL_GEN) + 2 * dirPass;
         const bool dense = TIER == 0 && !foPass;
+        const bool twoEnded = TIER > 0;                    // a retry row: draw w lies at retry_entry(w, nLong, n_chains)
         const int segStart = dense ? uni(B.dp_blk[(size_t)seg * B.dp_nblk]) : 0;
-        const int nItems = dense ? uni(B.dp_blk[(size_t)(seg + 1) * B.dp_nblk]) - segStart
-                         : (foPass ? uni(B.work_counter[WC_FO_COUNT + dirPass]) : uni(B.work_counter[12 + 4 * (TIER > 0 ? TIER - 1 : 0) + 2 * dirPass]));
+        const int nLong = twoEnded ? uni(B.work_counter[wc_retry_long(RT, dirPass)]) : 0;
+        const int nItems = dense ? uni(B.dp_blk[(size_t)(seg + 2) * B.dp_nblk]) - segStart
+                         : (foPass ? uni(B.work_counter[WC_FO_COUNT + dirPass]) : nLong + uni(B.work_counter[wc_retry_short(RT, dirPass)]));
+        const int nChains = B.n_chains;
         const int* srcList = dense ? B.dp_list + segStart
                            : (foPass ? B.retry_list + (size_t)(14 + dirPass) * (size_t)B.n_chains
-                           : B.retry_list + (size_t)(2 * (TIER > 0 ? TIER - 1 : 0) + dirPass) * (size_t)B.n_chains);
+                           : B.retry_list + (size_t)(2 * (RT - 1) + dirPass) * (size_t)B.n_chains);
         const bool fwd = dirPass != 0;                     // left extensions run backwards (alignerBase: extensionAligner.cpp:229-241)
         if constexpr (DRAW > 1) { if(gl == 0) { S.chunkNext = 0; S.chunkEnd = 0; } DSYNC(); }
         int phase = PH_IDLE;
@@ -1806,10 +1812,12 @@ __device__ __forceinline__ void dp_class_run(const DG& G, const DB& B, const DpI
                     else if(capacity && TIER < DP_LAST_TIER) {
                         // next tier, or straight to the first tier whose class holds what overflowed (no point in failing again on the way)
                         int to = TIER + 1; if(st.needTier > to) to = st.needTier; if(to > DP_LAST_TIER) to = DP_LAST_TIER;
-                        int* cnt = &B.work_counter[12 + 4 * (to - 1) + 2 * dirPass]; int* lst = B.retry_list + (size_t)(2 * (to - 1) + dirPass) * (size_t)B.n_chains;
+                        int* lst = B.retry_list + (size_t)(2 * (to - 1) + dirPass) * (size_t)B.n_chains;
                         // (a linked duplicate whose own backtrace outgrew the class takes over the item entry: the DP that ran is done with it)
                         if(st.isAlias) ((int*)(items + st.itemIdx))[0] = st.item;
-                        int q = atomicAdd(cnt, 1); lst[q] = st.itemIdx;
+                        // a long call from the front of the row, a short one from its back: the next class draws the long ones first
+                        if(dp_is_long(B.dp_long, dirPass, st.seqLen, st.start_seq)) { const int q = atomicAdd(&B.work_counter[wc_retry_long(to, dirPass)], 1); lst[q] = st.itemIdx; }
+                        else { const int q = atomicAdd(&B.work_counter[wc_retry_short(to, dirPass)], 1); lst[B.n_chains - 1 - q] = st.itemIdx; }
                         // (all chains that share this DP belong to one read: its pair waits for the side-stream classes)
                         if(to >= DP_SIDE_TIER && B.n_pairs > 0 && !B.unpaired) B.pair_deferred[B.chain_read[st.item >> 1] >> 1] = 1;
                     } else {
@@ -1851,7 +1859,7 @@ __device__ __forceinline__ void dp_class_run(const DG& G, const DB& B, const DpI
                 w = grp_bcast0<GW>(w);
                 if(w >= nItems) more = false;
                 else {
-                    const int idx = guni<GW>(srcList[w]);
+                    const int idx = guni<GW>(srcList[twoEnded ? retry_entry(w, nLong, nChains) : w]);
                     const int4* ip = (const int4*)(items + idx);
                     int4 a = ip[0], b = ip[1];
                     DpItem it; it.item = a.x; it.rOff = a.y; it.seqLen = a.z; it.start_seq = a.w; it.startLevel = b.x; it.startNode = b.y; it.pad0 = 0; it.pad1 = 0;
@@ -1871,7 +1879,17 @@ __device__ __forceinline__ void dp_class_run(const DG& G, const DB& B, const DpI
         atomicAdd(&B.counters[CNT_DP_CALLS], S.accCalls); atomicAdd(&B.counters[CNT_DP_ITERS], S.accIters);
         atomicAdd(&B.counters[CNT_DP_CELLS], S.accCells); atomicAdd(&B.counters[CNT_EDGES], S.accEdges);
     }
-#ifdef HLALA_DP_TIMING
+#if defined(HLALA_DP_TIMING) && HLALA_DP_TIMING + 0 == 2
+    // -DHLALA_DP_TIMING=2: the TAIL of the main-stream classes instead of the phase clocks below.  Every wavefront notes the constant-rate clock (100 MHz, one
+    // clock for the whole chip: the shader clock is not comparable across XCDs) when it has found its last list empty; counters[16 + 2 i] keeps the complement of
+    // the earliest, [17 + 2 i] the latest of launch i (0 jump-free, 1 general 16-lane, 2 32-lane, 3 64-lane, 4 wide).  Latest - earliest = how long the kernel's
+    // slowest call held it while other wavefronts sat idle.  tools/dp_tail.py prints them.
+    if(TIER <= 3 && (threadIdx.x & 63) == 0) {
+        constexpr int KI = TIER == 0 ? (C::JF ? 0 : 1) : TIER + 1;
+        const u64 now = (u64)wall_clock64();
+        atomicMax((unsigned long long*)&B.counters[16 + 2 * KI], (unsigned long long)~now); atomicMax((unsigned long long*)&B.counters[17 + 2 * KI], (unsigned long long)now);
+    }
+#elif defined(HLALA_DP_TIMING)
     if(TIER == 0 && (threadIdx.x & 63) == 0) { for(int i = 0; i < 8; i++) atomicAdd(&B.counters[24 + i], (u64)S.tPh[i]); for(int i = 0; i < 8; i++) atomicAdd(&B.counters[16 + i], (u64)S.tPh[8 + i]);
         for(int i = 0; i < 6; i++) atomicAdd(&B.counters[8 + i], (u64)tAcc[i]); atomicAdd(&B.counters[14], (u64)trips); atomicAdd(&B.counters[15], (u64)runGroups); }
 #endif

@@ -11,6 +11,7 @@ P = load_package()
 n_pairs = int(sys.argv[1]); G = int(sys.argv[2]); fg = float(sys.argv[3]) if len(sys.argv) > 3 else 1.0
 w = synth.make_world_m(seed=2, n_levels=G)
 b = synth.make_batch_m(w, n_pairs, seed=77, frac_gene=fg)
+os.environ["HLALA_DP_LONG_BASES"] = "0"          # no long calls: every call of a retry row is a short one, at the back of the row and counted by the exported work counter (batch.h: retry_entry)
 ctx = P.Context(w["graph"], w["contigs"], insert_mean=b["insert_mean"], insert_sd=b["insert_sd"], rng_seed=12345)
 gb = ctx.batch(b); gb.align(); st = gb.stats()
 nc = b["n_chains"]
@@ -39,7 +40,7 @@ for k in range(1, 7):
     sl = []
     for p in range(2):
         cnt = wc[12 + 4 * (k - 1) + 2 * p]
-        sl.append(retry[(2 * (k - 1) + p) * nc:(2 * (k - 1) + p) * nc + cnt])
+        sl.append(retry[(2 * (k - 1) + p + 1) * nc - cnt:(2 * (k - 1) + p + 1) * nc])
     sl = np.concatenate(sl); ent[k] = sl
     if len(sl):
         print("class %d: %6d calls entered; widest level: min %d, percentiles 1 / 10 / 50 / 90: %s" % (k, len(sl), wmax[sl].min(), np.percentile(wmax[sl], [1, 10, 50, 90])))
