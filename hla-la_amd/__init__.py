@@ -332,6 +332,13 @@ class SeedBatch:
         self.lib.hlala_seed_batch_group_counts(self.h, cnt)
         return tuple(int(x) for x in cnt)
 
+    def sort_counts(self):
+        """(units ordered by read name on the GPU, units of collided runs the host merged in, 1 if the whole sample was ordered by the host instead); all zero without SEEDS_GPU_SORT"""
+        cnt = (C.c_int64 * 3)()
+        self.lib.hlala_seed_batch_sort_counts.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        self.lib.hlala_seed_batch_sort_counts(self.h, cnt)
+        return tuple(int(x) for x in cnt)
+
     def inflate_counts(self):
         """(blocks inflated on the GPU, blocks the GPU rejected and the host engine ran again, blocks inflated on the host only)"""
         cnt = (C.c_int64 * 3)()
@@ -358,6 +365,7 @@ SEEDS_PACKED = 1          # HLALA_SEEDS_PACKED
 SEEDS_GPU_PARSE = 2       # HLALA_SEEDS_GPU_PARSE (Inflater.bam_open_seeds only): the record pass of every round on the GPU as well
 SEEDS_VERIFY_CRC = 4      # HLALA_SEEDS_VERIFY_CRC (bam_open_seeds and Inflater.bam_open_seeds): the CRC-32 of every BGZF block is compared with that of its inflated bytes
 SEEDS_GPU_GROUP = 8       # HLALA_SEEDS_GPU_GROUP (with SEEDS_GPU_PARSE only): the records are grouped by read name on the GPU as well
+SEEDS_GPU_SORT = 16       # HLALA_SEEDS_GPU_SORT (with SEEDS_GPU_GROUP only): the units are put into read-name order on the GPU as well
 
 
 def bam_open_seeds(lib, path, intervals, long_read_mode=False, threads=0, flags=0) -> SeedBatch:
@@ -397,6 +405,10 @@ class BamGroupStats(C.Structure):
 
 
 GROUP_START, GROUP_COLLIDED, GROUP_COMPLETE = 1, 2, 4          # flag[] of hlala_bam_group
+
+
+class BamNameOrderStats(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("n", "n_rounds", "n_equal_names")] + [(k, C.c_double) for k in ("ms_h2d", "ms_key", "ms_sort", "ms_mark", "ms_scatter", "ms_d2h", "ms_wall")]
 
 
 # hlala_bam_rec
@@ -504,6 +516,22 @@ class Inflater:
             raise HlalaError(f"hlala_bam_group failed ({rc}): {self.last_error()}")
         k = recs.size if rc == 0 else 0
         return rc, perm[:k], flag[:k], st
+
+    def bam_name_order(self, name_off, name_len, data, n=None, n_bytes=None):
+        """hlala_bam_name_order: name i is data[name_off[i] : name_off[i] + name_len[i]].  Returns (return code, order, BamNameOrderStats): order[k] is the index of the k-th
+        name (memcmp, then the shorter first; equal names by index); HLALA_E_ARG (-1) is returned, not raised (last_error() says why).  n / n_bytes: the sizes handed
+        in, where they are to differ from the arrays' (tests)."""
+        off = np.ascontiguousarray(name_off, np.uint64); ln = np.ascontiguousarray(name_len, np.uint32); data = np.ascontiguousarray(data, np.uint8)
+        if off.size != ln.size:
+            raise ValueError("name_off and name_len differ in size")
+        n = off.size if n is None else int(n); nb = data.size if n_bytes is None else int(n_bytes)
+        order = np.zeros(max(1, off.size), np.uint32); st = BamNameOrderStats()
+        self.lib.hlala_bam_name_order.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(BamNameOrderStats)]
+        rc = self.lib.hlala_bam_name_order(self.h, off.ctypes.data if off.size else None, ln.ctypes.data if ln.size else None, n, data.ctypes.data if data.size else None, nb,
+                                           order.ctypes.data, C.byref(st))
+        if rc not in (0, -1):
+            raise HlalaError(f"hlala_bam_name_order failed ({rc}): {self.last_error()}")
+        return rc, order[:off.size if rc == 0 else 0], st
 
     def last_error(self):
         return self.lib.hlala_inflater_last_error(self.h).decode(errors="replace")
@@ -903,6 +931,7 @@ EXPORTED_SYMBOLS = [
     "hlala_bgzf_inflate_crc", "hlala_seed_batch_crc_counts",
     "hlala_bam_scan", "hlala_bam_scan_status_text", "hlala_seed_batch_parse_counts", "hlala_seed_batch_transfer_bytes",
     "hlala_bam_group", "hlala_bam_group_rounds", "hlala_seed_batch_group_counts",
+    "hlala_bam_name_order", "hlala_seed_batch_sort_counts",
     "hlala_locus_cluster_kmers", "hlala_type_locus", "hlala_kmer_presence", "hlala_kmer_keep_reads", "hlala_kmer_presence_kept", "hlala_kmer_forget_reads", "hlala_unit_alignment_stats", "hlala_typer_write_summary", "hlala_typer_begin_output", "hlala_locus_write_files", "hlala_locus_write_pairs_file", "hlala_typer_end_output",
 ]
 

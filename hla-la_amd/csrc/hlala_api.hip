@@ -33,6 +33,7 @@
 #include "kernel_crc32.hip"
 #include "kernel_bamscan.hip"
 #include "kernel_bamgroup.hip"
+#include "kernel_bamnameorder.hip"
 
 namespace hlala {
 size_t proj_slab_bytes_host(int stride, int maxNodesPerLevel) { return proj_slab_bytes(stride, maxNodesPerLevel); }
@@ -2362,13 +2363,21 @@ struct GroupState {
     ScanBuf buf[GRP_NBUF]; hipEvent_t ev[GRP_NEV]{}; bool evReady = false;
     int64_t n = 0; uint64_t nameBytes = 0; double msAppend = 0;
     bool ok = true;                 // false: a round could not be appended (allocation, 2^31 descriptors): the sample is not grouped here
+    bool finished = false; int64_t nComplete = 0;      // group_finish has run over the n descriptors and found this many clean, complete runs (what HLALA_SEEDS_GPU_SORT orders)
 };
+// device buffers of the ordering stage (hlala_bam_name_order; HLALA_SEEDS_GPU_SORT): the names' offsets and lengths, the double-buffered working set (idx, seg, gp), the
+// scratch of a round; grown on demand, kept by the handle
+enum { NAM_IN_OFF, NAM_IN_LEN, NAM_IN_BYTES, NAM_SEL, NAM_SELOFF, NAM_IDX0, NAM_IDX1, NAM_SEG0, NAM_SEG1, NAM_GP0, NAM_GP1, NAM_KEY, NAM_KEYS, NAM_VAL, NAM_P1, NAM_K2, NAM_K2S, NAM_P2, NAM_NEWIDX,
+       NAM_FL, NAM_FLOFF, NAM_ORDER, NAM_COUNT, NAM_CUB, NAM_NBUF };
+constexpr int NAM_NEV = 7;
+struct NameOrderState { ScanBuf buf[NAM_NBUF]; hipEvent_t ev[NAM_NEV]{}; bool evReady = false; };
 struct hlala_inflater {
     int device = 0; size_t chunk = 0, outCap = 0; int64_t maxBlocks = 0;
     InflateSlot slot[3];
     ScanBuf scan[SCAN_NBUF]; hipEvent_t scanEv[SCAN_NEV]{}; bool scanEvReady = false;
     size_t roundBytes = 0;          // bytes of the decoder's last round in scan[SCAN_DATA] (hlala_host::bam_scan_round: their tail is the next round's carry)
     GroupState grp;
+    NameOrderState nam;
     std::string err;
 };
 static thread_local std::string g_inflater_create_error;
@@ -2389,6 +2398,8 @@ extern "C" void hlala_inflater_destroy(hlala_inflater* f)
     for(hipEvent_t e : f->scanEv) if(e) (void)hipEventDestroy(e);
     for(ScanBuf& b : f->grp.buf) if(b.p) (void)hipFree(b.p);
     for(hipEvent_t e : f->grp.ev) if(e) (void)hipEventDestroy(e);
+    for(ScanBuf& b : f->nam.buf) if(b.p) (void)hipFree(b.p);
+    for(hipEvent_t e : f->nam.ev) if(e) (void)hipEventDestroy(e);
     delete f;
 }
 extern "C" int hlala_inflater_create(int32_t device, size_t chunk_bytes, hlala_inflater** out)
@@ -2556,11 +2567,12 @@ static int bam_inflate_hook(void* inflater, const uint8_t* comp, size_t comp_byt
 }
 static int bam_scan_hook(void* inflater, hlala_host::bam_scan_round* R, std::string* err);      // (behind hlala_bam_scan, below)
 static int bam_group_hook(void* inflater, int64_t n, int32_t long_read_mode, uint32_t* perm, uint8_t* flag, hlala_bam_group_stats* stats, bool* available, std::string* err);      // (behind hlala_bam_group, below)
+static int bam_sort_hook(void* inflater, int64_t m, uint32_t* order, hlala_bam_name_order_stats* stats, bool* available, std::string* err);      // (behind hlala_bam_name_order, below)
 extern "C" int hlala_bam_extract_seeds_gpu(hlala_inflater* f, const char* path, int32_t n_intervals, const hlala_bam_interval* iv, int32_t long_read_mode, int32_t n_threads, int32_t flags,
                                            hlala_seed_batch** out)
 {
     static std::once_flag hookOnce;                  // (samples may decode on several threads)
-    std::call_once(hookOnce, []() { hlala_host::g_bam_inflate_hook = bam_inflate_hook; hlala_host::g_bam_inflate_crc_hook = bam_inflate_crc_hook; hlala_host::g_bam_scan_hook = bam_scan_hook; hlala_host::g_bam_group_hook = bam_group_hook; });
+    std::call_once(hookOnce, []() { hlala_host::g_bam_inflate_hook = bam_inflate_hook; hlala_host::g_bam_inflate_crc_hook = bam_inflate_crc_hook; hlala_host::g_bam_scan_hook = bam_scan_hook; hlala_host::g_bam_group_hook = bam_group_hook; hlala_host::g_bam_sort_hook = bam_sort_hook; });
     return hlala_host::bam_extract_seeds_impl(path, n_intervals, iv, long_read_mode, n_threads, flags, true, f, out);
 }
 
@@ -2765,7 +2777,7 @@ static int bam_scan_hook(void* inflater, hlala_host::bam_scan_round* R, std::str
 
 // ---- grouping by read name (include/hlala_gpu.h; kernel_bamgroup.hip).  Append per round on the scan's stream; after the last round one stretch of that stream: sort, mark,
 // run ids, fold, emit, download.  The host looks at the device twice per round (how many name bytes the round brings: the arena may have to grow) and once at the end.
-static void group_reset(hlala_inflater* f) { f->grp.n = 0; f->grp.nameBytes = 0; f->grp.msAppend = 0; f->grp.ok = true; }
+static void group_reset(hlala_inflater* f) { f->grp.n = 0; f->grp.nameBytes = 0; f->grp.msAppend = 0; f->grp.ok = true; f->grp.finished = false; f->grp.nComplete = 0; }
 // `keep` bytes of the old buffer survive (device to device); the stream is idle when the old buffer is freed
 static hipError_t group_grow(hlala_inflater* f, int which, size_t bytes, size_t keep, hipStream_t st)
 {
@@ -2831,7 +2843,7 @@ static int group_append(hlala_inflater* f, const hlala_bam_rec* dRecs, int64_t n
 static int group_finish(hlala_inflater* f, int32_t long_read_mode, uint32_t* perm, uint8_t* flag, hlala_bam_group_stats* stats, bool* noMemory)
 {
     GroupState& G = f->grp;
-    *noMemory = false;
+    *noMemory = false; G.finished = false;
     DevGuard g(f->device);
     hipStream_t st = f->slot[0].stream;
     hipError_t e = hipSuccess;
@@ -2875,6 +2887,7 @@ static int group_finish(hlala_inflater* f, int32_t long_read_mode, uint32_t* per
     if(e != hipSuccess) return failed("sort / k_grp_mark / k_grp_fold / k_grp_emit / download");
     stats->n_recs = G.n; stats->n_runs = (int64_t)lastRun[0] + lastRun[1]; stats->n_collided_runs = (int64_t)hCounts[0]; stats->n_units_complete = (int64_t)hCounts[1]; stats->n_units_incomplete = (int64_t)hCounts[2];
     stats->ms_append = G.msAppend; stats->ms_sort = ms(2, 3); stats->ms_mark = ms(3, 4); stats->ms_fold = ms(4, 5); stats->ms_emit = ms(5, 6); stats->ms_d2h = ms(6, 7);
+    G.finished = true; G.nComplete = stats->n_units_complete;
     return HLALA_OK;
 }
 extern "C" int hlala_bam_group_rounds(hlala_inflater* f, const hlala_bam_rec* recs, int64_t n, const uint8_t* bytes, size_t n_bytes, const int64_t* round_recs, int32_t n_rounds,
@@ -2943,13 +2956,183 @@ static int bam_group_hook(void* inflater, int64_t n, int32_t long_read_mode, uin
     return HLALA_OK;
 }
 
+// ---- the read-name order of names on the device (include/hlala_gpu.h; kernel_bamnameorder.hip).  One stretch of the scan's stream per round: key, sort (by key, then --
+// beyond the first round -- stably by segment), mark, the scan, scatter; the host reads one count per round (the names still unresolved) and stops at zero.
+static hipError_t nam_grow(hlala_inflater* f, int which, size_t bytes)
+{
+    ScanBuf& b = f->nam.buf[which];
+    if(bytes <= b.cap) return hipSuccess;
+    if(b.p) { (void)hipFree(b.p); b.p = nullptr; b.cap = 0; }
+    const size_t want = bytes + bytes / 4 + 256;
+    const hipError_t r = hipMalloc(&b.p, want);
+    if(r != hipSuccess) { b.p = nullptr; return r; }
+    b.cap = want;
+    return hipSuccess;
+}
+static hipError_t nam_events(hlala_inflater* f)
+{
+    if(f->nam.evReady) return hipSuccess;
+    for(hipEvent_t& ev : f->nam.ev) if(!ev) { const hipError_t e = hipEventCreate(&ev); if(e != hipSuccess) return e; }
+    f->nam.evReady = true;
+    return hipSuccess;
+}
+// n (> 0) names in device memory: name i is dNames[dOff[i] .. + dLen[i]).  order is host memory.  *noMemory: a device allocation failed, nothing ran.
+static int nam_run(hlala_inflater* f, const u64* dOff, const u32* dLen, u32 n, const uint8_t* dNames, u64 nBytes, int64_t maxRounds, uint32_t* order, hlala_bam_name_order_stats* stats, bool* noMemory)
+{
+    NameOrderState& S = f->nam;
+    *noMemory = false;
+    hipStream_t st = f->slot[0].stream;
+    hipError_t e = hipSuccess;
+    auto failed = [&](const char* what) { f->err = std::string("BAM name order: ") + what + ": " + hipGetErrorString(e); (void)hipStreamSynchronize(st); (void)hipGetLastError(); return HLALA_E_DEVICE; };
+    if((e = nam_events(f)) != hipSuccess) return failed("hipEventCreate");
+    const size_t N = n;
+    size_t cubKey = 0, cubSeg = 0, cubScan = 0;
+    if((e = hipcub::DeviceRadixSort::SortPairs(nullptr, cubKey, (const u64*)nullptr, (u64*)nullptr, (const u32*)nullptr, (u32*)nullptr, N, 0, 64, st)) != hipSuccess) return failed("hipcub::DeviceRadixSort::SortPairs");
+    if((e = hipcub::DeviceRadixSort::SortPairs(nullptr, cubSeg, (const u32*)nullptr, (u32*)nullptr, (const u32*)nullptr, (u32*)nullptr, N, 0, 32, st)) != hipSuccess) return failed("hipcub::DeviceRadixSort::SortPairs");
+    if((e = hipcub::DeviceScan::ExclusiveSum(nullptr, cubScan, (u64*)nullptr, (u64*)nullptr, N + 1, st)) != hipSuccess) return failed("hipcub::DeviceScan::ExclusiveSum");
+    const size_t cubBytes = std::max(std::max(cubKey, cubSeg), cubScan) + 16;
+    static const int four[] = {NAM_IDX0, NAM_IDX1, NAM_SEG0, NAM_SEG1, NAM_GP0, NAM_GP1, NAM_VAL, NAM_P1, NAM_K2, NAM_K2S, NAM_P2, NAM_NEWIDX, NAM_ORDER};
+    for(int w : four) if((e = nam_grow(f, w, N * 4)) != hipSuccess) break;
+    if(e != hipSuccess || (e = nam_grow(f, NAM_KEY, N * 8)) != hipSuccess || (e = nam_grow(f, NAM_KEYS, N * 8)) != hipSuccess || (e = nam_grow(f, NAM_FL, (N + 1) * 8)) != hipSuccess ||
+       (e = nam_grow(f, NAM_FLOFF, (N + 1) * 8)) != hipSuccess || (e = nam_grow(f, NAM_COUNT, 8)) != hipSuccess || (e = nam_grow(f, NAM_CUB, cubBytes)) != hipSuccess) { (void)hipGetLastError(); *noMemory = true; return HLALA_OK; }
+    auto u32buf = [&](int w) { return (u32*)S.buf[w].p; };
+    u32 *idx = u32buf(NAM_IDX0), *idx2 = u32buf(NAM_IDX1), *seg = u32buf(NAM_SEG0), *seg2 = u32buf(NAM_SEG1), *gp = u32buf(NAM_GP0), *gp2 = u32buf(NAM_GP1);
+    u32 *dVal = u32buf(NAM_VAL), *dP1 = u32buf(NAM_P1), *dK2 = u32buf(NAM_K2), *dK2s = u32buf(NAM_K2S), *dP2 = u32buf(NAM_P2), *dNewIdx = u32buf(NAM_NEWIDX), *dOrder = u32buf(NAM_ORDER);
+    u64 *dKey = (u64*)S.buf[NAM_KEY].p, *dKeys = (u64*)S.buf[NAM_KEYS].p, *dFl = (u64*)S.buf[NAM_FL].p, *dFlOff = (u64*)S.buf[NAM_FLOFF].p;
+    unsigned long long* dEqual = (unsigned long long*)S.buf[NAM_COUNT].p;
+    void* dCub = S.buf[NAM_CUB].p;
+    hipEvent_t* ev = S.ev;
+    auto ms = [&](int a, int b) { float t = 0; return hipEventElapsedTime(&t, ev[a], ev[b]) == hipSuccess ? (double)t : 0.0; };
+    e = hipMemsetAsync(dEqual, 0, 8, st);
+    if(e == hipSuccess) { hipLaunchKernelGGL(k_nam_init, dim3((n + 63u) / 64u), dim3(64), 0, st, n, idx, seg, gp); e = hipGetLastError(); }
+    if(e != hipSuccess) return failed("k_nam_init");
+    u32 a = n;
+    for(u32 r = 0; a > 0; r++) {
+        if((int64_t)r >= maxRounds) { (void)hipStreamSynchronize(st); f->err = "BAM name order: names unresolved after the last round"; return HLALA_E_DEVICE; }      // (cannot happen)
+        const u32 nb = (a + 63u) / 64u, nb1 = (a + 64u) / 64u;
+        // after a round every segment of the working set has two names or more: at most a / 2 segments, so many bits of the second sort's key count
+        const u32 maxSegs = r == 0 ? 1u : a / 2u;
+        int segBits = 0; while(segBits < 32 && (1ull << segBits) < maxSegs) segBits++;
+        const u32* p = dP1;
+        e = hipEventRecord(ev[0], st);
+        if(e == hipSuccess) { hipLaunchKernelGGL(k_nam_key, dim3(nb), dim3(64), 0, st, a, n, (const u32*)idx, dOff, dLen, dNames, nBytes, r, dKey, dVal); e = hipGetLastError(); }
+        if(e == hipSuccess) e = hipEventRecord(ev[1], st);
+        if(e == hipSuccess) e = hipcub::DeviceRadixSort::SortPairs(dCub, cubKey, (const u64*)dKey, dKeys, (const u32*)dVal, dP1, (size_t)a, 0, 64, st);
+        if(e == hipSuccess && segBits > 0) {
+            hipLaunchKernelGGL(k_nam_seg, dim3(nb), dim3(64), 0, st, a, (const u32*)dP1, (const u32*)seg, dK2); e = hipGetLastError();
+            if(e == hipSuccess) e = hipcub::DeviceRadixSort::SortPairs(dCub, cubSeg, (const u32*)dK2, dK2s, (const u32*)dP1, dP2, (size_t)a, 0, segBits, st);
+            p = dP2;
+        }
+        if(e == hipSuccess) e = hipEventRecord(ev[2], st);
+        if(e == hipSuccess) { hipLaunchKernelGGL(k_nam_mark, dim3(nb1), dim3(64), 0, st, a, p, (const u64*)dKey, (const u32*)seg, (const u32*)idx, dNewIdx, dFl, dEqual); e = hipGetLastError(); }
+        if(e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(dCub, cubScan, dFl, dFlOff, (size_t)a + 1, st);
+        if(e == hipSuccess) e = hipEventRecord(ev[3], st);
+        if(e == hipSuccess) { hipLaunchKernelGGL(k_nam_scatter, dim3(nb), dim3(64), 0, st, a, n, (const u64*)dFl, (const u64*)dFlOff, (const u32*)dNewIdx, (const u32*)gp, dOrder, idx2, seg2, gp2); e = hipGetLastError(); }
+        if(e == hipSuccess) e = hipEventRecord(ev[4], st);
+        u64 total = 0;
+        if(e == hipSuccess) e = hipMemcpyAsync(&total, dFlOff + a, 8, hipMemcpyDeviceToHost, st);
+        if(e == hipSuccess) e = hipStreamSynchronize(st);
+        if(e != hipSuccess) return failed("k_nam_key / sort / k_nam_mark / k_nam_scatter");
+        stats->n_rounds++; stats->ms_key += ms(0, 1); stats->ms_sort += ms(1, 2); stats->ms_mark += ms(2, 3); stats->ms_scatter += ms(3, 4);
+        const u32 left = (u32)total;
+        if(left > a || left == 1) { f->err = "BAM name order: an impossible count of unresolved names"; return HLALA_E_DEVICE; }      // (cannot happen)
+        std::swap(idx, idx2); std::swap(seg, seg2); std::swap(gp, gp2);
+        a = left;
+    }
+    unsigned long long hEqual = 0;
+    e = hipEventRecord(ev[5], st);
+    if(e == hipSuccess) e = hipMemcpyAsync(order, dOrder, N * 4, hipMemcpyDeviceToHost, st);
+    if(e == hipSuccess) e = hipMemcpyAsync(&hEqual, dEqual, 8, hipMemcpyDeviceToHost, st);
+    if(e == hipSuccess) e = hipEventRecord(ev[6], st);
+    if(e == hipSuccess) e = hipStreamSynchronize(st);
+    if(e != hipSuccess) return failed("download");
+    stats->n = (int64_t)n; stats->n_equal_names = (int64_t)hEqual; stats->ms_d2h = ms(5, 6);
+    return HLALA_OK;
+}
+extern "C" int hlala_bam_name_order(hlala_inflater* f, const uint64_t* name_off, const uint32_t* name_len, int64_t n, const uint8_t* bytes, size_t n_bytes, uint32_t* order,
+                                    hlala_bam_name_order_stats* stats)
+{
+    if(!f) { int ndev = 0; if(hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return HLALA_E_DEVICE; } return HLALA_E_ARG; }
+    f->err.clear();
+    uint32_t maxLen = 0;
+    const char* bad = hlala_nameorder::nam_check_args(name_off, name_len, n, bytes, n_bytes, order, stats, &maxLen);
+    if(bad) { f->err = std::string("hlala_bam_name_order: ") + bad; return HLALA_E_ARG; }
+    const auto tWall = std::chrono::steady_clock::now();
+    memset(stats, 0, sizeof(*stats));
+    if(n == 0) return HLALA_OK;
+    DevGuard g(f->device);
+    hipStream_t st = f->slot[0].stream;
+    hipError_t e = hipSuccess;
+    auto failed = [&](const char* what) { f->err = std::string("hlala_bam_name_order: ") + what + ": " + hipGetErrorString(e); (void)hipStreamSynchronize(st); (void)hipGetLastError(); return HLALA_E_DEVICE; };
+    if((e = nam_events(f)) != hipSuccess) return failed("hipEventCreate");
+    if((e = nam_grow(f, NAM_IN_OFF, (size_t)n * 8)) != hipSuccess || (e = nam_grow(f, NAM_IN_LEN, (size_t)n * 4)) != hipSuccess || (e = nam_grow(f, NAM_IN_BYTES, n_bytes)) != hipSuccess) return failed("hipMalloc");
+    u64* dOff = (u64*)f->nam.buf[NAM_IN_OFF].p; u32* dLen = (u32*)f->nam.buf[NAM_IN_LEN].p; uint8_t* dBytes = (uint8_t*)f->nam.buf[NAM_IN_BYTES].p;
+    e = hipEventRecord(f->nam.ev[5], st);
+    if(e == hipSuccess) e = hipMemcpyAsync(dOff, name_off, (size_t)n * 8, hipMemcpyHostToDevice, st);
+    if(e == hipSuccess) e = hipMemcpyAsync(dLen, name_len, (size_t)n * 4, hipMemcpyHostToDevice, st);
+    if(e == hipSuccess) e = hipMemcpyAsync(dBytes, bytes, n_bytes, hipMemcpyHostToDevice, st);
+    if(e == hipSuccess) e = hipEventRecord(f->nam.ev[6], st);
+    if(e == hipSuccess) e = hipStreamSynchronize(st);
+    if(e != hipSuccess) return failed("upload");
+    float tUp = 0; (void)hipEventElapsedTime(&tUp, f->nam.ev[5], f->nam.ev[6]);
+    bool noMemory = false;
+    const int rc = nam_run(f, dOff, dLen, (u32)n, dBytes, (u64)n_bytes, hlala_nameorder::nam_max_rounds(maxLen), order, stats, &noMemory);
+    if(rc != HLALA_OK) return rc;
+    if(noMemory) { f->err = "hlala_bam_name_order: no device memory for the passes"; return HLALA_E_DEVICE; }
+    stats->ms_h2d = (double)tUp;
+    stats->ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tWall).count();
+    return HLALA_OK;
+}
+// The decoder's sort phase with HLALA_SEEDS_GPU_SORT: directly behind group_finish, on its stream and over its arrays -- the first records of clean, complete runs are
+// selected in run order (k_nam_select, a scan, k_nam_units), their names ordered where they lie in the arena.  Nothing is uploaded.  *available = false (with HLALA_OK):
+// the grouping passes have not run over this sample, or a device allocation failed -- the host orders the sample itself.
+static int bam_sort_hook(void* inflater, int64_t m, uint32_t* order, hlala_bam_name_order_stats* stats, bool* available, std::string* err)
+{
+    hlala_inflater* f = (hlala_inflater*)inflater;
+    if(!f || !stats || !available || m < 0 || (m && !order)) return HLALA_E_ARG;
+    f->err.clear();
+    memset(stats, 0, sizeof(*stats));
+    GroupState& G = f->grp;
+    *available = G.ok && (G.finished || G.n == 0);
+    if(!*available) return HLALA_OK;
+    auto fail = [&](int rc) { if(err) *err = f->err; return rc; };
+    if(m != G.nComplete) { f->err = "BAM name order: the host holds " + std::to_string(m) + " units of clean runs, the grouping passes found " + std::to_string(G.nComplete); return fail(HLALA_E_DEVICE); }
+    if(m == 0) return HLALA_OK;
+    const auto tWall = std::chrono::steady_clock::now();
+    DevGuard g(f->device);
+    hipStream_t st = f->slot[0].stream;
+    hipError_t e = hipSuccess;
+    auto failed = [&](const char* what) { f->err = std::string("BAM name order: ") + what + ": " + hipGetErrorString(e); (void)hipStreamSynchronize(st); (void)hipGetLastError(); return fail(HLALA_E_DEVICE); };
+    const u32 N = (u32)G.n, M = (u32)m;
+    size_t cubScan = 0;
+    if((e = hipcub::DeviceScan::ExclusiveSum(nullptr, cubScan, (u32*)nullptr, (u32*)nullptr, (size_t)N + 1, st)) != hipSuccess) return failed("hipcub::DeviceScan::ExclusiveSum");
+    if((e = nam_grow(f, NAM_SEL, ((size_t)N + 1) * 4)) != hipSuccess || (e = nam_grow(f, NAM_SELOFF, ((size_t)N + 1) * 4)) != hipSuccess || (e = nam_grow(f, NAM_IN_OFF, (size_t)M * 8)) != hipSuccess ||
+       (e = nam_grow(f, NAM_IN_LEN, (size_t)M * 4)) != hipSuccess || (e = nam_grow(f, NAM_CUB, cubScan + 16)) != hipSuccess) { (void)hipGetLastError(); *available = false; return HLALA_OK; }
+    u32* dSel = (u32*)f->nam.buf[NAM_SEL].p; u32* dSelOff = (u32*)f->nam.buf[NAM_SELOFF].p; u64* dOff = (u64*)f->nam.buf[NAM_IN_OFF].p; u32* dLen = (u32*)f->nam.buf[NAM_IN_LEN].p;
+    hipLaunchKernelGGL(k_nam_select, dim3((N + 64u) / 64u), dim3(64), 0, st, N, (const uint8_t*)G.buf[GRP_FLAG].p, dSel); e = hipGetLastError();
+    if(e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(f->nam.buf[NAM_CUB].p, cubScan, dSel, dSelOff, (size_t)N + 1, st);
+    if(e == hipSuccess) { hipLaunchKernelGGL(k_nam_units, dim3((N + 63u) / 64u), dim3(64), 0, st, N, (const u32*)dSel, (const u32*)dSelOff, (const u32*)G.buf[GRP_VAL_OUT].p, (const u32*)G.buf[GRP_META].p,
+                                                (const u64*)G.buf[GRP_NAMEOFF].p, M, dOff, dLen); e = hipGetLastError(); }
+    u32 found = 0;
+    if(e == hipSuccess) e = hipMemcpyAsync(&found, dSelOff + N, 4, hipMemcpyDeviceToHost, st);
+    if(e == hipSuccess) e = hipStreamSynchronize(st);
+    if(e != hipSuccess) return failed("k_nam_select / k_nam_units");
+    if(found != M) { f->err = "BAM name order: " + std::to_string(found) + " first records of clean, complete runs, the grouping passes counted " + std::to_string(m); return fail(HLALA_E_DEVICE); }
+    bool noMemory = false;
+    const int rc = nam_run(f, dOff, dLen, M, (const uint8_t*)G.buf[GRP_NAMES].p, (u64)G.nameBytes, hlala_nameorder::nam_max_rounds(hlala_nameorder::NAM_MAX_LEN), order, stats, &noMemory);
+    if(rc != HLALA_OK) return fail(rc);
+    if(noMemory) *available = false;
+    stats->ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tWall).count();
+    return HLALA_OK;
+}
+
 extern "C" int hlala_abi_sizeof(const char* name)
 {
     if(!name) return -1;
     const std::string n(name);
 #define SZ(t) if(n == #t) return (int)sizeof(t);
     SZ(hlala_graph_desc) SZ(hlala_contigs_desc) SZ(hlala_params) SZ(hlala_graph_info) SZ(hlala_batch_in) SZ(hlala_seeds_in)
-    SZ(hlala_chains_out) SZ(hlala_pairs_out) SZ(hlala_batch_stats) SZ(hlala_exon_in) SZ(hlala_call_out) SZ(hlala_locus_desc) SZ(hlala_exon_positions_out) SZ(hlala_filter_params) SZ(hlala_filter_stats) SZ(hlala_insert_size_out) SZ(hlala_locus_info) SZ(hlala_locus_report_in) SZ(hlala_locus_report_out) SZ(hlala_unit_stats_out) SZ(hlala_pairs_packed_out) SZ(hlala_bgzf_block) SZ(hlala_inflate_stats) SZ(hlala_bam_rec) SZ(hlala_bam_scan_in) SZ(hlala_bam_scan_stats) SZ(hlala_bam_group_stats)
+    SZ(hlala_chains_out) SZ(hlala_pairs_out) SZ(hlala_batch_stats) SZ(hlala_exon_in) SZ(hlala_call_out) SZ(hlala_locus_desc) SZ(hlala_exon_positions_out) SZ(hlala_filter_params) SZ(hlala_filter_stats) SZ(hlala_insert_size_out) SZ(hlala_locus_info) SZ(hlala_locus_report_in) SZ(hlala_locus_report_out) SZ(hlala_unit_stats_out) SZ(hlala_pairs_packed_out) SZ(hlala_bgzf_block) SZ(hlala_inflate_stats) SZ(hlala_bam_rec) SZ(hlala_bam_scan_in) SZ(hlala_bam_scan_stats) SZ(hlala_bam_group_stats) SZ(hlala_bam_name_order_stats)
 #undef SZ
     return -1;
 }

@@ -242,6 +242,7 @@ struct hlala_seed_batch {
     int64_t parse_counts[3] = {0, 0, 0};        // records scanned on the GPU, rounds scanned there, rounds that fell back to the host's hop and parse
     int64_t transfer_bytes[2] = {0, 0};         // bytes the GPU paths of the decoder moved to the device and back
     int64_t group_counts[3] = {0, 0, 0};        // HLALA_SEEDS_GPU_GROUP: records grouped on the GPU, collided runs the host regrouped, 1 = the whole sample was grouped by the host instead
+    int64_t sort_counts[3] = {0, 0, 0};         // HLALA_SEEDS_GPU_SORT: units ordered on the GPU, units of collided runs the host merged in, 1 = the whole sample was ordered by the host instead
     bool pinned = false;
     // page-locking window by window (hlala_seed_batch_pin(S, 2)): per bulk array the bytes locked so far, and the regions to unlock
     bool pin_lazy = false; std::mutex pin_mu; std::vector<size_t> pin_cursor; std::vector<std::pair<void*, size_t>> pin_regions;
@@ -386,6 +387,7 @@ bam_inflate_hook_t g_bam_inflate_hook = nullptr;               // set by the GPU
 bam_inflate_crc_hook_t g_bam_inflate_crc_hook = nullptr;       // ... (HLALA_SEEDS_VERIFY_CRC)
 bam_scan_hook_t g_bam_scan_hook = nullptr;                     // ... (HLALA_SEEDS_GPU_PARSE)
 bam_group_hook_t g_bam_group_hook = nullptr;                   // ... (HLALA_SEEDS_GPU_GROUP)
+bam_sort_hook_t g_bam_sort_hook = nullptr;                     // ... (HLALA_SEEDS_GPU_SORT)
 }  // namespace hlala_host
 
 // (host code: no device involved)
@@ -493,6 +495,8 @@ try {
     if(gpuParse && (!gpu || !g_bam_scan_hook)) { g_bam_error = "HLALA_SEEDS_GPU_PARSE needs hlala_bam_extract_seeds_gpu"; return HLALA_E_ARG; }
     const bool gpuGroup = (flags & HLALA_SEEDS_GPU_GROUP) != 0;
     if(gpuGroup && (!gpuParse || !g_bam_group_hook)) { g_bam_error = "HLALA_SEEDS_GPU_GROUP needs HLALA_SEEDS_GPU_PARSE"; return HLALA_E_ARG; }
+    const bool gpuSort = (flags & HLALA_SEEDS_GPU_SORT) != 0;
+    if(gpuSort && (!gpuGroup || !g_bam_sort_hook)) { g_bam_error = "HLALA_SEEDS_GPU_SORT needs HLALA_SEEDS_GPU_GROUP"; return HLALA_E_ARG; }
     int T = n_threads;
     // Default: at most 32 threads.  Measured on a 256-thread host (tools/gpu_decode_threads.sh, 8.4 M pairs, 2.6 GB of BAM): 5.2 s on 8 threads, 3.5 on 16, 2.85 on 32,
     // 3.0 on 64, 3.3-3.7 on 128 -- the phases are passes over ~12 GB of inflated records bound by memory latency and by the first touch of their
@@ -844,6 +848,7 @@ try {
     tPhase = Clock::now();
     std::vector<std::vector<Rec>>& precs = W->precs; precs.resize(NPART);       // records of a partition sorted by (hash, name, file order)
     std::vector<std::vector<Unit>> punits(NPART);         // all units of the partition (complete or not)
+    std::vector<std::vector<Unit>> pcollided(NPART);      // HLALA_SEEDS_GPU_SORT: the units of the partition's collided runs, which the device does not order, apart from the others
     std::vector<int64_t> pIncomplete(NPART, 0);
     auto rec_name = [&](const Rec& r) { return r.name(); };
     // Sorted by (hash, file order) on 24-byte integer keys; the NAMES are looked at once per record afterwards, in sorted order and prefetched (they lie in the
@@ -898,7 +903,9 @@ try {
                     R.push_back(to_rec(x, cb));
                 }
                 auto same_name = [&](const Rec& a, const Rec& b) { return a.nameLen == b.nameLen && memcmp(rec_name(a), rec_name(b), a.nameLen) == 0; };
+                std::vector<Unit>& UC = gpuSort ? pcollided[(size_t)p] : U;
                 auto unit_of = [&](size_t i, size_t j, bool known, bool complete) {
+                    std::vector<Unit>& U = known ? punits[(size_t)p] : UC;
                     if(!known) { bool prim[2] = {false, false}; for(size_t k = i; k < j; k++) if(R[k].flags & 2) prim[R[k].which & 1] = true; complete = long_read_mode ? prim[0] : (prim[0] && prim[1]); }
                     if(complete) { Unit u; u.name = rec_name(R[i]); u.nameLen = R[i].nameLen; u.part = (uint32_t)p; u.first = (uint32_t)i; u.count = (uint32_t)(j - i); U.push_back(u); }
                     else pIncomplete[(size_t)p]++;
@@ -976,11 +983,48 @@ try {
     { size_t n = 0; for(auto& u : punits) n += u.size(); units.reserve(n); for(auto& u : punits) { units.insert(units.end(), u.begin(), u.end()); std::vector<Unit>().swap(u); } }
     for(int p = 0; p < NPART; p++) S->n_incomplete += pIncomplete[(size_t)p];
     S->n_seeds = (int64_t)units.size() + S->n_incomplete;
+    for(const auto& u : pcollided) S->n_seeds += (int64_t)u.size();
     S->seconds[3] = since(tPhase);
 
     // ---------------------------------------------------------------- sort: read-name order (parallel sample sort)
     tPhase = Clock::now();
-    if(T > 1 && units.size() > 100000) {
+    // HLALA_SEEDS_GPU_SORT: `units` holds the units of clean runs in run order -- what the device has selected behind its grouping passes and ordered (hlala_bam_name_order
+    // over the names in its arena).  They are permuted through its answer, once that is seen to be a permutation; the units the host split out of collided runs are put
+    // in order here and merged in.  Where the device has no answer the whole sample takes the host's sort below.
+    bool sortedOnGpu = false;
+    if(gpuSort) {
+        std::vector<Unit> collided;
+        for(auto& u : pcollided) { collided.insert(collided.end(), u.begin(), u.end()); std::vector<Unit>().swap(u); }
+        const size_t m = units.size();
+        bool available = false;
+        if(groupedOnGpu && m < ((size_t)1 << 31)) {
+            Buf<uint32_t> order; order.alloc(m);                       // (not cleared: the device's answer fills it)
+            hlala_bam_name_order_stats ns; std::string herr;
+            const int rc = g_bam_sort_hook(gpuInflater, (int64_t)m, order.data(), &ns, &available, &herr);
+            if(rc != HLALA_OK) throw Fail("BAM name order on the GPU failed: " + herr);
+            if(available) {
+                std::vector<uint64_t> seen((m + 63) / 64, 0);
+                for(size_t k = 0; k < m; k++) {
+                    const uint32_t v = order[k];
+                    if((size_t)v >= m || (seen[v >> 6] >> (v & 63) & 1)) throw Fail("BAM name order on the GPU: the order is not a permutation of the units");
+                    seen[v >> 6] |= 1ull << (v & 63);
+                }
+                std::vector<Unit> sorted(m);
+                parallel_for((int64_t)((m + 65535) / 65536), T, [&](int64_t c, int) { const size_t z = std::min(m, (size_t)(c + 1) * 65536); for(size_t k = (size_t)c * 65536; k < z; k++) sorted[k] = units[order[k]]; });
+                std::sort(collided.begin(), collided.end(), name_less);
+                if(collided.empty()) units.swap(sorted);
+                else { units.resize(m + collided.size()); std::merge(sorted.begin(), sorted.end(), collided.begin(), collided.end(), units.begin(), name_less); }
+                if(getenv("HLALA_BAM_DEBUG")) {
+                    for(size_t k = 1; k < units.size(); k++) if(!name_less(units[k - 1], units[k])) throw Fail("BAM name order on the GPU: units out of read-name order");
+                    fprintf(stderr, "bam-debug: name order on the GPU: %lld units in %lld rounds, %zu merged in by the host; key %.3f, sort %.3f, mark %.3f, scatter %.3f, download %.3f ms\n",
+                            (long long)ns.n, (long long)ns.n_rounds, collided.size(), ns.ms_key, ns.ms_sort, ns.ms_mark, ns.ms_scatter, ns.ms_d2h);
+                }
+                sortedOnGpu = true; S->sort_counts[0] = (int64_t)m; S->sort_counts[1] = (int64_t)collided.size();
+            }
+        }
+        if(!sortedOnGpu) { units.insert(units.end(), collided.begin(), collided.end()); S->sort_counts[2] = 1; }
+    }
+    if(!sortedOnGpu && T > 1 && units.size() > 100000) {
         const int NB = T * 4;
         std::vector<Unit> sample;
         const size_t stepS = std::max<size_t>(1, units.size() / (size_t)(NB * 64));
@@ -1007,7 +1051,7 @@ try {
         });
         parallel_for(NB, T, [&](int64_t bk, int) { std::sort(sorted.begin() + bstart[(size_t)bk], sorted.begin() + bstart[(size_t)bk + 1], name_less); });
         units.swap(sorted);
-    } else std::sort(units.begin(), units.end(), name_less);
+    } else if(!sortedOnGpu) std::sort(units.begin(), units.end(), name_less);
     S->seconds[4] = since(tPhase);
 
     // ---------------------------------------------------------------- layout
@@ -1135,6 +1179,12 @@ extern "C" int hlala_seed_batch_group_counts(const hlala_seed_batch* S, int64_t*
 {
     if(!S || !counts) return HLALA_E_ARG;
     for(int i = 0; i < 3; i++) counts[i] = S->group_counts[i];
+    return HLALA_OK;
+}
+extern "C" int hlala_seed_batch_sort_counts(const hlala_seed_batch* S, int64_t counts[3])
+{
+    if(!S || !counts) return HLALA_E_ARG;
+    for(int i = 0; i < 3; i++) counts[i] = S->sort_counts[i];
     return HLALA_OK;
 }
 extern "C" int hlala_seed_batch_transfer_bytes(const hlala_seed_batch* S, int64_t* bytes)

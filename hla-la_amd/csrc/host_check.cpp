@@ -8,6 +8,7 @@
 #include "crc32_core.h"
 #include "bam_scan_model.h"
 #include "bam_group_model.h"
+#include "bam_nameorder_model.h"
 
 static thread_local std::string g_err;
 
@@ -113,6 +114,15 @@ int hlala_host_bam_group_model(const hlala_bam_rec* recs, int64_t n, const uint8
     const char* why = nullptr;
     const int rc = hlala_bamgroup::group_model(recs, n, bytes, n_bytes, long_read_mode, perm, flag, stats, &why);
     g_err = why ? std::string("hlala_host_bam_group_model: ") + why : std::string();
+    return rc;
+}
+// The ordering passes of the device (kernel_bamnameorder.hip) run serially over the same core (bam_nameorder_model.h): the arguments, the return codes and every output
+// of hlala_bam_name_order but the device times, without a device.
+int hlala_host_bam_name_order_model(const uint64_t* name_off, const uint32_t* name_len, int64_t n, const uint8_t* bytes, size_t n_bytes, uint32_t* order, hlala_bam_name_order_stats* stats)
+{
+    const char* why = nullptr;
+    const int rc = hlala_nameorder::name_order_model(name_off, name_len, n, bytes, n_bytes, order, stats, &why);
+    g_err = why ? std::string("hlala_host_bam_name_order_model: ") + why : std::string();
     return rc;
 }
 }

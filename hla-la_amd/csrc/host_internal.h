@@ -71,6 +71,11 @@ extern bam_scan_hook_t g_bam_scan_hook;
 // appended (in the order of the rounds).  *available = false (with HLALA_OK): the device holds another count or could not allocate -- the host groups the sample itself.
 typedef int (*bam_group_hook_t)(void* inflater, int64_t n, int32_t long_read_mode, uint32_t* perm, uint8_t* flag, hlala_bam_group_stats* stats, bool* available, std::string* err);
 extern bam_group_hook_t g_bam_group_hook;
+// The sort phase on the GPU (HLALA_SEEDS_GPU_SORT): the fourth hook.  Directly behind the group hook's passes: order[m] of hlala_bam_name_order over the m first records of
+// clean, complete runs -- the host's units of clean runs, in run order.  *available = false (with HLALA_OK): the device holds no grouped sample or could not allocate
+// -- the host orders the sample itself.
+typedef int (*bam_sort_hook_t)(void* inflater, int64_t m, uint32_t* order, hlala_bam_name_order_stats* stats, bool* available, std::string* err);
+extern bam_sort_hook_t g_bam_sort_hook;
 // hlala_bam_extract_seeds_opt (gpu = false) and hlala_bam_extract_seeds_gpu (gpu = true: the hook above inflates with `inflater`)
 int bam_extract_seeds_impl(const char* path, int32_t n_intervals, const hlala_bam_interval* iv, int32_t long_read_mode, int32_t n_threads, int32_t flags, bool gpu, void* inflater, hlala_seed_batch** out);
 

@@ -622,6 +622,31 @@ int  hlala_bam_group_rounds(hlala_inflater* inf, const hlala_bam_rec* recs, int6
 /* counts[3]: records grouped on the GPU, collided runs the host regrouped, 1 if the whole sample was grouped by the host instead */
 int  hlala_seed_batch_group_counts(const hlala_seed_batch* s, int64_t* counts);
 
+/* ------------------------------------------------------------------------------------------
+ * Ordering names on the GPU (opt-in): the fifth stage of the GPU decode, the read-name order of a sample's units (csrc/kernel_bamnameorder.hip; the rules are
+ * csrc/bam_nameorder_core.h, which the host runs as a model).  The order is memcmp on the first min(la, lb) bytes, then the shorter name first; equal names by
+ * ascending input index.  MSD refinement in rounds of 7 bytes: k_nam_key gathers a 64-bit key (7 bytes big-endian, the count of valid bytes below them) for every
+ * name still in a segment of more than one, hipcub sorts by (segment, key), k_nam_mark splits the segments, a scan and k_nam_scatter write resolved names to their
+ * final places and compact the rest.  The host reads one count per round and stops at zero, at the latest after ceil(max name_len / 7) + 1 rounds.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct {
+    int64_t n, n_rounds, n_equal_names;         /* n_equal_names: names that equal the name before them in the order (n minus the distinct names) */
+    double ms_h2d, ms_key, ms_sort, ms_mark, ms_scatter, ms_d2h, ms_wall;
+} hlala_bam_name_order_stats;
+/* Name i is bytes[name_off[i] .. + name_len[i]); names may overlap and lie at any alignment.  order[k]: the input index of the k-th name.  All arguments are host
+ * pointers.  Checked before anything is uploaded (HLALA_E_ARG; hlala_inflater_last_error says which): n >= 2^31, a name that leaves the byte buffer, name_len 0 or
+ * above 65535, null pointers with n > 0.  n == 0: HLALA_OK with zeroed stats.  HLALA_E_DEVICE without a GPU (no inflater exists then). */
+int  hlala_bam_name_order(hlala_inflater* inf, const uint64_t* name_off, const uint32_t* name_len, int64_t n, const uint8_t* bytes, size_t n_bytes, uint32_t* order,
+                          hlala_bam_name_order_stats* stats);
+/* Flag of hlala_bam_extract_seeds_gpu (HLALA_E_ARG without HLALA_SEEDS_GPU_GROUP): the decoder's sort phase on the device as well.  Directly behind the grouping
+ * passes the device selects the first records of clean, complete runs -- the units, in run order -- and orders their names in the arena that is already there;
+ * the host permutes its units through the answer (checked to be a permutation) and merges in, by its own comparison, the units it split out of collided runs.  The
+ * whole sample is ordered by the host's own sort as without the flag where the grouping stage handed the sample back or a device allocation fails.  The sample is
+ * the same to the byte. */
+#define HLALA_SEEDS_GPU_SORT 16
+/* counts[3]: units ordered on the GPU, units merged in by the host (from collided runs), 1 if the host ordered the whole sample instead; (0, 0, 0) without the flag */
+int  hlala_seed_batch_sort_counts(const hlala_seed_batch* s, int64_t counts[3]);
+
 /* Page-locked host memory for the buffers a caller hands to hlala_batch_create / hlala_batch_get_pairs_packed / the getters: transfers from and
  * to such buffers are true DMA (asynchronous, full PCIe rate); pageable buffers work everywhere, at about a third of the rate.  hlala_host_register
  * pins an existing allocation in place (e.g. the arrays of a seed batch: hlala_seed_batch_pin), hlala_host_unregister undoes it.  */
@@ -960,7 +985,7 @@ int  hlala_abi_sizeof(const char* struct_name);
  * 6 = hlala_inflater_* / hlala_bgzf_inflate / hlala_bam_extract_seeds_gpu / hlala_seed_batch_inflate_counts exist (additive);
  * 7 = hlala_bam_scan / hlala_bam_scan_status_text and their structs, HLALA_SEEDS_GPU_PARSE, hlala_seed_batch_parse_counts / _transfer_bytes exist (additive).
  * Symbols that are purely additive no longer change it (hlala_set_pair_overflow; hlala_bgzf_inflate_crc, HLALA_SEEDS_VERIFY_CRC, hlala_seed_batch_crc_counts;
- * hlala_bam_group / _rounds, HLALA_SEEDS_GPU_GROUP, hlala_seed_batch_group_counts): a caller
+ * hlala_bam_group / _rounds, HLALA_SEEDS_GPU_GROUP, hlala_seed_batch_group_counts; hlala_bam_name_order, HLALA_SEEDS_GPU_SORT, hlala_seed_batch_sort_counts): a caller
  * detects them by the presence of the symbol.  A caller compares
  * hlala_abi_version() with the HLALA_ABI_VERSION it was compiled against and refuses to run on a mismatch (hla-la_amd/__init__.py and
  * hla-la_amd/host/hlala_host.hpp do). */

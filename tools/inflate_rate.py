@@ -14,7 +14,10 @@ and the share of the kept records that is tags (what compaction saves).  There i
 round --, and hlala_bgzf_inflate_crc on all blocks reports the summed device time of k_bgzf_crc32 beside that of k_bgzf_inflate over the same chunks.  The cost of the flag
 is read against the flag-off runs of the same call; on the host decoder it is the cost of the host's own CRC pass on the threads of that run.
 The fourth path (its output is meant for profiles/bam_group_gpu.txt): HLALA_SEEDS_GPU_PARSE | HLALA_SEEDS_GPU_GROUP in the same alternation; its group phase and wall clock are
-read against the third path's of the same call, and hlala_bam_group alone on the descriptors of the first --scan-mb MiB reports the device time per pass."""
+read against the third path's of the same call, and hlala_bam_group alone on the descriptors of the first --scan-mb MiB reports the device time per pass.
+The fifth path (its output is meant for profiles/bam_nameorder_gpu.txt): HLALA_SEEDS_GPU_PARSE | HLALA_SEEDS_GPU_GROUP | HLALA_SEEDS_GPU_SORT in the same alternation; its sort
+phase and wall clock are read against the fourth path's of the same call, and hlala_bam_name_order alone on the unit names of the first --scan-mb MiB reports the device
+time per pass and the rounds it took."""
 import argparse
 import os
 import sys
@@ -95,6 +98,30 @@ def group_alone(P, inf, recs, comp, args):
     print("    ms per pass, median (min .. max) of %d calls: %s" % (args.runs, "  ".join("%s %.3f (%.3f .. %.3f)" % (k, float(np.median(t[k])), min(t[k]), max(t[k])) for k in passes)))
     dev = sum(float(np.median(t[k])) for k in ("append", "sort", "mark", "fold", "emit"))
     print("    append + sort + mark + fold + emit: %.3f ms = %.1f M descriptors/s" % (dev, st.n_recs / 1e6 / max(1e-9, dev / 1e3)))
+    return perm, flag
+
+
+def name_order_alone(P, inf, recs, comp, perm, flag, args):
+    """hlala_bam_name_order on the names of the units hlala_bam_group has just found: the first records of clean, complete runs, in run order (host memory: the upload is
+    part of the call and timed on its own; the decoder uploads nothing)"""
+    first = perm[(flag & 5) == 5]
+    off = recs["rec_off"][first].astype(np.uint64) + 32; ln = recs["nameLen"][first].astype(np.uint32)
+    passes = ("h2d", "key", "sort", "mark", "scatter", "d2h", "wall")
+    t = {k: [] for k in passes}
+    for i in range(args.runs + 1):
+        rc, order, st = inf.bam_name_order(off, ln, comp)
+        assert rc == 0, inf.last_error()
+        if i:
+            for k in passes:
+                t[k].append(getattr(st, "ms_" + k))
+    b = comp.tobytes()
+    names = [b[int(o):int(o) + int(k)] for o, k in zip(off, ln)]
+    assert all(names[int(order[k - 1])] < names[int(order[k])] for k in range(1, len(order))), "the device's order does not ascend"
+    print("hlala_bam_name_order alone: %d unit names of %d .. %d bytes (%.3f GB of compact bytes uploaded with them), %d rounds, %d equal names; the order ascends (checked here)" % (
+        st.n, int(ln.min()), int(ln.max()), comp.size / 1e9, st.n_rounds, st.n_equal_names))
+    print("    ms per pass summed over the rounds, median (min .. max) of %d calls: %s" % (args.runs, "  ".join("%s %.3f (%.3f .. %.3f)" % (k, float(np.median(t[k])), min(t[k]), max(t[k])) for k in passes)))
+    dev = sum(float(np.median(t[k])) for k in ("key", "sort", "mark", "scatter"))
+    print("    key + sort + mark + scatter: %.3f ms = %.1f M names/s" % (dev, st.n / 1e6 / max(1e-9, dev / 1e3)))
 
 
 def main():
@@ -147,21 +174,22 @@ def main():
 
     def run(label, opener, timed):
         t = time.time(); S = opener(); wall = time.time() - t
-        tm = S.timing(); cnt = S.inflate_counts(); pc = S.parse_counts(); tb = S.transfer_bytes(); cc = S.crc_counts(); gc = S.group_counts(); units = S.n_units; S.close()
+        tm = S.timing(); cnt = S.inflate_counts(); pc = S.parse_counts(); tb = S.transfer_bytes(); cc = S.crc_counts(); gc = S.group_counts(); sc = S.sort_counts(); units = S.n_units; S.close()
         if timed and args.verify_crc:
             print("%-13s wall %.3f s  %s  threads %d  units %d  blocks gpu/retried/host %d/%d/%d  CRC verified gpu/host/rechecked %d/%d/%d" % (
                 label, wall, "  ".join("%s %.3f" % (k, tm[k]) for k in keys), tm["threads"], units, cnt[0], cnt[1], cnt[2], cc[0], cc[1], cc[2]))
         elif timed:
-            print("%-15s wall %.3f s  %s  threads %d  units %d  blocks gpu/retried/host %d/%d/%d  records on the GPU %d in %d rounds, %d rounds fell back  PCIe up %.3f GB, down %.3f GB  grouped on the GPU %d, runs regrouped %d, by the host %d" % (
-                label, wall, "  ".join("%s %.3f" % (k, tm[k]) for k in keys), tm["threads"], units, cnt[0], cnt[1], cnt[2], pc[0], pc[1], pc[2], tb[0] / 1e9, tb[1] / 1e9, gc[0], gc[1], gc[2]))
-        return tm["inflate"], tm["inflate"] + tm["parse"], wall, tm["group"]
+            print("%-15s wall %.3f s  %s  threads %d  units %d  blocks gpu/retried/host %d/%d/%d  records on the GPU %d in %d rounds, %d rounds fell back  PCIe up %.3f GB, down %.3f GB  grouped on the GPU %d, runs regrouped %d, by the host %d  ordered on the GPU %d, merged in %d, by the host %d" % (
+                label, wall, "  ".join("%s %.3f" % (k, tm[k]) for k in keys), tm["threads"], units, cnt[0], cnt[1], cnt[2], pc[0], pc[1], pc[2], tb[0] / 1e9, tb[1] / 1e9, gc[0], gc[1], gc[2], sc[0], sc[1], sc[2]))
+        return tm["inflate"], tm["inflate"] + tm["parse"], wall, tm["group"], tm["name_sort"]
     host = lambda: P.bam_open_seeds(lib, bam, intervals, threads=args.threads, flags=P.SEEDS_PACKED)                 # noqa: E731
     gpu = (lambda: inf.bam_open_seeds(bam, intervals, threads=args.threads, flags=P.SEEDS_PACKED)) if inf else None      # noqa: E731
     gpu_parse = (lambda: inf.bam_open_seeds(bam, intervals, threads=args.threads, flags=P.SEEDS_PACKED | P.SEEDS_GPU_PARSE)) if inf else None      # noqa: E731
     gpu_group = (lambda: inf.bam_open_seeds(bam, intervals, threads=args.threads, flags=P.SEEDS_PACKED | P.SEEDS_GPU_PARSE | P.SEEDS_GPU_GROUP)) if inf else None      # noqa: E731
-    res = {"host": [], "gpu": [], "gpu+parse": [], "gpu+parse+group": []}
-    order = ["host", "gpu", "gpu+parse", "gpu+parse+group"]
-    openers = {"host": host, "gpu": gpu, "gpu+parse": gpu_parse, "gpu+parse+group": gpu_group}
+    gpu_sort = (lambda: inf.bam_open_seeds(bam, intervals, threads=args.threads, flags=P.SEEDS_PACKED | P.SEEDS_GPU_PARSE | P.SEEDS_GPU_GROUP | P.SEEDS_GPU_SORT)) if inf else None      # noqa: E731
+    res = {"host": [], "gpu": [], "gpu+parse": [], "gpu+parse+group": [], "gpu+parse+group+sort": []}
+    order = ["host", "gpu", "gpu+parse", "gpu+parse+group", "gpu+parse+group+sort"]
+    openers = {"host": host, "gpu": gpu, "gpu+parse": gpu_parse, "gpu+parse+group": gpu_group, "gpu+parse+group+sort": gpu_sort}
     if args.verify_crc:
         V = P.SEEDS_PACKED | P.SEEDS_VERIFY_CRC
         openers["host+crc"] = lambda: P.bam_open_seeds(lib, bam, intervals, threads=args.threads, flags=V)                 # noqa: E731
@@ -177,13 +205,17 @@ def main():
         if len(res[k]) > 1:
             v = [x[0] for x in res[k][1:]]
             print("inflate phase, %s: median %.3f s (%.2f GB/s inflated) of %s" % (k, float(np.median(v)), n_inflated / 1e9 / float(np.median(v)), ["%.3f" % x for x in v]))
-            for j, what in ((1, "inflate + parse phases"), (3, "group phase"), (2, "decode, wall")):
+            for j, what in ((1, "inflate + parse phases"), (3, "group phase"), (4, "sort phase"), (2, "decode, wall")):
                 v = [x[j] for x in res[k][1:]]
                 print("%s, %s: median %.3f s, range %.3f .. %.3f of %d runs" % (what, k, float(np.median(v)), min(v), max(v), len(v)))
     if len(res.get("gpu+parse", [])) > 1 and len(res.get("gpu+parse+group", [])) > 1:
         for j, what in ((3, "group phase"), (2, "decode, wall")):
             a = float(np.median([x[j] for x in res["gpu+parse"][1:]])); b = float(np.median([x[j] for x in res["gpu+parse+group"][1:]]))
             print("HLALA_SEEDS_GPU_GROUP against gpu+parse, %s: %+.3f s (median %.3f with against %.3f without)" % (what, b - a, b, a))
+    if len(res.get("gpu+parse+group", [])) > 1 and len(res.get("gpu+parse+group+sort", [])) > 1:
+        for j, what in ((4, "sort phase"), (2, "decode, wall")):
+            a = float(np.median([x[j] for x in res["gpu+parse+group"][1:]])); b = float(np.median([x[j] for x in res["gpu+parse+group+sort"][1:]]))
+            print("HLALA_SEEDS_GPU_SORT against gpu+parse+group, %s: %+.3f s (median %.3f with against %.3f without)" % (what, b - a, b, a))
     if args.verify_crc:
         for k in ("host", "gpu", "gpu+parse"):
             if len(res[k]) > 1 and len(res[k + "+crc"]) > 1:
@@ -217,7 +249,8 @@ def main():
         if args.scan_mb > 0:
             kept = scan_alone(P, inf, out, intervals, args)
             if kept is not None and len(kept[0]):
-                group_alone(P, inf, kept[0], kept[1], args)
+                perm, flag = group_alone(P, inf, kept[0], kept[1], args)
+                name_order_alone(P, inf, kept[0], kept[1], perm, flag, args)
         inf.close()
     if tmp:
         import shutil
