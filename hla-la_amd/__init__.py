@@ -339,6 +339,20 @@ class SeedBatch:
         self.lib.hlala_seed_batch_sort_counts(self.h, cnt)
         return tuple(int(x) for x in cnt)
 
+    def fill_counts(self):
+        """(units the GPU fills, host units, 1 if the whole sample was laid out and filled by the host instead); all zero without SEEDS_GPU_FILL"""
+        cnt = (C.c_int64 * 3)()
+        self.lib.hlala_seed_batch_fill_counts.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        self.lib.hlala_seed_batch_fill_counts(self.h, cnt)
+        return tuple(int(x) for x in cnt)
+
+    def fill_ms(self):
+        """device milliseconds of the window passes of SEEDS_GPU_FILL so far: (chain, cigar, names, bases, download)"""
+        ms = (C.c_double * 5)()
+        self.lib.hlala_seed_batch_fill_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        self.lib.hlala_seed_batch_fill_ms(self.h, ms)
+        return tuple(float(x) for x in ms)
+
     def inflate_counts(self):
         """(blocks inflated on the GPU, blocks the GPU rejected and the host engine ran again, blocks inflated on the host only)"""
         cnt = (C.c_int64 * 3)()
@@ -366,6 +380,7 @@ SEEDS_GPU_PARSE = 2       # HLALA_SEEDS_GPU_PARSE (Inflater.bam_open_seeds only)
 SEEDS_VERIFY_CRC = 4      # HLALA_SEEDS_VERIFY_CRC (bam_open_seeds and Inflater.bam_open_seeds): the CRC-32 of every BGZF block is compared with that of its inflated bytes
 SEEDS_GPU_GROUP = 8       # HLALA_SEEDS_GPU_GROUP (with SEEDS_GPU_PARSE only): the records are grouped by read name on the GPU as well
 SEEDS_GPU_SORT = 16       # HLALA_SEEDS_GPU_SORT (with SEEDS_GPU_GROUP only): the units are put into read-name order on the GPU as well
+SEEDS_GPU_FILL = 32       # HLALA_SEEDS_GPU_FILL (with SEEDS_GPU_SORT only): the sample is laid out and its windows are filled on the GPU as well
 
 
 def bam_open_seeds(lib, path, intervals, long_read_mode=False, threads=0, flags=0) -> SeedBatch:
@@ -409,6 +424,94 @@ GROUP_START, GROUP_COLLIDED, GROUP_COMPLETE = 1, 2, 4          # flag[] of hlala
 
 class BamNameOrderStats(C.Structure):
     _fields_ = [(k, C.c_int64) for k in ("n", "n_rounds", "n_equal_names")] + [(k, C.c_double) for k in ("ms_h2d", "ms_key", "ms_sort", "ms_mark", "ms_scatter", "ms_d2h", "ms_wall")]
+
+
+class BamFillIn(C.Structure):
+    _fields_ = [("recs", C.c_void_p), ("n", C.c_int64), ("bytes", C.c_void_p), ("n_bytes", C.c_size_t), ("unit_first", C.c_void_p), ("unit_count", C.c_void_p), ("n_units", C.c_int64),
+                ("host_sizes", C.c_void_p), ("n_host_units", C.c_int64), ("long_read_mode", C.c_int32), ("packed", C.c_int32)]
+
+
+BAM_FILL_OUT_FIELDS = (("read_primary", np.int32), ("read_bases", np.uint8), ("read_bases_packed", np.uint8), ("read_quals", np.uint8), ("chain_contig", np.int32), ("chain_pos", np.int32),
+                       ("chain_offset", np.int32), ("chain_as", np.int32), ("chain_reverse", np.uint8), ("cigar_off_end", np.int64), ("cigar", np.uint32), ("name_chars", np.uint8))
+
+
+class BamFillOut(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k, _ in BAM_FILL_OUT_FIELDS]
+
+
+class BamFillStats(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("n_units", "n_host_units", "n_reads", "n_chains", "n_cigar", "n_bases", "n_name_bytes", "bytes_h2d", "bytes_d2h")] + \
+               [(k, C.c_double) for k in ("ms_h2d", "ms_rank", "ms_host", "ms_scan", "ms_src", "ms_chain", "ms_cigar", "ms_names", "ms_bases", "ms_d2h", "ms_wall")]
+
+
+BAM_FILL_HOST, BAM_FILL_MAX_MATE = 0xFFFFFFFF, 16          # HLALA_BAM_FILL_HOST, HLALA_BAM_FILL_MAX_MATE
+
+
+def bam_fill_in(recs, data, unit_first, unit_count, host_sizes=(), long_read_mode=False, packed=False, n=None, n_bytes=None, n_units=None, n_host_units=None):
+    """hlala_bam_fill_in: recs a BAM_REC_DTYPE array grouped by unit, data the bytes rec_off points into, unit_first / unit_count per unit (BAM_FILL_HOST marks a host
+    unit), host_sizes the 3 * nm + 1 sizes of every host unit.  n / n_bytes / n_units / n_host_units: the sizes handed in, where they are to differ from the arrays'
+    (tests).  Returns (struct, the arrays it points into: keep them alive)."""
+    recs = np.ascontiguousarray(recs, BAM_REC_DTYPE); data = np.ascontiguousarray(data, np.uint8)
+    uf = np.ascontiguousarray(unit_first, np.uint32); uc = np.ascontiguousarray(unit_count, np.uint32); hs = np.ascontiguousarray(host_sizes, np.int64).ravel()
+    nm = 1 if long_read_mode else 2
+    p = lambda a: a.ctypes.data if a.size else None
+    a = BamFillIn(p(recs), recs.size if n is None else int(n), p(data), data.size if n_bytes is None else int(n_bytes), p(uf), p(uc), uf.size if n_units is None else int(n_units),
+                  p(hs), hs.size // (3 * nm + 1) if n_host_units is None else int(n_host_units), int(bool(long_read_mode)), int(bool(packed)))
+    return a, (recs, data, uf, uc, hs)
+
+
+def bam_fill_offsets(n_units, long_read_mode=False):
+    """the four offset arrays hlala_bam_fill_create writes: read_off, chain_off, cigar_count [n_reads + 1], name_off [n_units + 1]"""
+    nr = n_units * (1 if long_read_mode else 2)
+    return dict(read_off=np.zeros(nr + 1, np.int64), chain_off=np.zeros(nr + 1, np.int64), cigar_count=np.zeros(nr + 1, np.int64), name_off=np.zeros(n_units + 1, np.int64))
+
+
+def bam_fill_window_arrays(off, first_unit, n_units, long_read_mode=False, packed=False, canary=0xA5):
+    """the slices of hlala_bam_fill_out for units [first_unit, first_unit + n_units), sized from the offsets `off` and filled with `canary`.  Returns (struct, dict of arrays)."""
+    nm = 1 if long_read_mode else 2
+    r0, r1 = first_unit * nm, (first_unit + n_units) * nm
+    ro, co, gc, no = off["read_off"], off["chain_off"], off["cigar_count"], off["name_off"]
+    nb, nc, ng, nn = int(ro[r1] - ro[r0]), int(co[r1] - co[r0]), int(gc[r1] - gc[r0]), int(no[first_unit + n_units] - no[first_unit])
+    npk = ((int(ro[r1]) + r1 + 1) >> 1) - ((int(ro[r0]) + r0 + 1) >> 1)
+    size = dict(read_primary=r1 - r0, read_bases=0 if packed else nb, read_bases_packed=npk if packed else 0, read_quals=nb, chain_contig=nc, chain_pos=nc, chain_offset=nc, chain_as=nc,
+                chain_reverse=nc, cigar_off_end=nc, cigar=ng, name_chars=nn)
+    arrs = {k: np.frombuffer(bytes([canary]) * (np.dtype(dt).itemsize * (size[k] + 1)), dt).copy() for k, dt in BAM_FILL_OUT_FIELDS}       # (one spare element: no array is empty, what lies behind a slice is seen untouched)
+    unused = "read_bases" if packed else "read_bases_packed"
+    out = BamFillOut(*[None if k == unused else arrs[k].ctypes.data for k, _ in BAM_FILL_OUT_FIELDS])
+    return out, arrs, size
+
+
+class BamFill:
+    """hlala_bam_fill: a sample resident on the device, laid out; window() fills the slices of a range of units"""
+
+    def __init__(self, lib, h, off, long_read_mode, packed):
+        self.lib, self.h, self.off, self.long_read_mode, self.packed = lib, h, off, bool(long_read_mode), bool(packed)
+        lib.hlala_bam_fill_window.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.POINTER(BamFillOut), C.POINTER(BamFillStats)]
+        lib.hlala_bam_fill_destroy.argtypes = [C.c_void_p]; lib.hlala_bam_fill_destroy.restype = None
+        lib.hlala_bam_fill_last_error.argtypes = [C.c_void_p]; lib.hlala_bam_fill_last_error.restype = C.c_char_p
+
+    def window(self, first_unit, n_units, canary=0xA5):
+        """(return code, dict of the slices -- each with one spare element behind it that still holds the canary --, BamFillStats)"""
+        st = BamFillStats()
+        in_range = 0 <= first_unit and 0 <= n_units and first_unit + n_units < len(self.off["name_off"])
+        out, arrs, size = bam_fill_window_arrays(self.off, first_unit, n_units, self.long_read_mode, self.packed, canary) if in_range else (BamFillOut(), {}, {})
+        rc = self.lib.hlala_bam_fill_window(self.h, int(first_unit), int(n_units), C.byref(out), C.byref(st))
+        if rc not in (0, -1):
+            raise HlalaError(f"hlala_bam_fill_window failed ({rc}): {self.last_error()}")
+        return rc, arrs, st
+
+    def last_error(self):
+        return self.lib.hlala_bam_fill_last_error(self.h).decode(errors="replace")
+
+    def close(self):
+        if self.h:
+            self.lib.hlala_bam_fill_destroy(self.h); self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 # hlala_bam_rec
@@ -532,6 +635,17 @@ class Inflater:
         if rc not in (0, -1):
             raise HlalaError(f"hlala_bam_name_order failed ({rc}): {self.last_error()}")
         return rc, order[:off.size if rc == 0 else 0], st
+
+    def bam_fill_create(self, fill_in, n_units, long_read_mode=False, packed=False):
+        """hlala_bam_fill_create on the struct of bam_fill_in().  Returns (return code, BamFill or None, offsets dict, BamFillStats); HLALA_E_ARG (-1) is returned, not raised
+        (last_error() says why).  n_units: what the offset arrays are sized for."""
+        off = bam_fill_offsets(n_units, long_read_mode); st = BamFillStats(); h = C.c_void_p()
+        self.lib.hlala_bam_fill_create.argtypes = [C.c_void_p, C.POINTER(BamFillIn), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(BamFillStats)]
+        rc = self.lib.hlala_bam_fill_create(self.h, C.byref(fill_in), off["read_off"].ctypes.data, off["chain_off"].ctypes.data, off["cigar_count"].ctypes.data, off["name_off"].ctypes.data,
+                                            C.byref(h), C.byref(st))
+        if rc not in (0, -1):
+            raise HlalaError(f"hlala_bam_fill_create failed ({rc}): {self.last_error()}")
+        return rc, (BamFill(self.lib, h, off, long_read_mode, packed) if rc == 0 and h.value else None), off, st
 
     def last_error(self):
         return self.lib.hlala_inflater_last_error(self.h).decode(errors="replace")
@@ -932,6 +1046,7 @@ EXPORTED_SYMBOLS = [
     "hlala_bam_scan", "hlala_bam_scan_status_text", "hlala_seed_batch_parse_counts", "hlala_seed_batch_transfer_bytes",
     "hlala_bam_group", "hlala_bam_group_rounds", "hlala_seed_batch_group_counts",
     "hlala_bam_name_order", "hlala_seed_batch_sort_counts",
+    "hlala_bam_fill_create", "hlala_bam_fill_window", "hlala_bam_fill_last_error", "hlala_bam_fill_destroy", "hlala_seed_batch_fill_counts", "hlala_seed_batch_fill_ms",
     "hlala_locus_cluster_kmers", "hlala_type_locus", "hlala_kmer_presence", "hlala_kmer_keep_reads", "hlala_kmer_presence_kept", "hlala_kmer_forget_reads", "hlala_unit_alignment_stats", "hlala_typer_write_summary", "hlala_typer_begin_output", "hlala_locus_write_files", "hlala_locus_write_pairs_file", "hlala_typer_end_output",
 ]
 

@@ -4,6 +4,7 @@
 #include <cstring>
 #include <cstdlib>
 #include <algorithm>
+#include <atomic>
 #include <map>
 #include <mutex>
 #include <chrono>
@@ -34,6 +35,7 @@
 #include "kernel_bamscan.hip"
 #include "kernel_bamgroup.hip"
 #include "kernel_bamnameorder.hip"
+#include "kernel_bamfill.hip"
 
 namespace hlala {
 size_t proj_slab_bytes_host(int stride, int maxNodesPerLevel) { return proj_slab_bytes(stride, maxNodesPerLevel); }
@@ -2371,6 +2373,8 @@ enum { NAM_IN_OFF, NAM_IN_LEN, NAM_IN_BYTES, NAM_SEL, NAM_SELOFF, NAM_IDX0, NAM_
        NAM_FL, NAM_FLOFF, NAM_ORDER, NAM_COUNT, NAM_CUB, NAM_NBUF };
 constexpr int NAM_NEV = 7;
 struct NameOrderState { ScanBuf buf[NAM_NBUF]; hipEvent_t ev[NAM_NEV]{}; bool evReady = false; };
+// HLALA_SEEDS_GPU_FILL: the sample's descriptors (rec_off into `bytes`) and compact bytes, kept round by round behind the scan; the fill hook takes them over
+struct FillKeep { ScanBuf recs, bytes; int64_t n = 0; uint64_t nBytes = 0; bool ok = false; };
 struct hlala_inflater {
     int device = 0; size_t chunk = 0, outCap = 0; int64_t maxBlocks = 0;
     InflateSlot slot[3];
@@ -2378,6 +2382,7 @@ struct hlala_inflater {
     size_t roundBytes = 0;          // bytes of the decoder's last round in scan[SCAN_DATA] (hlala_host::bam_scan_round: their tail is the next round's carry)
     GroupState grp;
     NameOrderState nam;
+    FillKeep keep;
     std::string err;
 };
 static thread_local std::string g_inflater_create_error;
@@ -2400,6 +2405,8 @@ extern "C" void hlala_inflater_destroy(hlala_inflater* f)
     for(hipEvent_t e : f->grp.ev) if(e) (void)hipEventDestroy(e);
     for(ScanBuf& b : f->nam.buf) if(b.p) (void)hipFree(b.p);
     for(hipEvent_t e : f->nam.ev) if(e) (void)hipEventDestroy(e);
+    if(f->keep.recs.p) (void)hipFree(f->keep.recs.p);
+    if(f->keep.bytes.p) (void)hipFree(f->keep.bytes.p);
     delete f;
 }
 extern "C" int hlala_inflater_create(int32_t device, size_t chunk_bytes, hlala_inflater** out)
@@ -2568,11 +2575,13 @@ static int bam_inflate_hook(void* inflater, const uint8_t* comp, size_t comp_byt
 static int bam_scan_hook(void* inflater, hlala_host::bam_scan_round* R, std::string* err);      // (behind hlala_bam_scan, below)
 static int bam_group_hook(void* inflater, int64_t n, int32_t long_read_mode, uint32_t* perm, uint8_t* flag, hlala_bam_group_stats* stats, bool* available, std::string* err);      // (behind hlala_bam_group, below)
 static int bam_sort_hook(void* inflater, int64_t m, uint32_t* order, hlala_bam_name_order_stats* stats, bool* available, std::string* err);      // (behind hlala_bam_name_order, below)
+static int bam_fill_hook(void* inflater, const hlala_bam_fill_in* in, int64_t* read_off, int64_t* chain_off, int64_t* cigar_count, int64_t* name_off, hlala_host::bam_fill_handle* handle,
+                         hlala_bam_fill_stats* stats, bool* available, std::string* err);      // (behind hlala_bam_fill_create, below)
 extern "C" int hlala_bam_extract_seeds_gpu(hlala_inflater* f, const char* path, int32_t n_intervals, const hlala_bam_interval* iv, int32_t long_read_mode, int32_t n_threads, int32_t flags,
                                            hlala_seed_batch** out)
 {
     static std::once_flag hookOnce;                  // (samples may decode on several threads)
-    std::call_once(hookOnce, []() { hlala_host::g_bam_inflate_hook = bam_inflate_hook; hlala_host::g_bam_inflate_crc_hook = bam_inflate_crc_hook; hlala_host::g_bam_scan_hook = bam_scan_hook; hlala_host::g_bam_group_hook = bam_group_hook; hlala_host::g_bam_sort_hook = bam_sort_hook; });
+    std::call_once(hookOnce, []() { hlala_host::g_bam_inflate_hook = bam_inflate_hook; hlala_host::g_bam_inflate_crc_hook = bam_inflate_crc_hook; hlala_host::g_bam_scan_hook = bam_scan_hook; hlala_host::g_bam_group_hook = bam_group_hook; hlala_host::g_bam_sort_hook = bam_sort_hook; hlala_host::g_bam_fill_hook = bam_fill_hook; });
     return hlala_host::bam_extract_seeds_impl(path, n_intervals, iv, long_read_mode, n_threads, flags, true, f, out);
 }
 
@@ -2701,6 +2710,9 @@ extern "C" int hlala_bam_scan(hlala_inflater* f, const uint8_t* data, size_t n, 
     return scan_run(f, n ? data : &none, n, first, last, in, sink, stats);
 }
 static void group_reset(hlala_inflater* f);
+static void keep_reset(hlala_inflater* f);
+static void keep_drop(hlala_inflater* f);
+static int keep_append(hlala_inflater* f, const hlala_bam_rec* dRecs, int64_t n, const uint8_t* dBytes, size_t nBytes);
 static int group_append(hlala_inflater* f, const hlala_bam_rec* dRecs, int64_t n, const uint8_t* dBytes, size_t nBytes);
 // One round of the decoder with HLALA_SEEDS_GPU_PARSE (hlala_host::bam_scan_round): carry to the front, inflate into the device round buffer, the record pass on it.
 static int bam_scan_hook(void* inflater, hlala_host::bam_scan_round* R, std::string* err)
@@ -2770,6 +2782,16 @@ static int bam_scan_hook(void* inflater, hlala_host::bam_scan_round* R, std::str
             if(rc != HLALA_OK) return out(rc);
             R->group_appended = f->grp.ok;
         } else f->grp.ok = false;
+    }
+    // HLALA_SEEDS_GPU_FILL: ... and stay on the device whole, for the fill hook
+    R->kept = false;
+    if(R->keep && R->group) {
+        if(R->group_first) keep_reset(f);
+        if(R->group_appended && f->keep.ok) {
+            rc = R->stats.n_recs ? keep_append(f, (const hlala_bam_rec*)f->scan[SCAN_RECS].p, R->stats.n_recs, (const uint8_t*)f->scan[SCAN_COMPACT].p, (size_t)R->stats.compact_bytes) : HLALA_OK;
+            if(rc != HLALA_OK) return out(rc);
+            R->kept = f->keep.ok;
+        } else if(f->keep.ok || f->keep.recs.p) keep_drop(f);
     }
     R->s_scan = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
     return HLALA_OK;
@@ -3126,13 +3148,343 @@ static int bam_sort_hook(void* inflater, int64_t m, uint32_t* order, hlala_bam_n
     return HLALA_OK;
 }
 
+// ---- the layout and the fill on the device (include/hlala_gpu.h; kernel_bamfill.hip).  A handle of its own: the sample's descriptors, bytes, permutation and unit
+// arrays, what the layout passes leave (offsets, chain sources, primaries), a stream, events, one device block and one page-locked block for a window's slices.
+enum { FIL_RECS, FIL_BYTES, FIL_PERM, FIL_UFIRST, FIL_UCOUNT, FIL_SIZES, FIL_OFFS, FIL_CHAINSRC, FIL_CHAINCIG, FIL_PRIMARY, FIL_WIN, FIL_NBUF };
+constexpr int FIL_NEV = 8;
+struct hlala_bam_fill {
+    int device = 0; hipStream_t st = nullptr; hipEvent_t ev[FIL_NEV]{};
+    ScanBuf buf[FIL_NBUF];
+    FilSample S{}; int packed = 0; u64 nReads = 0, nChains = 0;
+    uint8_t* hStage = nullptr; size_t stageCap = 0; int64_t* hBounds = nullptr;
+    std::string err;
+    int64_t* off(int which) const { return (int64_t*)buf[FIL_OFFS].p + (size_t)which * (nReads + 1); }      // 0 read_off, 1 chain_off, 2 cigar_count, 3 name_off
+};
+static void fill_free(hlala_bam_fill* H)
+{
+    if(!H) return;
+    DevGuard g(H->device);
+    if(H->st) (void)hipStreamSynchronize(H->st);
+    for(ScanBuf& b : H->buf) if(b.p) (void)hipFree(b.p);
+    for(hipEvent_t e : H->ev) if(e) (void)hipEventDestroy(e);
+    if(H->hStage) (void)hipHostFree(H->hStage);
+    if(H->hBounds) (void)hipHostFree(H->hBounds);
+    if(H->st) (void)hipStreamDestroy(H->st);
+    delete H;
+}
+static hipError_t fill_alloc(hlala_bam_fill* H, int which, size_t bytes)
+{
+    ScanBuf& b = H->buf[which];
+    if(bytes <= b.cap && b.p) return hipSuccess;
+    if(b.p) { (void)hipFree(b.p); b.p = nullptr; b.cap = 0; }
+    const hipError_t r = hipMalloc(&b.p, bytes ? bytes : 1);
+    if(r != hipSuccess) { b.p = nullptr; return r; }
+    b.cap = bytes ? bytes : 1;
+    return hipSuccess;
+}
+// The layout passes.  H holds FIL_RECS / FIL_BYTES (/ FIL_PERM) and S.n, S.nBytes; the unit arrays and the host units' sizes are host memory and are uploaded here.
+// *noMemory: a device allocation failed, nothing of the sample is laid out (the decoder's hook hands the sample back; the entry point fails).
+static int fill_layout(hlala_bam_fill* H, const hlala_bam_fill_in* in, int64_t* read_off, int64_t* chain_off, int64_t* cigar_count, int64_t* name_off, hlala_bam_fill_stats* stats, bool* noMemory)
+{
+    using namespace hlala_bamfill;
+    *noMemory = false;
+    hipStream_t st = H->st;
+    hipError_t e = hipSuccess;
+    auto failed = [&](const char* what) { H->err = std::string("BAM fill: ") + what + ": " + hipGetErrorString(e); (void)hipStreamSynchronize(st); (void)hipGetLastError(); return HLALA_E_DEVICE; };
+    const u32 nm = (u32)fil_nm(in->long_read_mode);
+    const size_t nU = (size_t)in->n_units, nR = nU * nm, nHost = (size_t)in->n_host_units, perHost = 3 * nm + 1;
+    H->nReads = nR; H->packed = in->packed ? 1 : 0;
+    std::vector<u32> hostUnit; hostUnit.reserve(nHost);
+    for(size_t u = 0; u < nU; u++) if(in->unit_first[u] == FIL_HOST) hostUnit.push_back((u32)u);
+    if(hostUnit.size() != nHost) { H->err = "BAM fill: the host units marked are not n_host_units"; return HLALA_E_ARG; }
+    size_t cubBytes = 0;
+    if((e = hipcub::DeviceScan::ExclusiveSum(nullptr, cubBytes, (int64_t*)nullptr, (int64_t*)nullptr, nR + 1, st)) != hipSuccess) return failed("hipcub::DeviceScan::ExclusiveSum");
+    // FIL_SIZES: the four size arrays [nR + 1] each (name sizes use nU + 1 of theirs); behind them the host units' numbers and sizes, then the scan's scratch and the bad bits
+    const size_t sizesBytes = 4 * (nR + 1) * 8, hostBytes = nHost * 4 + 8 + nHost * perHost * 8;
+    if((e = fill_alloc(H, FIL_UFIRST, nU * 4)) != hipSuccess || (e = fill_alloc(H, FIL_UCOUNT, nU * 4)) != hipSuccess || (e = fill_alloc(H, FIL_SIZES, sizesBytes + hostBytes + cubBytes + 64)) != hipSuccess ||
+       (e = fill_alloc(H, FIL_OFFS, sizesBytes)) != hipSuccess || (e = fill_alloc(H, FIL_PRIMARY, nR * 4)) != hipSuccess) { (void)hipGetLastError(); *noMemory = true; return HLALA_OK; }
+    int64_t* dSize = (int64_t*)H->buf[FIL_SIZES].p;
+    int64_t* dHostSizes = dSize + 4 * (nR + 1); u32* dHostUnit = (u32*)(dHostSizes + nHost * perHost); u32* dBad = dHostUnit + nHost + (nHost & 1);
+    void* dCub = (void*)(((uintptr_t)(dBad + 2) + 15) & ~(uintptr_t)15);
+    H->S.unitFirst = (const u32*)H->buf[FIL_UFIRST].p; H->S.unitCount = (const u32*)H->buf[FIL_UCOUNT].p; H->S.nUnits = (u32)nU; H->S.nm = nm;
+    auto ms = [&](int a, int b) { float t = 0; return hipEventElapsedTime(&t, H->ev[a], H->ev[b]) == hipSuccess ? (double)t : 0.0; };
+    e = hipEventRecord(H->ev[0], st);
+    if(e == hipSuccess) e = hipMemcpyAsync(H->buf[FIL_UFIRST].p, in->unit_first, nU * 4, hipMemcpyHostToDevice, st);
+    if(e == hipSuccess) e = hipMemcpyAsync(H->buf[FIL_UCOUNT].p, in->unit_count, nU * 4, hipMemcpyHostToDevice, st);
+    if(e == hipSuccess && nHost) e = hipMemcpyAsync(dHostSizes, in->host_sizes, nHost * perHost * 8, hipMemcpyHostToDevice, st);
+    if(e == hipSuccess && nHost) e = hipMemcpyAsync(dHostUnit, hostUnit.data(), nHost * 4, hipMemcpyHostToDevice, st);
+    if(e == hipSuccess) e = hipMemsetAsync(dSize, 0, sizesBytes, st);
+    if(e == hipSuccess) e = hipMemsetAsync(dBad, 0, 8, st);
+    if(e == hipSuccess) e = hipMemsetAsync(H->buf[FIL_PRIMARY].p, 0, nR * 4, st);
+    if(e == hipSuccess) e = hipEventRecord(H->ev[1], st);
+    const u32 rankBlocks = (u32)((nR * 16 + 255) / 256);
+    int64_t *sL = dSize, *sC = dSize + (nR + 1), *sG = dSize + 2 * (nR + 1), *sN = dSize + 3 * (nR + 1);
+    if(e == hipSuccess) { hipLaunchKernelGGL(k_fil_rank, dim3(rankBlocks), dim3(256), 0, st, H->S, (u64)nR, sL, sC, sG, sN, dBad); e = hipGetLastError(); }
+    if(e == hipSuccess) e = hipEventRecord(H->ev[2], st);
+    if(e == hipSuccess && nHost) { hipLaunchKernelGGL(k_fil_host, dim3((u32)((nHost + 63) / 64)), dim3(64), 0, st, (u32)nHost, (u32)nU, nm, (const u32*)dHostUnit, (const int64_t*)dHostSizes, sL, sC, sG, sN); e = hipGetLastError(); }
+    if(e == hipSuccess) e = hipEventRecord(H->ev[3], st);
+    for(int w = 0; w < 4 && e == hipSuccess; w++) e = hipcub::DeviceScan::ExclusiveSum(dCub, cubBytes, dSize + (size_t)w * (nR + 1), H->off(w), w == 3 ? nU + 1 : nR + 1, st);
+    if(e == hipSuccess) e = hipEventRecord(H->ev[4], st);
+    u32 hBad[2] = {0, 0}; int64_t totals[4] = {0, 0, 0, 0};
+    if(e == hipSuccess) e = hipMemcpyAsync(hBad, dBad, 8, hipMemcpyDeviceToHost, st);
+    for(int w = 0; w < 4 && e == hipSuccess; w++) e = hipMemcpyAsync(&totals[w], H->off(w) + (w == 3 ? nU : nR), 8, hipMemcpyDeviceToHost, st);
+    if(e == hipSuccess) e = hipStreamSynchronize(st);
+    if(e != hipSuccess) return failed("upload / k_fil_rank / k_fil_host / the scans");
+    if(hBad[0]) {
+        H->err = std::string("BAM fill: ") + ((hBad[0] & FIL_BAD_MATE) ? "a filled unit with more than 16 alignments on one mate" : (hBad[0] & FIL_BAD_PRIMARY) ? "a filled unit without a primary on a required mate"
+                                                                       : "a unit whose records lie beyond the descriptors");
+        return HLALA_E_ARG;
+    }
+    if(totals[1] < 0 || totals[1] > 0x7FFFFFFFll) { H->err = "BAM fill: more than 2^31 - 1 chains"; return HLALA_E_ARG; }
+    const size_t nC = (size_t)totals[1];
+    H->nChains = nC;
+    if((e = fill_alloc(H, FIL_CHAINSRC, nC * 4)) != hipSuccess || (e = fill_alloc(H, FIL_CHAINCIG, nC * 8)) != hipSuccess) { (void)hipGetLastError(); *noMemory = true; return HLALA_OK; }
+    e = hipMemsetAsync(H->buf[FIL_CHAINSRC].p, 0xFF, nC * 4, st);
+    if(e == hipSuccess) e = hipMemsetAsync(H->buf[FIL_CHAINCIG].p, 0, nC * 8, st);
+    if(e == hipSuccess) e = hipEventRecord(H->ev[5], st);
+    if(e == hipSuccess) { hipLaunchKernelGGL(k_fil_src, dim3(rankBlocks), dim3(256), 0, st, H->S, (u64)nR, (const int64_t*)H->off(1), (const int64_t*)H->off(2), (u64)nC, (u32*)H->buf[FIL_CHAINSRC].p,
+                                             (int64_t*)H->buf[FIL_CHAINCIG].p, (int32_t*)H->buf[FIL_PRIMARY].p); e = hipGetLastError(); }
+    if(e == hipSuccess) e = hipEventRecord(H->ev[6], st);
+    if(e == hipSuccess) e = hipMemcpyAsync(read_off, H->off(0), (nR + 1) * 8, hipMemcpyDeviceToHost, st);
+    if(e == hipSuccess) e = hipMemcpyAsync(chain_off, H->off(1), (nR + 1) * 8, hipMemcpyDeviceToHost, st);
+    if(e == hipSuccess) e = hipMemcpyAsync(cigar_count, H->off(2), (nR + 1) * 8, hipMemcpyDeviceToHost, st);
+    if(e == hipSuccess) e = hipMemcpyAsync(name_off, H->off(3), (nU + 1) * 8, hipMemcpyDeviceToHost, st);
+    if(e == hipSuccess) e = hipEventRecord(H->ev[7], st);
+    if(e == hipSuccess) e = hipStreamSynchronize(st);
+    if(e != hipSuccess) return failed("k_fil_src / download");
+    stats->n_units = (int64_t)nU; stats->n_host_units = (int64_t)nHost; stats->n_reads = (int64_t)nR; stats->n_chains = totals[1]; stats->n_cigar = totals[2]; stats->n_bases = totals[0]; stats->n_name_bytes = totals[3];
+    stats->ms_h2d += ms(0, 1); stats->ms_rank = ms(1, 2); stats->ms_host = ms(2, 3); stats->ms_scan = ms(3, 4); stats->ms_src = ms(5, 6); stats->ms_d2h = ms(6, 7);
+    stats->bytes_h2d += (int64_t)(nU * 8 + nHost * (perHost * 8 + 4)); stats->bytes_d2h += (int64_t)((3 * (nR + 1) + nU + 1) * 8);
+    return HLALA_OK;
+}
+static hlala_bam_fill* fill_new(int device, std::string* why)
+{
+    hlala_bam_fill* H = new hlala_bam_fill(); H->device = device;
+    DevGuard g(device);
+    hipError_t e = hipStreamCreateWithFlags(&H->st, hipStreamNonBlocking);
+    for(hipEvent_t& ev : H->ev) if(e == hipSuccess) e = hipEventCreate(&ev);
+    if(e == hipSuccess) e = hipHostMalloc((void**)&H->hBounds, 8 * 8, hipHostMallocDefault);
+    if(e != hipSuccess) { if(why) *why = std::string("BAM fill: stream / events / staging: ") + hipGetErrorString(e); (void)hipGetLastError(); fill_free(H); return nullptr; }
+    return H;
+}
+// The slices of a window from the staging block to where they belong.  The destination's pages are often first touched here (the arrays of a seed batch are not
+// cleared), which one thread does at a fraction of the rate the copy engine delivers: beyond a few MiB the pieces are cut across the CPUs this process may keep busy.
+struct FillPiece { void* to; const void* from; size_t bytes; };
+static void fill_scatter(const std::vector<FillPiece>& slices)
+{
+    constexpr size_t CUT = (size_t)2 << 20;
+    std::vector<FillPiece> pieces; size_t total = 0;
+    for(const FillPiece& s : slices) { total += s.bytes; for(size_t o = 0; o < s.bytes; o += CUT) pieces.push_back(FillPiece{(uint8_t*)s.to + o, (const uint8_t*)s.from + o, std::min(CUT, s.bytes - o)}); }
+    int T = std::min(16, hlala_host::host_cpu_budget()); if((size_t)T > pieces.size()) T = (int)pieces.size();
+    if(total < 4 * CUT || T <= 1) { for(const FillPiece& q : pieces) memcpy(q.to, q.from, q.bytes); return; }
+    std::atomic<size_t> next(0);
+    auto work = [&]() { for(;;) { const size_t i = next.fetch_add(1); if(i >= pieces.size()) break; memcpy(pieces[i].to, pieces[i].from, pieces[i].bytes); } };
+    std::vector<std::thread> th;
+    try { for(int t = 1; t < T; t++) th.emplace_back(work); } catch(...) {}       // (a thread that cannot be started: the others and this one do its share)
+    work();
+    for(std::thread& x : th) x.join();
+}
+static int fill_window(hlala_bam_fill* H, int64_t first_unit, int64_t n_units, const hlala_bam_fill_out* out, hlala_bam_fill_stats* stats)
+{
+    using namespace hlala_bamfill;
+    H->err.clear();
+    if(!stats) { H->err = "hlala_bam_fill_window: null argument"; return HLALA_E_ARG; }
+    memset(stats, 0, sizeof(*stats));
+    if(first_unit < 0 || n_units < 0 || first_unit + n_units > (int64_t)H->S.nUnits) { H->err = "hlala_bam_fill_window: units outside the sample"; return HLALA_E_ARG; }
+    if(n_units == 0) return HLALA_OK;
+    const bool need = out && out->read_primary && out->read_quals && (H->packed ? out->read_bases_packed : out->read_bases) && out->chain_contig && out->chain_pos && out->chain_offset && out->chain_as &&
+                      out->chain_reverse && out->cigar_off_end && out->cigar && out->name_chars;
+    if(!need) { H->err = "hlala_bam_fill_window: null argument"; return HLALA_E_ARG; }
+    const auto tWall = std::chrono::steady_clock::now();
+    DevGuard g(H->device);
+    hipStream_t st = H->st;
+    hipError_t e = hipSuccess;
+    auto failed = [&](const char* what) { H->err = std::string("hlala_bam_fill_window: ") + what + ": " + hipGetErrorString(e); (void)hipStreamSynchronize(st); (void)hipGetLastError(); return HLALA_E_DEVICE; };
+    const u64 nm = H->S.nm, u0 = (u64)first_unit, u1 = u0 + (u64)n_units, r0 = u0 * nm, r1 = u1 * nm;
+    // the window's bounds in the four offset arrays
+    const u64 at[8] = {r0, r1, r0, r1, r0, r1, u0, u1};
+    for(int k = 0; k < 8 && e == hipSuccess; k++) e = hipMemcpyAsync(H->hBounds + k, H->off(k / 2) + at[k], 8, hipMemcpyDeviceToHost, st);
+    if(e == hipSuccess) e = hipStreamSynchronize(st);
+    if(e != hipSuccess) return failed("the window's bounds");
+    const int64_t* hb = H->hBounds;
+    for(int k = 0; k < 4; k++) if(hb[2 * k] < 0 || hb[2 * k + 1] < hb[2 * k]) { H->err = "hlala_bam_fill_window: offsets that do not ascend"; return HLALA_E_DEVICE; }      // (cannot happen)
+    FilWindow W{};
+    W.r0 = r0; W.nr = r1 - r0; W.b0 = (u64)hb[0]; W.nb = (u64)(hb[1] - hb[0]); W.c0 = (u64)hb[2]; W.nc = (u64)(hb[3] - hb[2]); W.g0 = (u64)hb[4]; W.ng = (u64)(hb[5] - hb[4]);
+    W.u0 = u0; W.nu = u1 - u0; W.n0 = (u64)hb[6]; W.nn = (u64)(hb[7] - hb[6]);
+    W.p0 = (u64)fil_packed_at(hb[0], (int64_t)r0); W.np = H->packed ? (u64)fil_packed_at(hb[1], (int64_t)r1) - W.p0 : 0;
+    if(W.c0 + W.nc > H->nChains) { H->err = "hlala_bam_fill_window: chains beyond the sample"; return HLALA_E_DEVICE; }      // (cannot happen)
+    // one block for the window's slices, every slice on a 16-byte boundary
+    size_t total = 0;
+    auto place = [&](size_t bytes) { const size_t o = total; total += (bytes + 15) & ~(size_t)15; return o; };
+    const size_t oContig = place(W.nc * 4), oPos = place(W.nc * 4), oOffset = place(W.nc * 4), oAs = place(W.nc * 4), oRev = place(W.nc), oCigEnd = place(W.nc * 8), oCigar = place(W.ng * 4), oNames = place(W.nn),
+                 oBases = place(H->packed ? W.np : W.nb), oQuals = place(W.nb), oPrim = place(W.nr * 4);
+    if((e = fill_alloc(H, FIL_WIN, total)) != hipSuccess) return failed("hipMalloc");
+    if(total > H->stageCap) {
+        if(H->hStage) { (void)hipHostFree(H->hStage); H->hStage = nullptr; H->stageCap = 0; }
+        if((e = hipHostMalloc((void**)&H->hStage, total + total / 4, hipHostMallocDefault)) != hipSuccess) { H->hStage = nullptr; return failed("hipHostMalloc"); }
+        H->stageCap = total + total / 4;
+    }
+    uint8_t* d = (uint8_t*)H->buf[FIL_WIN].p;
+    W.chainContig = (int32_t*)(d + oContig); W.chainPos = (int32_t*)(d + oPos); W.chainOffset = (int32_t*)(d + oOffset); W.chainAs = (int32_t*)(d + oAs); W.chainReverse = d + oRev;
+    W.cigarOffEnd = (int64_t*)(d + oCigEnd); W.cigar = (u32*)(d + oCigar); W.names = d + oNames; W.bases = H->packed ? nullptr : d + oBases; W.packed = H->packed ? d + oBases : nullptr; W.quals = d + oQuals;
+    const u32* dSrc = (const u32*)H->buf[FIL_CHAINSRC].p; const int64_t* dCig = (const int64_t*)H->buf[FIL_CHAINCIG].p; const int32_t* dPrim = (const int32_t*)H->buf[FIL_PRIMARY].p;
+    auto ms = [&](int a, int b) { float t = 0; return hipEventElapsedTime(&t, H->ev[a], H->ev[b]) == hipSuccess ? (double)t : 0.0; };
+    e = hipMemsetAsync(d, 0, total, st);
+    if(e == hipSuccess) e = hipMemcpyAsync(d + oPrim, dPrim + r0, W.nr * 4, hipMemcpyDeviceToDevice, st);
+    if(e == hipSuccess) e = hipEventRecord(H->ev[0], st);
+    if(e == hipSuccess && W.nc) { hipLaunchKernelGGL(k_fil_chain, dim3((u32)((W.nc + 255) / 256)), dim3(256), 0, st, H->S, W, dSrc, dCig); e = hipGetLastError(); }
+    if(e == hipSuccess) e = hipEventRecord(H->ev[1], st);
+    if(e == hipSuccess && W.nc) { hipLaunchKernelGGL(k_fil_cigar, dim3((u32)((W.nc * 16 + 255) / 256)), dim3(256), 0, st, H->S, W, dSrc, dCig); e = hipGetLastError(); }
+    if(e == hipSuccess) e = hipEventRecord(H->ev[2], st);
+    if(e == hipSuccess) { hipLaunchKernelGGL(k_fil_names, dim3((u32)((W.nu * 16 + 255) / 256)), dim3(256), 0, st, H->S, W, (const int64_t*)H->off(3)); e = hipGetLastError(); }
+    if(e == hipSuccess) e = hipEventRecord(H->ev[3], st);
+    if(e == hipSuccess) { hipLaunchKernelGGL(k_fil_bases, dim3((u32)((W.nr + 3) / 4)), dim3(256), 0, st, H->S, W, (const int64_t*)H->off(0), dPrim, dSrc, (u64)H->nChains); e = hipGetLastError(); }
+    if(e == hipSuccess) e = hipEventRecord(H->ev[4], st);
+    if(e == hipSuccess) e = hipMemcpyAsync(H->hStage, d, total, hipMemcpyDeviceToHost, st);
+    if(e == hipSuccess) e = hipEventRecord(H->ev[5], st);
+    if(e == hipSuccess) e = hipStreamSynchronize(st);
+    if(e != hipSuccess) return failed("k_fil_chain / k_fil_cigar / k_fil_names / k_fil_bases / download");
+    const uint8_t* h = H->hStage;
+    fill_scatter({{out->chain_contig, h + oContig, W.nc * 4}, {out->chain_pos, h + oPos, W.nc * 4}, {out->chain_offset, h + oOffset, W.nc * 4}, {out->chain_as, h + oAs, W.nc * 4}, {out->chain_reverse, h + oRev, W.nc},
+                  {out->cigar_off_end, h + oCigEnd, W.nc * 8}, {out->cigar, h + oCigar, W.ng * 4}, {out->name_chars, h + oNames, W.nn},
+                  {H->packed ? out->read_bases_packed : out->read_bases, h + oBases, H->packed ? W.np : W.nb}, {out->read_quals, h + oQuals, W.nb}, {out->read_primary, h + oPrim, W.nr * 4}});
+    stats->n_units = n_units; stats->n_reads = (int64_t)W.nr; stats->n_chains = (int64_t)W.nc; stats->n_cigar = (int64_t)W.ng; stats->n_bases = (int64_t)W.nb; stats->n_name_bytes = (int64_t)W.nn;
+    stats->ms_chain = ms(0, 1); stats->ms_cigar = ms(1, 2); stats->ms_names = ms(2, 3); stats->ms_bases = ms(3, 4); stats->ms_d2h = ms(4, 5); stats->bytes_d2h = (int64_t)total + 64;
+    stats->ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tWall).count();
+    return HLALA_OK;
+}
+extern "C" int hlala_bam_fill_create(hlala_inflater* f, const hlala_bam_fill_in* in, int64_t* read_off, int64_t* chain_off, int64_t* cigar_count, int64_t* name_off, hlala_bam_fill** out,
+                                     hlala_bam_fill_stats* stats)
+{
+    if(!f) { int ndev = 0; if(hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return HLALA_E_DEVICE; } return HLALA_E_ARG; }
+    f->err.clear();
+    if(out) *out = nullptr;
+    const char* bad = out ? hlala_bamfill::fil_check_args(in, read_off, chain_off, cigar_count, name_off, stats) : "null argument";
+    if(bad) { f->err = std::string("hlala_bam_fill_create: ") + bad; return HLALA_E_ARG; }
+    const auto tWall = std::chrono::steady_clock::now();
+    memset(stats, 0, sizeof(*stats));
+    if(in->n_units == 0) return HLALA_OK;
+    hlala_bam_fill* H = fill_new(f->device, &f->err);
+    if(!H) return HLALA_E_DEVICE;
+    DevGuard g(f->device);
+    hipError_t e = hipSuccess;
+    auto failed = [&](const char* what) { f->err = std::string("hlala_bam_fill_create: ") + what + ": " + hipGetErrorString(e); (void)hipGetLastError(); fill_free(H); return HLALA_E_DEVICE; };
+    const size_t recBytes = (size_t)in->n * sizeof(hlala_bam_rec);
+    if((e = fill_alloc(H, FIL_RECS, recBytes)) != hipSuccess || (e = fill_alloc(H, FIL_BYTES, in->n_bytes)) != hipSuccess) return failed("hipMalloc");
+    e = hipEventRecord(H->ev[0], H->st);
+    if(e == hipSuccess && recBytes) e = hipMemcpyAsync(H->buf[FIL_RECS].p, in->recs, recBytes, hipMemcpyHostToDevice, H->st);
+    if(e == hipSuccess && in->n_bytes) e = hipMemcpyAsync(H->buf[FIL_BYTES].p, in->bytes, in->n_bytes, hipMemcpyHostToDevice, H->st);
+    if(e == hipSuccess) e = hipEventRecord(H->ev[1], H->st);
+    if(e == hipSuccess) e = hipStreamSynchronize(H->st);
+    if(e != hipSuccess) return failed("upload");
+    { float t = 0; if(hipEventElapsedTime(&t, H->ev[0], H->ev[1]) == hipSuccess) stats->ms_h2d = (double)t; }
+    stats->bytes_h2d = (int64_t)(recBytes + in->n_bytes);
+    H->S.recs = (const hlala_bam_rec*)H->buf[FIL_RECS].p; H->S.n = (u32)in->n; H->S.bytes = (const uint8_t*)H->buf[FIL_BYTES].p; H->S.nBytes = (u64)in->n_bytes; H->S.perm = nullptr;
+    bool noMemory = false;
+    const int rc = fill_layout(H, in, read_off, chain_off, cigar_count, name_off, stats, &noMemory);
+    if(rc != HLALA_OK || noMemory) { f->err = noMemory ? std::string("hlala_bam_fill_create: no device memory for the passes") : H->err; fill_free(H); return noMemory ? HLALA_E_DEVICE : rc; }
+    stats->ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tWall).count();
+    *out = H;
+    return HLALA_OK;
+}
+extern "C" int hlala_bam_fill_window(hlala_bam_fill* h, int64_t first_unit, int64_t n_units, const hlala_bam_fill_out* out, hlala_bam_fill_stats* stats)
+{
+    if(!h) return HLALA_E_ARG;
+    return fill_window(h, first_unit, n_units, out, stats);
+}
+extern "C" const char* hlala_bam_fill_last_error(const hlala_bam_fill* h) { return h ? h->err.c_str() : ""; }
+extern "C" void hlala_bam_fill_destroy(hlala_bam_fill* h) { fill_free(h); }
+
+// The decoder with HLALA_SEEDS_GPU_FILL.  The scan hook keeps a round's descriptors (rec_off moved by where its compact bytes go) and compact bytes in sample-long
+// device buffers of the inflater; the fill hook moves those buffers into a fill state, copies the grouping permutation beside them and runs the layout passes.  From
+// then on the state stands alone.  An allocation that fails is no error: keep.ok = false, or *available = false, and the host fills the sample itself.
+static void keep_reset(hlala_inflater* f) { f->keep.n = 0; f->keep.nBytes = 0; f->keep.ok = true; }
+static void keep_drop(hlala_inflater* f)
+{
+    for(ScanBuf* b : {&f->keep.recs, &f->keep.bytes}) { if(b->p) (void)hipFree(b->p); b->p = nullptr; b->cap = 0; }
+    f->keep.n = 0; f->keep.nBytes = 0; f->keep.ok = false;
+}
+static hipError_t keep_grow(ScanBuf& b, size_t bytes, size_t keep, hipStream_t st)
+{
+    if(bytes <= b.cap) return hipSuccess;
+    const size_t want = 2 * bytes + 256;
+    void* p = nullptr;
+    hipError_t r = hipMalloc(&p, want);
+    if(r != hipSuccess) return r;
+    if(keep && b.p) { r = hipMemcpyAsync(p, b.p, keep, hipMemcpyDeviceToDevice, st); if(r == hipSuccess) r = hipStreamSynchronize(st); if(r != hipSuccess) { (void)hipFree(p); return r; } }
+    if(b.p) (void)hipFree(b.p);
+    b.p = p; b.cap = want;
+    return hipSuccess;
+}
+static int keep_append(hlala_inflater* f, const hlala_bam_rec* dRecs, int64_t n, const uint8_t* dBytes, size_t nBytes)
+{
+    FillKeep& K = f->keep;
+    if(K.n + n >= ((int64_t)1 << 31)) { keep_drop(f); return HLALA_OK; }
+    DevGuard g(f->device);
+    hipStream_t st = f->slot[0].stream;
+    hipError_t e = hipSuccess;
+    const size_t have = (size_t)K.n, total = have + (size_t)n;
+    if((e = keep_grow(K.recs, total * sizeof(hlala_bam_rec), have * sizeof(hlala_bam_rec), st)) != hipSuccess || (e = keep_grow(K.bytes, (size_t)K.nBytes + nBytes + 1, (size_t)K.nBytes, st)) != hipSuccess) {
+        (void)hipGetLastError(); keep_drop(f); return HLALA_OK;
+    }
+    hipLaunchKernelGGL(k_fil_append, dim3((u32)((n + 255) / 256)), dim3(256), 0, st, (u32)n, dRecs, (u64)K.nBytes, (hlala_bam_rec*)K.recs.p + have);
+    e = hipGetLastError();
+    if(e == hipSuccess && nBytes) e = hipMemcpyAsync((uint8_t*)K.bytes.p + K.nBytes, dBytes, nBytes, hipMemcpyDeviceToDevice, st);
+    if(e == hipSuccess) e = hipStreamSynchronize(st);
+    if(e != hipSuccess) { f->err = std::string("BAM fill: k_fil_append: ") + hipGetErrorString(e); (void)hipGetLastError(); return HLALA_E_DEVICE; }
+    K.n = (int64_t)total; K.nBytes += nBytes;
+    return HLALA_OK;
+}
+static int fill_state_window(void* state, int64_t first_unit, int64_t n_units, const hlala_bam_fill_out* out, hlala_bam_fill_stats* stats, std::string* err)
+{
+    hlala_bam_fill* H = (hlala_bam_fill*)state;
+    const int rc = fill_window(H, first_unit, n_units, out, stats);
+    if(rc != HLALA_OK && err) *err = H->err;
+    return rc;
+}
+static void fill_state_destroy(void* state) { fill_free((hlala_bam_fill*)state); }
+static int bam_fill_hook(void* inflater, const hlala_bam_fill_in* in, int64_t* read_off, int64_t* chain_off, int64_t* cigar_count, int64_t* name_off, hlala_host::bam_fill_handle* handle,
+                         hlala_bam_fill_stats* stats, bool* available, std::string* err)
+{
+    hlala_inflater* f = (hlala_inflater*)inflater;
+    if(!f || !in || !handle || !stats || !available) return HLALA_E_ARG;
+    f->err.clear();
+    memset(stats, 0, sizeof(*stats));
+    GroupState& G = f->grp; FillKeep& K = f->keep;
+    *available = K.ok && G.ok && G.finished && K.n == G.n && in->n == K.n && in->n_units > 0 && in->n_units < ((int64_t)1 << 30);
+    if(!*available) return HLALA_OK;
+    const auto tWall = std::chrono::steady_clock::now();
+    auto fail = [&](int rc) { if(err) *err = f->err; return rc; };
+    hlala_bam_fill* H = fill_new(f->device, &f->err);
+    if(!H) { (void)hipGetLastError(); *available = false; return HLALA_OK; }
+    DevGuard g(f->device);
+    // the kept buffers change hands; the permutation is copied (the grouping state keeps its own)
+    H->buf[FIL_RECS] = K.recs; H->buf[FIL_BYTES] = K.bytes; K.recs = ScanBuf(); K.bytes = ScanBuf();
+    H->S.recs = (const hlala_bam_rec*)H->buf[FIL_RECS].p; H->S.n = (u32)K.n; H->S.bytes = (const uint8_t*)H->buf[FIL_BYTES].p; H->S.nBytes = (u64)K.nBytes;
+    K.n = 0; K.nBytes = 0; K.ok = false;
+    hipError_t e = fill_alloc(H, FIL_PERM, (size_t)H->S.n * 4);
+    if(e != hipSuccess) { (void)hipGetLastError(); fill_free(H); *available = false; return HLALA_OK; }
+    e = hipStreamSynchronize(f->slot[0].stream);
+    if(e == hipSuccess) e = hipMemcpyAsync(H->buf[FIL_PERM].p, G.buf[GRP_VAL_OUT].p, (size_t)H->S.n * 4, hipMemcpyDeviceToDevice, H->st);
+    if(e == hipSuccess) e = hipStreamSynchronize(H->st);
+    if(e != hipSuccess) { f->err = std::string("BAM fill: the permutation: ") + hipGetErrorString(e); (void)hipGetLastError(); fill_free(H); return fail(HLALA_E_DEVICE); }
+    H->S.perm = (const u32*)H->buf[FIL_PERM].p;
+    bool noMemory = false;
+    const int rc = fill_layout(H, in, read_off, chain_off, cigar_count, name_off, stats, &noMemory);
+    if(rc != HLALA_OK) { f->err = H->err; fill_free(H); return fail(rc); }
+    if(noMemory) { fill_free(H); *available = false; return HLALA_OK; }
+    stats->ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tWall).count();
+    handle->state = H; handle->window = fill_state_window; handle->destroy = fill_state_destroy;
+    return HLALA_OK;
+}
+
 extern "C" int hlala_abi_sizeof(const char* name)
 {
     if(!name) return -1;
     const std::string n(name);
 #define SZ(t) if(n == #t) return (int)sizeof(t);
     SZ(hlala_graph_desc) SZ(hlala_contigs_desc) SZ(hlala_params) SZ(hlala_graph_info) SZ(hlala_batch_in) SZ(hlala_seeds_in)
-    SZ(hlala_chains_out) SZ(hlala_pairs_out) SZ(hlala_batch_stats) SZ(hlala_exon_in) SZ(hlala_call_out) SZ(hlala_locus_desc) SZ(hlala_exon_positions_out) SZ(hlala_filter_params) SZ(hlala_filter_stats) SZ(hlala_insert_size_out) SZ(hlala_locus_info) SZ(hlala_locus_report_in) SZ(hlala_locus_report_out) SZ(hlala_unit_stats_out) SZ(hlala_pairs_packed_out) SZ(hlala_bgzf_block) SZ(hlala_inflate_stats) SZ(hlala_bam_rec) SZ(hlala_bam_scan_in) SZ(hlala_bam_scan_stats) SZ(hlala_bam_group_stats) SZ(hlala_bam_name_order_stats)
+    SZ(hlala_chains_out) SZ(hlala_pairs_out) SZ(hlala_batch_stats) SZ(hlala_exon_in) SZ(hlala_call_out) SZ(hlala_locus_desc) SZ(hlala_exon_positions_out) SZ(hlala_filter_params) SZ(hlala_filter_stats) SZ(hlala_insert_size_out) SZ(hlala_locus_info) SZ(hlala_locus_report_in) SZ(hlala_locus_report_out) SZ(hlala_unit_stats_out) SZ(hlala_pairs_packed_out) SZ(hlala_bgzf_block) SZ(hlala_inflate_stats) SZ(hlala_bam_rec) SZ(hlala_bam_scan_in) SZ(hlala_bam_scan_stats) SZ(hlala_bam_group_stats) SZ(hlala_bam_name_order_stats) SZ(hlala_bam_fill_in) SZ(hlala_bam_fill_out) SZ(hlala_bam_fill_stats)
 #undef SZ
     return -1;
 }

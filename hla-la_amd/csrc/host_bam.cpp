@@ -208,7 +208,7 @@ uint64_t hash_name(const uint8_t* s, size_t n)
     return h;
 }
 
-struct Unit { const char* name; uint32_t nameLen; uint32_t part; uint32_t first, count; };      // recs [first, first + count) of the partition's sorted record list
+struct Unit { const char* name; uint32_t nameLen; uint16_t part; uint16_t host; uint32_t first, count; };      // recs [first, first + count) of the partition's sorted record list; host: split out of a collided hash run by the host (HLALA_SEEDS_GPU_FILL: the device does not fill it)
 
 // The decoder's working memory: the inflated rounds (the records the Recs point into), the kept records by name partition, the units in name order.  It outlives
 // hlala_bam_extract_seeds_mt: the arrays of the result are FILLED per window, when a window is first asked for (fill state below), and released when the last
@@ -216,7 +216,11 @@ struct Unit { const char* name; uint32_t nameLen; uint32_t part; uint32_t first,
 struct Work { std::vector<Arena> arenas; std::vector<std::vector<Rec>> precs; std::vector<Unit> units; Buf<int64_t> cigCount;
               std::vector<std::unique_ptr<uint8_t, BigFree>> inflated;
               // ---- fill state: the units are filled in chunks of UCH (chunk c = units [c * UCH, (c + 1) * UCH)), `done` per chunk, under the seed batch's fill_mu
-              int nm = 2, T = 1; int64_t UCH = 1, nUChunks = 0, remaining = 0; std::vector<uint8_t> done; };
+              int nm = 2, T = 1; int64_t UCH = 1, nUChunks = 0, remaining = 0; std::vector<uint8_t> done;
+              // ---- HLALA_SEEDS_GPU_FILL: the device's fill state (null: the host fills every unit) and the units it leaves to the host, ascending
+              hlala_host::bam_fill_handle gpuFill; std::vector<uint32_t> hostUnits;
+              void release_gpu() { if(gpuFill.state && gpuFill.destroy) gpuFill.destroy(gpuFill.state); gpuFill = hlala_host::bam_fill_handle(); }
+              ~Work() { release_gpu(); } };
 
 bool name_less(const Unit& a, const Unit& b)
 {
@@ -243,12 +247,15 @@ struct hlala_seed_batch {
     int64_t transfer_bytes[2] = {0, 0};         // bytes the GPU paths of the decoder moved to the device and back
     int64_t group_counts[3] = {0, 0, 0};        // HLALA_SEEDS_GPU_GROUP: records grouped on the GPU, collided runs the host regrouped, 1 = the whole sample was grouped by the host instead
     int64_t sort_counts[3] = {0, 0, 0};         // HLALA_SEEDS_GPU_SORT: units ordered on the GPU, units of collided runs the host merged in, 1 = the whole sample was ordered by the host instead
+    int64_t fill_counts[3] = {0, 0, 0};         // HLALA_SEEDS_GPU_FILL: units the GPU fills, host units, 1 = the whole sample was laid out and filled by the host instead
+    double fill_window_ms = 0;                  // ... wall clock of its window calls so far (HLALA_BAM_DEBUG prints it)
+    double fill_ms[5] = {0, 0, 0, 0, 0};        // ... device milliseconds of its window passes so far: chain, cigar, names, bases, download
     bool pinned = false;
     // page-locking window by window (hlala_seed_batch_pin(S, 2)): per bulk array the bytes locked so far, and the regions to unlock
     bool pin_lazy = false; std::mutex pin_mu; std::vector<size_t> pin_cursor; std::vector<std::pair<void*, size_t>> pin_regions;
     // the decoder's working memory while units remain to be filled (hlala_seed_batch_window fills what it hands out); null once every unit is filled
     Work* work = nullptr; double fill_seconds = 0; std::mutex fill_mu;       // (the mutex lives here, not in the working memory it outlives)
-    ~hlala_seed_batch() { if(work) { Work* w = work; work = nullptr; try { std::thread([w]() { delete w; }).detach(); } catch(...) { delete w; } } }
+    ~hlala_seed_batch() { if(work) { Work* w = work; work = nullptr; w->release_gpu(); try { std::thread([w]() { delete w; }).detach(); } catch(...) { delete w; } } }
 };
 
 namespace {
@@ -311,6 +318,26 @@ void fill_units(hlala_seed_batch* S, const Work& W, const size_t a, const size_t
     }
 }
 
+// HLALA_SEEDS_GPU_FILL: the units [a, z) by the device's fill state -- one slice per array, written by its window call where they belong in the sample's arrays
+constexpr size_t GPU_FILL_RANGE = 65536;
+void fill_range_gpu(hlala_seed_batch* S, Work& W, const size_t a, const size_t z)
+{
+    static uint8_t none[16];                                   // (an array of the sample without an element: the window call takes no null pointer)
+    auto at = [](auto& buf, size_t i) { return buf.size() ? buf.data() + i : (decltype(buf.data()))(void*)none; };
+    const size_t r0 = a * (size_t)W.nm, c0 = (size_t)S->chain_off[r0], b0 = (size_t)S->read_off[r0];
+    hlala_bam_fill_out out; memset(&out, 0, sizeof(out));
+    out.read_primary = at(S->read_primary, r0); out.read_quals = at(S->read_quals, b0);
+    if(S->packed) out.read_bases_packed = at(S->read_bases_packed, (b0 + r0 + 1) >> 1); else out.read_bases = at(S->read_bases, b0);
+    out.chain_contig = at(S->chain_contig, c0); out.chain_pos = at(S->chain_pos, c0); out.chain_offset = at(S->chain_offset, c0); out.chain_as = at(S->chain_as, c0); out.chain_reverse = at(S->chain_reverse, c0);
+    out.cigar_off_end = at(S->cigar_off, c0 + 1); out.cigar = at(S->cigar, (size_t)W.cigCount[r0]); out.name_chars = at(S->name_chars, (size_t)S->name_off[a]);
+    hlala_bam_fill_stats st; std::string herr;
+    const int rc = W.gpuFill.window(W.gpuFill.state, (int64_t)a, (int64_t)(z - a), &out, &st, &herr);
+    if(rc != HLALA_OK) throw Fail("BAM fill on the GPU failed: " + herr);
+    S->transfer_bytes[1] += st.bytes_d2h;
+    for(int k = 0; k < 5; k++) S->fill_ms[k] += (&st.ms_chain)[k];
+    S->fill_window_ms += st.ms_wall;
+}
+
 // The units [u0, u1) are filled before this returns (whichever thread asks first fills them, on the decoder's thread count; the others wait).  Once no unit is left
 // the working memory is released on a thread of its own (unmapping a dozen GB takes about a second that the caller need not wait for).
 void ensure_filled(const hlala_seed_batch* Sc, int64_t u0, int64_t u1)
@@ -323,7 +350,24 @@ void ensure_filled(const hlala_seed_batch* Sc, int64_t u0, int64_t u1)
     const Clock::time_point t0 = Clock::now();
     std::vector<int64_t> todo;
     for(int64_t c = u0 / W->UCH; c <= (u1 - 1) / W->UCH && c < W->nUChunks; c++) if(!W->done[(size_t)c]) todo.push_back(c);
-    if(!todo.empty()) {
+    if(!todo.empty() && W->gpuFill.state) {
+        // HLALA_SEEDS_GPU_FILL: the contiguous unit ranges of the chunks that are not done (cut at GPU_FILL_RANGE units: the staging of a range stays small); every array
+        // of a range is one contiguous slice, which the device fills and hands down; the host units inside it are filled here afterwards, by the code below
+        const size_t nU = W->units.size();
+        for(size_t i = 0; i < todo.size();) {
+            size_t j = i + 1;
+            while(j < todo.size() && todo[j] == todo[j - 1] + 1) j++;
+            const size_t ua = (size_t)(todo[i] * W->UCH), uz = std::min(nU, (size_t)((todo[j - 1] + 1) * W->UCH));
+            for(size_t a = ua; a < uz; a += GPU_FILL_RANGE) fill_range_gpu(S, *W, a, std::min(uz, a + GPU_FILL_RANGE));
+            const std::vector<uint32_t>& H = W->hostUnits;
+            const size_t ha = (size_t)(std::lower_bound(H.begin(), H.end(), (uint32_t)ua) - H.begin()), hz = (size_t)(std::lower_bound(H.begin(), H.end(), (uint32_t)uz) - H.begin());
+            std::vector<std::vector<uint32_t>> order((size_t)W->T);
+            parallel_for((int64_t)(hz - ha), W->T, [&](int64_t k, int t) { const size_t u = H[ha + (size_t)k]; fill_units(S, *W, u, u + 1, order[(size_t)t]); });
+            i = j;
+        }
+        for(int64_t c : todo) W->done[(size_t)c] = 1;
+        W->remaining -= (int64_t)todo.size();
+    } else if(!todo.empty()) {
         std::vector<std::vector<uint32_t>> order((size_t)W->T);
         const size_t nU = W->units.size();
         parallel_for((int64_t)todo.size(), W->T, [&](int64_t i, int t) {
@@ -337,6 +381,10 @@ void ensure_filled(const hlala_seed_batch* Sc, int64_t u0, int64_t u1)
     S->fill_seconds += dt; S->seconds[5] += dt;
     if(W->remaining <= 0) {
         S->work = nullptr;
+        const bool onGpu = W->gpuFill.state != nullptr; const Clock::time_point tR = Clock::now();
+        W->release_gpu();
+        if(onGpu && getenv("HLALA_BAM_DEBUG")) fprintf(stderr, "bam-debug: fill on the GPU: window calls %.3f s (device: chain %.3f, cigar %.3f, names %.3f, bases %.3f, download %.3f ms), all fills %.3f s, state released in %.3f s\n",
+                                                       S->fill_window_ms / 1e3, S->fill_ms[0], S->fill_ms[1], S->fill_ms[2], S->fill_ms[3], S->fill_ms[4], S->fill_seconds, since(tR));
         g.unlock();
         try { std::thread([W]() { delete W; }).detach(); } catch(...) { delete W; }
     }
@@ -388,6 +436,7 @@ bam_inflate_crc_hook_t g_bam_inflate_crc_hook = nullptr;       // ... (HLALA_SEE
 bam_scan_hook_t g_bam_scan_hook = nullptr;                     // ... (HLALA_SEEDS_GPU_PARSE)
 bam_group_hook_t g_bam_group_hook = nullptr;                   // ... (HLALA_SEEDS_GPU_GROUP)
 bam_sort_hook_t g_bam_sort_hook = nullptr;                     // ... (HLALA_SEEDS_GPU_SORT)
+bam_fill_hook_t g_bam_fill_hook = nullptr;                     // ... (HLALA_SEEDS_GPU_FILL)
 }  // namespace hlala_host
 
 // (host code: no device involved)
@@ -497,6 +546,8 @@ try {
     if(gpuGroup && (!gpuParse || !g_bam_group_hook)) { g_bam_error = "HLALA_SEEDS_GPU_GROUP needs HLALA_SEEDS_GPU_PARSE"; return HLALA_E_ARG; }
     const bool gpuSort = (flags & HLALA_SEEDS_GPU_SORT) != 0;
     if(gpuSort && (!gpuGroup || !g_bam_sort_hook)) { g_bam_error = "HLALA_SEEDS_GPU_SORT needs HLALA_SEEDS_GPU_GROUP"; return HLALA_E_ARG; }
+    const bool gpuFill = (flags & HLALA_SEEDS_GPU_FILL) != 0;
+    if(gpuFill && (!gpuSort || !g_bam_fill_hook)) { g_bam_error = "HLALA_SEEDS_GPU_FILL needs HLALA_SEEDS_GPU_SORT"; return HLALA_E_ARG; }
     int T = n_threads;
     // Default: at most 32 threads.  Measured on a 256-thread host (tools/gpu_decode_threads.sh, 8.4 M pairs, 2.6 GB of BAM): 5.2 s on 8 threads, 3.5 on 16, 2.85 on 32,
     // 3.0 on 64, 3.3-3.7 on 128 -- the phases are passes over ~12 GB of inflated records bound by memory latency and by the first touch of their
@@ -620,6 +671,7 @@ try {
     // sample after all, they are scattered then, and the host groups as ever
     struct KeptRound { DescBuf recs; const uint8_t* cb; };
     std::vector<KeptRound> kept; bool groupOnGpu = gpuGroup;
+    bool fillKept = gpuFill;                                           // HLALA_SEEDS_GPU_FILL: every round so far has stayed on the device
     auto give_up_gpu_group = [&]() { groupOnGpu = false; for(KeptRound& k : kept) scatter(k.recs, k.cb); std::vector<KeptRound>().swap(kept); };
     for(size_t b0 = 0; b0 < blocks.size();) {
         size_t b1 = b0; size_t segBytes = 0;
@@ -644,7 +696,7 @@ try {
             bam_scan_round R; memset((void*)&R, 0, sizeof(R));
             R.comp = mf.p; R.comp_bytes = mf.n; R.blocks = desc.data(); R.n_blocks = (int64_t)nBlk; R.seg_bytes = segBytes; R.carry = carry; R.first = b0 == 0 ? firstRecord : 0; R.last = lastSegment ? 1 : 0; R.in = &sin; R.crc_expect = verifyCrc ? crcExpect.data() : nullptr;
             R.user = &U; R.host_inflate = ScanRound::host_inflate; R.alloc_recs = ScanRound::alloc_recs; R.alloc_compact = ScanRound::alloc_compact; R.alloc_fallback = ScanRound::alloc_fallback;
-            R.group = groupOnGpu ? 1 : 0; R.group_first = b0 == 0 ? 1 : 0;
+            R.group = groupOnGpu ? 1 : 0; R.group_first = b0 == 0 ? 1 : 0; R.keep = fillKept && groupOnGpu ? 1 : 0;
             std::string herr;
             const int rc = g_bam_scan_hook(gpuInflater, &R, &herr);
             if(U.err) std::rethrow_exception(U.err);
@@ -652,6 +704,7 @@ try {
             S->inflate_counts[0] += R.n_gpu; S->inflate_counts[1] += R.n_retried; S->transfer_bytes[0] += R.bytes_h2d; S->transfer_bytes[1] += R.bytes_d2h;
             if(verifyCrc) { S->crc_counts[0] += R.n_gpu; S->crc_counts[1] += R.n_retried; S->crc_counts[2] += R.n_crc_recheck; }
             sGpuInflate = R.s_inflate;
+            if(!R.kept) fillKept = false;
             if(!R.fell_back) {
                 if(R.stats.status != HLALA_BAMSCAN_OK) throw Fail(hlala_bam_scan_status_text(R.stats.status));
                 const uint8_t* cb = U.compact.get();
@@ -859,6 +912,7 @@ try {
     // and builds its units by walking flag: no name is compared and no primary looked for in a clean run.  A collided run is put into (name, file order) order and
     // split as below.
     bool groupedOnGpu = false;
+    std::vector<size_t> groupedPartStart; size_t groupedDesc = 0;      // HLALA_SEEDS_GPU_FILL: where the partitions start in the grouped order, how many descriptors it has
     if(gpuGroup) {
         size_t nDesc = 0; for(const KeptRound& k : kept) nDesc += k.recs.size();
         double tHook = 0;
@@ -890,6 +944,7 @@ try {
                 while(lo < hi) { const size_t mid = (lo + hi) / 2; const uint8_t* cb; if((int)(desc_at(gperm[mid], &cb).hash >> 56) >= p) hi = mid; else lo = mid + 1; }
                 partStart[(size_t)p] = lo;
             }
+            groupedPartStart = partStart; groupedDesc = nDesc;
             std::vector<int64_t> pCollided(NPART, 0);
             parallel_for(NPART, T, [&](int64_t p, int) {
                 // the partition's records: one gather through perm (its pages are first touched here, by the thread that fills them)
@@ -907,7 +962,7 @@ try {
                 auto unit_of = [&](size_t i, size_t j, bool known, bool complete) {
                     std::vector<Unit>& U = known ? punits[(size_t)p] : UC;
                     if(!known) { bool prim[2] = {false, false}; for(size_t k = i; k < j; k++) if(R[k].flags & 2) prim[R[k].which & 1] = true; complete = long_read_mode ? prim[0] : (prim[0] && prim[1]); }
-                    if(complete) { Unit u; u.name = rec_name(R[i]); u.nameLen = R[i].nameLen; u.part = (uint32_t)p; u.first = (uint32_t)i; u.count = (uint32_t)(j - i); U.push_back(u); }
+                    if(complete) { Unit u; u.name = rec_name(R[i]); u.nameLen = R[i].nameLen; u.part = (uint16_t)p; u.host = known ? 0 : 1; u.first = (uint32_t)i; u.count = (uint32_t)(j - i); U.push_back(u); }
                     else pIncomplete[(size_t)p]++;
                 };
                 for(size_t i = 0; i < n;) {
@@ -974,7 +1029,7 @@ try {
             bool prim[2] = {false, false};
             for(size_t k = i; k < j; k++) if(R[k].flags & 2) prim[R[k].which] = true;                // takeAlignment, protoSeeds.cpp:23-36
             const bool complete = long_read_mode ? prim[0] : (prim[0] && prim[1]);                  // isComplete / isComplete_unpaired, protoSeeds.cpp:371-380
-            if(complete) { Unit u; u.name = rec_name(R[i]); u.nameLen = R[i].nameLen; u.part = (uint32_t)p; u.first = (uint32_t)i; u.count = (uint32_t)(j - i); U.push_back(u); }
+            if(complete) { Unit u; u.name = rec_name(R[i]); u.nameLen = R[i].nameLen; u.part = (uint16_t)p; u.host = 0; u.first = (uint32_t)i; u.count = (uint32_t)(j - i); U.push_back(u); }
             else pIncomplete[(size_t)p]++;
             i = j;
         }
@@ -1067,7 +1122,51 @@ try {
     Buf<int64_t>& cigCount = W->cigCount; cigCount.alloc(nR + 1); cigCount[0] = 0;
     std::vector<std::vector<uint32_t>> order((size_t)T);
     const int64_t UCH = std::max<int64_t>(16, std::min<int64_t>(8192, (int64_t)nU / ((int64_t)T * 8) + 1)); const int64_t nUChunks = ((int64_t)nU + UCH - 1) / UCH;
-    parallel_for(nUChunks, T, [&](int64_t c, int t) {
+    // HLALA_SEEDS_GPU_FILL: the device lays the sample out and fills its windows (hlala_bam_fill_create's passes over what the scan hook has kept there).  The host says
+    // which units it keeps for itself -- those it split out of collided runs (their records are no longer where the device's permutation says) and those with more
+    // than HLALA_BAM_FILL_MAX_MATE alignments on a mate (at most 16 records: no look at the mates; 17 to 32: counted; more: a host unit) -- and computes their sizes
+    // with its own sorted_mate.  Where the device has no answer the host lays out and fills the whole sample as without the flag.
+    bool filledOnGpu = false;
+    if(gpuFill) {
+        if(fillKept && groupedOnGpu && sortedOnGpu && nU > 0 && nU < ((size_t)1 << 30) && groupedDesc < ((size_t)1 << 31)) {
+            Buf<uint32_t> ufirst, ucount; ufirst.alloc(nU); ucount.alloc(nU);
+            parallel_for(nUChunks, T, [&](int64_t c, int) {
+                const size_t a = (size_t)(c * UCH), z = std::min(nU, a + (size_t)UCH);
+                for(size_t ui = a; ui < z; ui++) {
+                    const Unit& u = units[ui];
+                    bool host = u.host != 0 || u.count > 2 * HLALA_BAM_FILL_MAX_MATE;
+                    if(!host && u.count > HLALA_BAM_FILL_MAX_MATE) { uint32_t k0 = 0; const Rec* R = precs[u.part].data() + u.first; for(uint32_t k = 0; k < u.count; k++) k0 += R[k].which == 0; host = k0 > HLALA_BAM_FILL_MAX_MATE || u.count - k0 > HLALA_BAM_FILL_MAX_MATE; }
+                    ufirst[ui] = host ? HLALA_BAM_FILL_HOST : (uint32_t)(groupedPartStart[u.part] + u.first); ucount[ui] = u.count;
+                }
+            });
+            std::vector<uint32_t>& hostUnits = W->hostUnits; std::vector<int64_t> hostSizes;
+            for(size_t ui = 0; ui < nU; ui++) if(ufirst[ui] == HLALA_BAM_FILL_HOST) {
+                const Unit& u = units[ui]; const std::vector<Rec>& R = precs[u.part]; std::vector<uint32_t>& idx = order[0];
+                hostUnits.push_back((uint32_t)ui);
+                for(int m = 0; m < nm; m++) { const size_t prim = sorted_mate(precs, u, m, idx); int64_t cg = 0; for(uint32_t k : idx) cg += R[k].n_cigar; hostSizes.push_back(R[idx[prim]].l_seq); hostSizes.push_back((int64_t)idx.size()); hostSizes.push_back(cg); }
+                hostSizes.push_back((int64_t)u.nameLen + 1);
+            }
+            hlala_bam_fill_in fin; memset(&fin, 0, sizeof(fin));
+            fin.n = (int64_t)groupedDesc; fin.unit_first = ufirst.data(); fin.unit_count = ucount.data(); fin.n_units = (int64_t)nU; fin.host_sizes = hostSizes.data(); fin.n_host_units = (int64_t)hostUnits.size();
+            fin.long_read_mode = long_read_mode ? 1 : 0; fin.packed = S->packed ? 1 : 0;
+            hlala_bam_fill_stats fs; bool available = false; std::string herr; bam_fill_handle handle;
+            const int rc = g_bam_fill_hook(gpuInflater, &fin, S->read_off.data(), S->chain_off.data(), cigCount.data(), S->name_off.data(), &handle, &fs, &available, &herr);
+            if(rc != HLALA_OK) throw Fail("BAM fill on the GPU failed: " + herr);
+            if(available) {
+                if(S->read_off[0] != 0 || S->chain_off[0] != 0 || cigCount[0] != 0 || S->name_off[0] != 0 || S->read_off[nR] < 0 || S->chain_off[nR] < 0 || cigCount[nR] < 0 || S->name_off[nU] < (int64_t)nU) {
+                    if(handle.destroy) handle.destroy(handle.state);
+                    throw Fail("BAM fill on the GPU: offsets that cannot be a layout");
+                }
+                W->gpuFill = handle; filledOnGpu = true;
+                S->fill_counts[0] = (int64_t)(nU - hostUnits.size()); S->fill_counts[1] = (int64_t)hostUnits.size();
+                S->transfer_bytes[0] += fs.bytes_h2d; S->transfer_bytes[1] += fs.bytes_d2h;
+                if(getenv("HLALA_BAM_DEBUG")) fprintf(stderr, "bam-debug: layout on the GPU (%.3f s of the layout phase so far, the host units' sizes and the hook): %lld units (%lld host units), %lld chains; upload %.3f, rank %.3f, host sizes %.3f, scans %.3f, sources %.3f, download %.3f ms\n",
+                                                       since(tPhase), (long long)fs.n_units, (long long)fs.n_host_units, (long long)fs.n_chains, fs.ms_h2d, fs.ms_rank, fs.ms_host, fs.ms_scan, fs.ms_src, fs.ms_d2h);
+            } else hostUnits.clear();
+        }
+        if(!filledOnGpu) S->fill_counts[2] = 1;
+    }
+    if(!filledOnGpu) parallel_for(nUChunks, T, [&](int64_t c, int t) {
         std::vector<uint32_t>& idx = order[(size_t)t];
         const size_t a = (size_t)(c * UCH), z = std::min(nU, a + (size_t)UCH);
         for(size_t ui = a; ui < z; ui++) {
@@ -1085,8 +1184,10 @@ try {
         }
     });
     const bool dbgL = getenv("HLALA_BAM_DEBUG") != nullptr; const double tL1 = since(tPhase);
-    for(size_t r = 0; r < nR; r++) { S->read_off[r + 1] += S->read_off[r]; S->chain_off[r + 1] += S->chain_off[r]; cigCount[r + 1] += cigCount[r]; }
-    for(size_t ui = 0; ui < nU; ui++) S->name_off[ui + 1] += S->name_off[ui];
+    if(!filledOnGpu) {
+        for(size_t r = 0; r < nR; r++) { S->read_off[r + 1] += S->read_off[r]; S->chain_off[r + 1] += S->chain_off[r]; cigCount[r + 1] += cigCount[r]; }
+        for(size_t ui = 0; ui < nU; ui++) S->name_off[ui + 1] += S->name_off[ui];
+    }
     const size_t nBases = (size_t)S->read_off[nR], nChains = (size_t)S->chain_off[nR], nCig = (size_t)cigCount[nR];
     if(nChains > 0x7FFFFFFFull) throw Fail("more than 2^31 - 1 alignments in one sample: chain numbers are 32-bit");
     if(S->packed) S->read_bases_packed.alloc((nBases + nR + 1) / 2 + 2); else S->read_bases.alloc(nBases);
@@ -1185,6 +1286,19 @@ extern "C" int hlala_seed_batch_sort_counts(const hlala_seed_batch* S, int64_t c
 {
     if(!S || !counts) return HLALA_E_ARG;
     for(int i = 0; i < 3; i++) counts[i] = S->sort_counts[i];
+    return HLALA_OK;
+}
+extern "C" int hlala_seed_batch_fill_counts(const hlala_seed_batch* S, int64_t counts[3])
+{
+    if(!S || !counts) return HLALA_E_ARG;
+    for(int i = 0; i < 3; i++) counts[i] = S->fill_counts[i];
+    return HLALA_OK;
+}
+// the device milliseconds of the window passes of HLALA_SEEDS_GPU_FILL so far: chain, cigar, names, bases, download
+extern "C" int hlala_seed_batch_fill_ms(const hlala_seed_batch* S, double ms[5])
+{
+    if(!S || !ms) return HLALA_E_ARG;
+    for(int i = 0; i < 5; i++) ms[i] = S->fill_ms[i];
     return HLALA_OK;
 }
 extern "C" int hlala_seed_batch_transfer_bytes(const hlala_seed_batch* S, int64_t* bytes)

@@ -9,6 +9,7 @@
 #include "bam_scan_model.h"
 #include "bam_group_model.h"
 #include "bam_nameorder_model.h"
+#include "bam_fill_model.h"
 
 static thread_local std::string g_err;
 
@@ -123,6 +124,18 @@ int hlala_host_bam_name_order_model(const uint64_t* name_off, const uint32_t* na
     const char* why = nullptr;
     const int rc = hlala_nameorder::name_order_model(name_off, name_len, n, bytes, n_bytes, order, stats, &why);
     g_err = why ? std::string("hlala_host_bam_name_order_model: ") + why : std::string();
+    return rc;
+}
+// The layout and fill passes of the device (kernel_bamfill.hip) run serially over the same core (bam_fill_model.h): hlala_bam_fill_create followed by one
+// hlala_bam_fill_window over units [first_unit, first_unit + n_units) (n_units < 0: no window), every output but the device times, without a device.
+int hlala_host_bam_fill_model(const hlala_bam_fill_in* in, int64_t* read_off, int64_t* chain_off, int64_t* cigar_count, int64_t* name_off, int64_t first_unit, int64_t n_units,
+                              const hlala_bam_fill_out* out, hlala_bam_fill_stats* stats)
+{
+    const char* why = nullptr;
+    hlala_bamfill::FillLayout L;
+    int rc = hlala_bamfill::fill_model_create(in, read_off, chain_off, cigar_count, name_off, &L, stats, &why);
+    if(rc == HLALA_OK && n_units >= 0 && in->n_units > 0) rc = hlala_bamfill::fill_model_window(in, &L, read_off, chain_off, cigar_count, name_off, first_unit, n_units, out, &why);
+    g_err = why ? std::string("hlala_host_bam_fill_model: ") + why : std::string();
     return rc;
 }
 }

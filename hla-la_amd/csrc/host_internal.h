@@ -61,8 +61,10 @@ struct bam_scan_round {
     uint8_t* (*alloc_compact)(void* user, size_t bytes);
     uint8_t* (*alloc_fallback)(void* user, size_t bytes);              // carry + seg_bytes
     int32_t group, group_first;                                        // HLALA_SEEDS_GPU_GROUP: the round's descriptors are appended to the sample-long device arrays behind k_bam_emit (group_first: a new sample)
+    int32_t keep;                                                      // HLALA_SEEDS_GPU_FILL (with group): the round's descriptors and compact bytes stay on the device as well, for the fill hook
     // results
     bool group_appended;                                               // false: they could not be (a device allocation failed, or the round fell back): the host groups the sample itself
+    bool kept;                                                         // false: they were not kept (a device allocation failed, the round fell back, or a hook that knows no fill): the host fills the sample itself
     hlala_bam_scan_stats stats; int64_t n_gpu, n_retried, n_crc_recheck; bool fell_back; double s_inflate, s_scan; int64_t bytes_h2d, bytes_d2h;
 };
 typedef int (*bam_scan_hook_t)(void* inflater, bam_scan_round* R, std::string* err);
@@ -76,6 +78,20 @@ extern bam_group_hook_t g_bam_group_hook;
 // -- the host orders the sample itself.
 typedef int (*bam_sort_hook_t)(void* inflater, int64_t m, uint32_t* order, hlala_bam_name_order_stats* stats, bool* available, std::string* err);
 extern bam_sort_hook_t g_bam_sort_hook;
+// The layout and the fill on the GPU (HLALA_SEEDS_GPU_FILL): the fifth hook.  Behind the sort hook: a fill state over the descriptors and compact bytes the scan hook has kept
+// (in->recs and in->bytes are null, in->n is the host's count of them) and the grouping permutation: in->unit_first[u] is the place of the unit's first record in the
+// grouped order, HLALA_BAM_FILL_HOST for a host unit.  Writes the four offset arrays as hlala_bam_fill_create does and hands back a state of its own -- device buffers, a
+// stream, page-locked staging -- that does not refer to the inflater; the seed batch owns it and calls window / destroy through the pointers in the handle, from whichever
+// thread asks for a window.  *available = false (with HLALA_OK): the device does not hold the sample or could not allocate -- the host lays out and fills it itself.
+// HLALA_E_ARG: the device met a unit it cannot fill (a mate beyond 16 alignments, no primary).
+struct bam_fill_handle {
+    void* state = nullptr;
+    int (*window)(void* state, int64_t first_unit, int64_t n_units, const hlala_bam_fill_out* out, hlala_bam_fill_stats* stats, std::string* err) = nullptr;
+    void (*destroy)(void* state) = nullptr;
+};
+typedef int (*bam_fill_hook_t)(void* inflater, const hlala_bam_fill_in* in, int64_t* read_off, int64_t* chain_off, int64_t* cigar_count, int64_t* name_off, bam_fill_handle* handle,
+                               hlala_bam_fill_stats* stats, bool* available, std::string* err);
+extern bam_fill_hook_t g_bam_fill_hook;
 // hlala_bam_extract_seeds_opt (gpu = false) and hlala_bam_extract_seeds_gpu (gpu = true: the hook above inflates with `inflater`)
 int bam_extract_seeds_impl(const char* path, int32_t n_intervals, const hlala_bam_interval* iv, int32_t long_read_mode, int32_t n_threads, int32_t flags, bool gpu, void* inflater, hlala_seed_batch** out);
 

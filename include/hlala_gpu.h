@@ -647,6 +647,65 @@ int  hlala_bam_name_order(hlala_inflater* inf, const uint64_t* name_off, const u
 /* counts[3]: units ordered on the GPU, units merged in by the host (from collided runs), 1 if the host ordered the whole sample instead; (0, 0, 0) without the flag */
 int  hlala_seed_batch_sort_counts(const hlala_seed_batch* s, int64_t counts[3]);
 
+/* ------------------------------------------------------------------------------------------
+ * Filling a sample's windows on the GPU (opt-in): the sixth stage of the GPU decode, the layout and the fill of a seed batch (csrc/kernel_bamfill.hip; the rules
+ * are csrc/bam_fill_core.h, which the host runs as a model).  Read r = unit * nm + mate (nm = 1 in long-read mode, else 2) takes the unit's records of that mate in
+ * file order and puts them into the order sortChainsInSeeds leaves: descending AS, equal AS in descending file order (what std::sort + std::reverse give for at most
+ * 16 alignments, where libstdc++'s std::sort is an insertion sort; claimed up to HLALA_BAM_FILL_MAX_MATE only).  The read's primary is the first record with
+ * flags & 2 in that order; l_seq, bases and qualities (+ 33 modulo 256) are its own; chains and CIGARs are written in that order; chain_offset = 0; names carry a NUL.
+ * k_fil_rank ranks a mate on a 16-lane group by counting over lane exchanges and writes the sizes, k_fil_host writes the sizes of host units, four exclusive sums
+ * (hipcub) give the offsets, k_fil_src writes per chain its descriptor and where its CIGAR starts, and per read its primary.  A window is four launches: k_fil_chain,
+ * k_fil_cigar, k_fil_names and k_fil_bases (a wavefront per read: bases and qualities).  Every pass is a launch of its own on one stream.
+ * ---------------------------------------------------------------------------------------- */
+#define HLALA_BAM_FILL_MAX_MATE 16
+#define HLALA_BAM_FILL_HOST 0xFFFFFFFFu      /* unit_first of a host unit: the device leaves its ranges of every array alone */
+typedef struct {
+    const hlala_bam_rec* recs; int64_t n;          /* grouped: the records of unit u are recs[unit_first[u] .. + unit_count[u]) in file order */
+    const uint8_t* bytes; size_t n_bytes;          /* what rec_off points into */
+    const uint32_t* unit_first; const uint32_t* unit_count; int64_t n_units;
+    /* the sizes of the host units, in ascending unit number: per host unit and mate (l_seq of the primary, chains, CIGAR operations), then the name length + 1:
+     * 3 * nm + 1 values each */
+    const int64_t* host_sizes; int64_t n_host_units;
+    int32_t long_read_mode, packed;
+} hlala_bam_fill_in;
+/* The slices of a window [u0, u1) = reads [r0, r1) = chains [c0, c1): every pointer is where the WINDOW's part of the array starts.  read_primary [r1 - r0] (chain
+ * numbers of the sample), read_quals and read_bases [read_off[r1] - read_off[r0]] (packed: read_bases_packed instead, the bytes
+ * [(read_off[r0] + r0 + 1) >> 1, (read_off[r1] + r1 + 1) >> 1) of the packed layout of hlala_batch_in), the chain arrays [c1 - c0], cigar_off_end [c1 - c0] (entry
+ * c + 1 of the sample's cigar_off for chain c), cigar [cigar_count[r1] - cigar_count[r0]], name_chars [name_off[u1] - name_off[u0]]. */
+typedef struct {
+    int32_t* read_primary; uint8_t* read_bases; uint8_t* read_bases_packed; uint8_t* read_quals;
+    int32_t* chain_contig; int32_t* chain_pos; int32_t* chain_offset; int32_t* chain_as; uint8_t* chain_reverse;
+    int64_t* cigar_off_end; uint32_t* cigar; char* name_chars;
+} hlala_bam_fill_out;
+typedef struct {
+    int64_t n_units, n_host_units, n_reads, n_chains, n_cigar, n_bases, n_name_bytes, bytes_h2d, bytes_d2h;
+    double ms_h2d, ms_rank, ms_host, ms_scan, ms_src, ms_chain, ms_cigar, ms_names, ms_bases, ms_d2h, ms_wall;
+} hlala_bam_fill_stats;
+typedef struct hlala_bam_fill hlala_bam_fill;
+/* All arguments are host pointers.  Writes read_off, chain_off, cigar_count [n_reads + 1] and name_off [n_units + 1] (n_reads = n_units * nm) and creates a handle that
+ * owns device copies of the inputs, a stream and page-locked staging; it does not refer to the inflater afterwards (beyond its device).  Checked before anything is
+ * uploaded (HLALA_E_ARG; hlala_inflater_last_error says which): a unit range or a record extent that leaves its buffer, unit_count 0, a mate other than 0 / 1 (0 in
+ * long-read mode), a filled unit with a mate beyond HLALA_BAM_FILL_MAX_MATE or without a primary on a required mate, more than 2^31 - 1 chains, n or n_units >= 2^31.
+ * n_units == 0: HLALA_OK with zeroed stats and no handle. */
+int  hlala_bam_fill_create(hlala_inflater* inf, const hlala_bam_fill_in* in, int64_t* read_off, int64_t* chain_off, int64_t* cigar_count, int64_t* name_off,
+                           hlala_bam_fill** out, hlala_bam_fill_stats* stats);
+/* the slices of units [first_unit, first_unit + n_units); the ranges of host units inside them are written as zeros.  May be called from any thread (one call at a time
+ * per handle); sets the device of its stream itself.  hlala_bam_fill_last_error says what failed. */
+int  hlala_bam_fill_window(hlala_bam_fill* h, int64_t first_unit, int64_t n_units, const hlala_bam_fill_out* out, hlala_bam_fill_stats* stats);
+const char* hlala_bam_fill_last_error(const hlala_bam_fill* h);
+void hlala_bam_fill_destroy(hlala_bam_fill* h);
+/* Flag of hlala_bam_extract_seeds_gpu (HLALA_E_ARG without HLALA_SEEDS_GPU_SORT): the decoder's layout and fill on the device as well.  The scan hook keeps every
+ * round's descriptors and compact bytes on the device (they are still downloaded: the host needs them for collided runs and host units); behind the sort phase a fill
+ * state is built from them and the grouping permutation, which the seed batch owns until its last unit is filled.  A window asked for is then one download per array
+ * and contiguous range of units, and the host fills the host units inside it: the units it split out of collided hash runs and the units with more than
+ * HLALA_BAM_FILL_MAX_MATE alignments on a mate.  The host lays out and fills the whole sample as without the flag where an earlier stage handed the sample back or a
+ * device allocation fails.  The sample is the same to the byte. */
+#define HLALA_SEEDS_GPU_FILL 32
+/* counts[3]: units the device fills, host units, 1 if the host laid out and filled the whole sample instead; (0, 0, 0) without the flag */
+int  hlala_seed_batch_fill_counts(const hlala_seed_batch* s, int64_t counts[3]);
+/* ms[5]: device milliseconds of the window passes so far (chain, cigar, names, bases, download), summed over the windows handed out; zeros without the flag */
+int  hlala_seed_batch_fill_ms(const hlala_seed_batch* s, double ms[5]);
+
 /* Page-locked host memory for the buffers a caller hands to hlala_batch_create / hlala_batch_get_pairs_packed / the getters: transfers from and
  * to such buffers are true DMA (asynchronous, full PCIe rate); pageable buffers work everywhere, at about a third of the rate.  hlala_host_register
  * pins an existing allocation in place (e.g. the arrays of a seed batch: hlala_seed_batch_pin), hlala_host_unregister undoes it.  */
@@ -985,7 +1044,8 @@ int  hlala_abi_sizeof(const char* struct_name);
  * 6 = hlala_inflater_* / hlala_bgzf_inflate / hlala_bam_extract_seeds_gpu / hlala_seed_batch_inflate_counts exist (additive);
  * 7 = hlala_bam_scan / hlala_bam_scan_status_text and their structs, HLALA_SEEDS_GPU_PARSE, hlala_seed_batch_parse_counts / _transfer_bytes exist (additive).
  * Symbols that are purely additive no longer change it (hlala_set_pair_overflow; hlala_bgzf_inflate_crc, HLALA_SEEDS_VERIFY_CRC, hlala_seed_batch_crc_counts;
- * hlala_bam_group / _rounds, HLALA_SEEDS_GPU_GROUP, hlala_seed_batch_group_counts; hlala_bam_name_order, HLALA_SEEDS_GPU_SORT, hlala_seed_batch_sort_counts): a caller
+ * hlala_bam_group / _rounds, HLALA_SEEDS_GPU_GROUP, hlala_seed_batch_group_counts; hlala_bam_name_order, HLALA_SEEDS_GPU_SORT, hlala_seed_batch_sort_counts;
+ * hlala_bam_fill_create / _window / _destroy / _last_error, HLALA_SEEDS_GPU_FILL, hlala_seed_batch_fill_counts): a caller
  * detects them by the presence of the symbol.  A caller compares
  * hlala_abi_version() with the HLALA_ABI_VERSION it was compiled against and refuses to run on a mismatch (hla-la_amd/__init__.py and
  * hla-la_amd/host/hlala_host.hpp do). */

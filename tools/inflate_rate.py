@@ -17,7 +17,10 @@ The fourth path (its output is meant for profiles/bam_group_gpu.txt): HLALA_SEED
 read against the third path's of the same call, and hlala_bam_group alone on the descriptors of the first --scan-mb MiB reports the device time per pass.
 The fifth path (its output is meant for profiles/bam_nameorder_gpu.txt): HLALA_SEEDS_GPU_PARSE | HLALA_SEEDS_GPU_GROUP | HLALA_SEEDS_GPU_SORT in the same alternation; its sort
 phase and wall clock are read against the fourth path's of the same call, and hlala_bam_name_order alone on the unit names of the first --scan-mb MiB reports the device
-time per pass and the rounds it took."""
+time per pass and the rounds it took.
+The sixth path (its output is meant for profiles/bam_fill_gpu.txt): all of the fifth plus HLALA_SEEDS_GPU_FILL in the same alternation; its layout phase (layout + fill with
+HLALA_BAM_EAGER=1, which the caller sets for both) and wall clock are read against the fifth path's of the same call; every run prints the units the device filled and the
+host units, the device time of the window passes (hlala_seed_batch_fill_ms) and the bytes moved each way.  --paths a,b restricts the alternation to the named paths."""
 import argparse
 import os
 import sys
@@ -136,6 +139,7 @@ def main():
     ap.add_argument("--scan-mb", type=int, default=256, help="inflated MiB handed to hlala_bam_scan alone (below 4096)")
     ap.add_argument("--verify-crc", action="store_true", help="every decoder with and without HLALA_SEEDS_VERIFY_CRC in the same alternation; k_bgzf_crc32's device time beside the inflate kernel's")
     ap.add_argument("--bam", default="", help="use this BAM (reference names PRG_<n>) instead of generating one; needs --levels of the world it was made from")
+    ap.add_argument("--paths", default="", help="comma-separated paths that alternate (default: all), e.g. gpu+parse+group+sort,gpu+parse+group+sort+fill")
     ap.add_argument("--no-gpu", action="store_true", help="host engine only (a box without a GPU: checks the generator and the host figures)")
     args = ap.parse_args()
     import importlib.util
@@ -174,22 +178,28 @@ def main():
 
     def run(label, opener, timed):
         t = time.time(); S = opener(); wall = time.time() - t
-        tm = S.timing(); cnt = S.inflate_counts(); pc = S.parse_counts(); tb = S.transfer_bytes(); cc = S.crc_counts(); gc = S.group_counts(); sc = S.sort_counts(); units = S.n_units; S.close()
+        tm = S.timing(); cnt = S.inflate_counts(); pc = S.parse_counts(); tb = S.transfer_bytes(); cc = S.crc_counts(); gc = S.group_counts(); sc = S.sort_counts(); fc = S.fill_counts(); fm = S.fill_ms(); units = S.n_units; S.close()
         if timed and args.verify_crc:
             print("%-13s wall %.3f s  %s  threads %d  units %d  blocks gpu/retried/host %d/%d/%d  CRC verified gpu/host/rechecked %d/%d/%d" % (
                 label, wall, "  ".join("%s %.3f" % (k, tm[k]) for k in keys), tm["threads"], units, cnt[0], cnt[1], cnt[2], cc[0], cc[1], cc[2]))
         elif timed:
             print("%-15s wall %.3f s  %s  threads %d  units %d  blocks gpu/retried/host %d/%d/%d  records on the GPU %d in %d rounds, %d rounds fell back  PCIe up %.3f GB, down %.3f GB  grouped on the GPU %d, runs regrouped %d, by the host %d  ordered on the GPU %d, merged in %d, by the host %d" % (
                 label, wall, "  ".join("%s %.3f" % (k, tm[k]) for k in keys), tm["threads"], units, cnt[0], cnt[1], cnt[2], pc[0], pc[1], pc[2], tb[0] / 1e9, tb[1] / 1e9, gc[0], gc[1], gc[2], sc[0], sc[1], sc[2]))
-        return tm["inflate"], tm["inflate"] + tm["parse"], wall, tm["group"], tm["name_sort"]
+            if fc != (0, 0, 0):
+                print("%-15s filled on the GPU %d units, host units %d, by the host %d; window passes on the device: chain %.3f, cigar %.3f, names %.3f, bases %.3f, download %.3f ms" % (
+                    "", fc[0], fc[1], fc[2], fm[0], fm[1], fm[2], fm[3], fm[4]))
+        return tm["inflate"], tm["inflate"] + tm["parse"], wall, tm["group"], tm["name_sort"], tm["layout"], tb[0] / 1e9, tb[1] / 1e9, sum(fm[:4]), fm[4]
     host = lambda: P.bam_open_seeds(lib, bam, intervals, threads=args.threads, flags=P.SEEDS_PACKED)                 # noqa: E731
     gpu = (lambda: inf.bam_open_seeds(bam, intervals, threads=args.threads, flags=P.SEEDS_PACKED)) if inf else None      # noqa: E731
     gpu_parse = (lambda: inf.bam_open_seeds(bam, intervals, threads=args.threads, flags=P.SEEDS_PACKED | P.SEEDS_GPU_PARSE)) if inf else None      # noqa: E731
     gpu_group = (lambda: inf.bam_open_seeds(bam, intervals, threads=args.threads, flags=P.SEEDS_PACKED | P.SEEDS_GPU_PARSE | P.SEEDS_GPU_GROUP)) if inf else None      # noqa: E731
     gpu_sort = (lambda: inf.bam_open_seeds(bam, intervals, threads=args.threads, flags=P.SEEDS_PACKED | P.SEEDS_GPU_PARSE | P.SEEDS_GPU_GROUP | P.SEEDS_GPU_SORT)) if inf else None      # noqa: E731
-    res = {"host": [], "gpu": [], "gpu+parse": [], "gpu+parse+group": [], "gpu+parse+group+sort": []}
-    order = ["host", "gpu", "gpu+parse", "gpu+parse+group", "gpu+parse+group+sort"]
-    openers = {"host": host, "gpu": gpu, "gpu+parse": gpu_parse, "gpu+parse+group": gpu_group, "gpu+parse+group+sort": gpu_sort}
+    gpu_fill = (lambda: inf.bam_open_seeds(bam, intervals, threads=args.threads, flags=P.SEEDS_PACKED | P.SEEDS_GPU_PARSE | P.SEEDS_GPU_GROUP | P.SEEDS_GPU_SORT | P.SEEDS_GPU_FILL)) if inf else None      # noqa: E731
+    order = ["host", "gpu", "gpu+parse", "gpu+parse+group", "gpu+parse+group+sort", "gpu+parse+group+sort+fill"]
+    openers = {"host": host, "gpu": gpu, "gpu+parse": gpu_parse, "gpu+parse+group": gpu_group, "gpu+parse+group+sort": gpu_sort, "gpu+parse+group+sort+fill": gpu_fill}
+    if args.paths:
+        order = [k for k in order if k in args.paths.split(",")]
+    res = {k: [] for k in order}
     if args.verify_crc:
         V = P.SEEDS_PACKED | P.SEEDS_VERIFY_CRC
         openers["host+crc"] = lambda: P.bam_open_seeds(lib, bam, intervals, threads=args.threads, flags=V)                 # noqa: E731
@@ -205,9 +215,9 @@ def main():
         if len(res[k]) > 1:
             v = [x[0] for x in res[k][1:]]
             print("inflate phase, %s: median %.3f s (%.2f GB/s inflated) of %s" % (k, float(np.median(v)), n_inflated / 1e9 / float(np.median(v)), ["%.3f" % x for x in v]))
-            for j, what in ((1, "inflate + parse phases"), (3, "group phase"), (4, "sort phase"), (2, "decode, wall")):
+            for j, what in ((1, "inflate + parse phases"), (3, "group phase"), (4, "sort phase"), (5, "layout + fill phase"), (2, "decode, wall"), (6, "PCIe up, GB"), (7, "PCIe down, GB")):
                 v = [x[j] for x in res[k][1:]]
-                print("%s, %s: median %.3f s, range %.3f .. %.3f of %d runs" % (what, k, float(np.median(v)), min(v), max(v), len(v)))
+                print("%s, %s: median %.3f%s, range %.3f .. %.3f of %d runs" % (what, k, float(np.median(v)), "" if j >= 6 else " s", min(v), max(v), len(v)))
     if len(res.get("gpu+parse", [])) > 1 and len(res.get("gpu+parse+group", [])) > 1:
         for j, what in ((3, "group phase"), (2, "decode, wall")):
             a = float(np.median([x[j] for x in res["gpu+parse"][1:]])); b = float(np.median([x[j] for x in res["gpu+parse+group"][1:]]))
@@ -216,6 +226,13 @@ def main():
         for j, what in ((4, "sort phase"), (2, "decode, wall")):
             a = float(np.median([x[j] for x in res["gpu+parse+group"][1:]])); b = float(np.median([x[j] for x in res["gpu+parse+group+sort"][1:]]))
             print("HLALA_SEEDS_GPU_SORT against gpu+parse+group, %s: %+.3f s (median %.3f with against %.3f without)" % (what, b - a, b, a))
+    if len(res.get("gpu+parse+group+sort", [])) > 1 and len(res.get("gpu+parse+group+sort+fill", [])) > 1:
+        for j, what in ((5, "layout + fill phase"), (2, "decode, wall")):
+            a = float(np.median([x[j] for x in res["gpu+parse+group+sort"][1:]])); b = float(np.median([x[j] for x in res["gpu+parse+group+sort+fill"][1:]]))
+            print("HLALA_SEEDS_GPU_FILL against gpu+parse+group+sort, %s: %+.3f s (median %.3f with against %.3f without)" % (what, b - a, b, a))
+        for j, what in ((8, "window kernels, device ms"), (9, "window downloads, device ms")):
+            v = [x[j] for x in res["gpu+parse+group+sort+fill"][1:]]
+            print("HLALA_SEEDS_GPU_FILL, %s: median %.3f, range %.3f .. %.3f of %d runs" % (what, float(np.median(v)), min(v), max(v), len(v)))
     if args.verify_crc:
         for k in ("host", "gpu", "gpu+parse"):
             if len(res[k]) > 1 and len(res[k + "+crc"]) > 1:
