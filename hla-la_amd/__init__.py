@@ -1039,7 +1039,7 @@ def load_library(path: str | None = None):
 
 
 ABI_VERSION = 7              # HLALA_ABI_VERSION of include/hlala_gpu.h
-DEBUG_WC_N, DEBUG_WC_BAND_FETCH, DEBUG_WC_BAND_WHY, DEBUG_WC_BAND_TIED = 88, 48, 62, 68      # include/hlala_gpu.h: debug section
+DEBUG_WC_N, DEBUG_WC_BAND_FETCH, DEBUG_WC_BAND_WHY, DEBUG_WC_BAND_TIED, DEBUG_WC_BAND_NODES = 88, 48, 62, 68, 69      # include/hlala_gpu.h: debug section
 BUILD_AGENT_RELEASE = 2      # hlala_build_flags(): the in-memory DP class releases at agent scope (make EXTRA=-DHLALA_DP_AGENT_RELEASE)
 
 

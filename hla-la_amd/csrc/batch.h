@@ -93,6 +93,7 @@ template <template <class> class Ptr> struct DevBatchT {
     int dp_nblk;                    // blocks of k_dp_items
     int dp_band;                    // > 0: calls whose reach (read bases left + dp_band - 1 levels) stays inside a linear run of the graph go to the band kernel's lists (kernel_dp_band.hip); 0: HLALA_DP_BAND=0
     int dp_band_risky;              // tests (HLALA_DP_BAND_RISKY=1): a call is listed for the band kernel as soon as the linear run covers its read bases -- many then walk past it and exercise the fail-over
+    int dp_band_nodes;              // 1: the run of a band call is the unary path of its start NODE (FlatGraph::npf_steps / npb_steps); 0 (HLALA_DP_BAND_NODES=0): the linear run of its start level, which such a path always covers
     int dp_jf;                      // > 0: calls that meet no gap-path jump go to the lists of the jump-free instantiations, reach = read bases left + dp_jf - 1 levels (HLALA_DP_JF_MARGIN + 1)
     int dp_long;                    // > 0: a call with at least this many read bases left is LONG -- drawn before the short calls of its list (dpl_list, retry_long_counter); 0: no call is (HLALA_DP_LONG_BASES)
     Ptr<void> dp_items;                 // [2*n_chains] DpItem (kernel_dp.hip)
@@ -139,7 +140,7 @@ __host__ __device__ inline bool dp_is_long(int dpLong, int dir, int seqLen, int 
 // [7] chains stitched, [8] / [9] left / right DP calls, [12..35] retry lists of tiers 1..6 (count, fetched) x (left, right), [36] / [37] second stitch / pairing pass,
 // [40..47] round 6: the lists of the pairs with several combinations (k_pair_chains -> k_pair_multi): per pass (main / side stream) count and fetched of class 0, of class 1; round 5: items fetched by the three band kernels (left, right each), the fail-over list's counts and fetch counters, band calls that
 // failed over, band calls listed, jump-free calls that met a jump, and why band calls failed ([WC_BAND_WHY + 2 .. + 5]: past the staged levels, past the linear run, too
-// many iterations, too many tied end cells)
+// many iterations, too many tied end cells); [WC_BAND_NODES]: band calls listed through the path of their start node that the linear run of its level does not cover
 // [72..79] the overflow lists of the pairing passes (k_pair_chains -> k_pair_overflow, kernel_pair_overflow.hip): per pass (main / side stream) pairs listed, fetched,
 // scored, refused for want of slab
 // [80..87] unused: [72..87] counted the calls of the two-track band kernels of round 6, which were removed; the debug export (include/hlala_gpu.h: HLALA_DEBUG_WC_N) stays at
@@ -147,7 +148,7 @@ __host__ __device__ inline bool dp_is_long(int dpLong, int dir, int seqLen, int 
 // [88..99] the LONG calls on the retry lists of tiers 1..6 x (left, right).  A row of retry_list is filled from both ends: a long call takes entry q of
 // work_counter[WC_RETRY_LONG + ...] from the front, a short one entry n_chains - 1 - q of the row's old counter ([12 + 4(k-1) + 2p], which with B.dp_long = 0 counts every call,
 // as it always did) from the back; the class that draws the row takes the long ones first (retry_entry).  A row holds a direction's items at most once each: the ends never meet.
-enum { WC_PAIR_MULTI = 40, WC_PAIR_OVER = 72, WC_BAND_FETCH = 48, WC_FO_COUNT = 54, WC_FO_FETCH = 56, WC_BAND_FAILED = 58, WC_BAND_CALLS = 59, WC_JF_FAILED = 60, WC_BAND_WHY = 62, WC_BAND_TIED = 68,
+enum { WC_PAIR_MULTI = 40, WC_PAIR_OVER = 72, WC_BAND_FETCH = 48, WC_FO_COUNT = 54, WC_FO_FETCH = 56, WC_BAND_FAILED = 58, WC_BAND_CALLS = 59, WC_JF_FAILED = 60, WC_BAND_WHY = 62, WC_BAND_TIED = 68, WC_BAND_NODES = 69,
        WC_RETRY_LONG = 88, WC_N = 100 };
 // counters of the retry list of tier k = 1..6 and direction p: the short calls pushed (from the back), the fetch counter of the whole row, the long calls pushed (from the front)
 __host__ __device__ inline int wc_retry_short(int tier, int dir) { return 12 + 4 * (tier - 1) + 2 * dir; }
@@ -158,7 +159,7 @@ __host__ __device__ inline int retry_entry(int w, int nLong, int nChains) { retu
 // the fail-over list of the first classes: calls the band kernel (kernel_dp_band.hip) or the jump-free instantiation could not finish; k_dp<DpTiny, 0> draws it after
 // its own lists.  Entries (slots of dp_items) at retry_list[(14 + direction) * n_chains ...], counts in work_counter[WC_FO_COUNT + direction].
 // ---- capacities of the band kernels (kernel_dp_band.hip): read bases a call may have left for the instantiation with 16 / 32 / 64 lanes per call; k_dp_items lists a call
-// for one of them when the linear run ahead of its start level covers bases left + margin + min(bases left + 6, 40) levels
+// for one of them when the unary path ahead of its start node (dp_band_nodes = 0: the linear run ahead of its start level) covers bases left + margin + min(bases left + 6, 40) steps
 constexpr int BAND_MAXJ16 = 15, BAND_MAXJ32 = 31, BAND_MAXJ64 = 48;
 
 enum {

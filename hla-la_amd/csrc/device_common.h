@@ -44,7 +44,11 @@ template <template <class> class Ptr> struct DevGraphT {
     Ptr<const int> jb_off; Ptr<const int> jb_node; Ptr<const int> jb_path; Ptr<const int> jb_lvl;
     Ptr<const uint8_t> out_prank; Ptr<const uint8_t> in_prank; Ptr<const uint8_t> jf_prank; Ptr<const uint8_t> jb_prank;   // rank among the node's earlier entries to the same target (flat_graph.hpp)
     Ptr<const uint8_t> jfree_out; Ptr<const uint8_t> jfree_in;   // [L] levels without a gap-path jump from this level on, in either direction (flat_graph.hpp)
-    Ptr<const u32> lin_label; Ptr<const uint8_t> lin_out; Ptr<const uint8_t> lin_in; Ptr<const int> lin_eid;   // [L] linear steps and their run lengths (flat_graph.hpp; kernel_dp_band.hip)
+    Ptr<const uint8_t> lin_out; Ptr<const uint8_t> lin_in;   // [L] run lengths of the linear steps (flat_graph.hpp): the level rule of HLALA_DP_BAND_NODES=0 and the counter of what the node paths add
+    // [N] node paths of the band kernels (flat_graph.hpp; kernel_dp_band.hip), f: forward over out-edges, b: backward over in-edges.  By position: labels of the step, its first edge,
+    // the node, steps along consecutive positions; by node: its position.  A run of linear steps is a run of positions, so lin_label / lin_eid are not uploaded.
+    Ptr<const u32> npf_label; Ptr<const u32> npb_label; Ptr<const int> npf_eid; Ptr<const int> npb_eid; Ptr<const int> npf_node; Ptr<const int> npb_node;
+    Ptr<const uint8_t> npf_steps; Ptr<const uint8_t> npb_steps; Ptr<const int> npf_pos; Ptr<const int> npb_pos;
     Ptr<const int4> nrec_out;      // [2*N] 32-byte node records of the extension DP (flat_graph.hpp)
     Ptr<const int4> nrec_in;
     Ptr<const int> path_len;       // [P]

@@ -309,6 +309,43 @@ std::string flatten_graph(const hlala_graph_desc* g, const hlala_contigs_desc* c
             run = 0;
             for(int32_t l = 0; l < F.L; l++) { run = (l > 0 && F.lin_label[(size_t)l - 1]) ? std::min(255, run + 1) : 0; F.lin_in[(size_t)l] = (uint8_t)run; }
         }
+        // ---- node paths (flat_graph.hpp): unary nodes, their primary predecessors, the path order and the steps along it; one pass over the edges and three over the nodes
+        auto paths = [&](const std::vector<int32_t>& off, const std::vector<int32_t>& to, const std::vector<uint8_t>& lab, const std::vector<int32_t>& eid,
+                         const std::vector<int32_t>& joff, const int32_t dir, std::vector<uint32_t>& pLabel, std::vector<int32_t>& pEid, std::vector<int32_t>& pNode,
+                         std::vector<uint8_t>& pSteps, std::vector<int32_t>& pos) {
+            std::vector<int32_t> succ((size_t)N, -1), prim((size_t)N, -1);       // succ[u] >= 0: u is unary; prim[v]: primary predecessor of v
+            std::vector<uint32_t> word((size_t)N, 0);
+            for(int32_t u = 0; u < N; u++) {
+                const int32_t e0 = off[u], K = off[u + 1] - e0;
+                if(K < 1 || K > 4 || joff[u + 1] > joff[u]) continue;
+                const int32_t v = to[e0];
+                if(F.node_level[v] != F.node_level[u] + dir) continue;
+                uint32_t w = 0; bool ok = true;
+                for(int32_t k = 0; k < K && ok; k++) { ok = to[e0 + k] == v && lab[e0 + k] != '_' && lab[e0 + k] != 0; w |= (uint32_t)lab[e0 + k] << (8 * k); }
+                if(!ok) continue;
+                succ[(size_t)u] = v; word[(size_t)u] = w;
+                if(prim[(size_t)v] < 0) prim[(size_t)v] = u;                     // (u ascends: the first is the smallest)
+            }
+            pLabel.assign((size_t)N, 0); pEid.assign((size_t)N, -1); pNode.assign((size_t)N, 0); pSteps.assign((size_t)N, 0); pos.assign((size_t)N, 0);
+            int32_t p = 0;
+            for(int32_t h = 0; h < N; h++) {
+                if(prim[(size_t)h] >= 0) continue;                               // not a chain head: its primary's chain places it
+                for(int32_t u = h;;) {
+                    pos[(size_t)u] = p; pNode[(size_t)p] = u; pLabel[(size_t)p] = word[(size_t)u]; if(succ[(size_t)u] >= 0) pEid[(size_t)p] = eid[off[u]];
+                    p++;
+                    const int32_t v = succ[(size_t)u];
+                    if(v < 0 || prim[(size_t)v] != u) break;
+                    u = v;
+                }
+            }
+            for(int32_t q = N - 1; q >= 0; q--) {
+                const int32_t u = pNode[(size_t)q], v = succ[(size_t)u];
+                if(v < 0) continue;
+                pSteps[(size_t)q] = (uint8_t)std::min(255, 1 + (prim[(size_t)v] == u ? (int)pSteps[(size_t)q + 1] : 0));
+            }
+        };
+        paths(F.out_off, F.out_to, F.out_label, F.out_eid, F.djf_off, 1, F.npf_label, F.npf_eid, F.npf_node, F.npf_steps, F.npf_pos);
+        paths(F.in_off, F.in_from, F.in_label, F.in_eid, F.djb_off, -1, F.npb_label, F.npb_eid, F.npb_node, F.npb_steps, F.npb_pos);
     }
     return "";
 }

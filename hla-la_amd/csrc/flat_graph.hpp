@@ -73,6 +73,21 @@ struct FlatGraph {
     std::vector<uint32_t> lin_label;                   // [L]
     std::vector<uint8_t> lin_out, lin_in;              // [L]
     std::vector<int32_t> lin_eid;                      // [L]
+    // NODE PATHS (kernel_dp_band.hip): the same band of cells exists wherever the nodes a call can REACH form a path, whatever else their levels hold.  Forward
+    // (npf_*): node u is UNARY when it has one to four out-edges, all of them end in ONE node v = succ(u) on the next level, no label is '_' or 0 and u has no
+    // forward gap-path jump (djf_off).  The PRIMARY predecessor of v is the smallest-numbered unary u with succ(u) = v.  Nodes are laid out in PATH ORDER:
+    // pos(succ(u)) = pos(u) + 1 exactly when u is the primary predecessor of succ(u) -- chains start at the nodes without a unary predecessor, in node order, and
+    // follow the successor while the chain's node is its primary.  By position: npf_label = the labels of the node's out-edges in CSR order, one per byte from the
+    // low byte up (0: not unary), npf_eid = creation index of its first out-edge (-1: not unary), npf_node = the node, npf_steps = unary steps that can be walked
+    // along consecutive positions: 0 when not unary, else 1 + (steps of the next position when the node is the primary of its successor, else 0), capped at
+    // 255.  npf_pos: node -> position.  Backward (npb_*): the same over in-edges -- one to four, all from one node on the level before, in in-CSR order, no
+    // backward jump (djb_off); positions then ASCEND towards lower levels.  A run of linear steps (lin_out / lin_in) is such a run of positions: its nodes have one
+    // predecessor each, which is their primary.
+    std::vector<uint32_t> npf_label, npb_label;        // [N] by position
+    std::vector<int32_t> npf_eid, npb_eid;             // [N] by position
+    std::vector<int32_t> npf_node, npb_node;           // [N] by position
+    std::vector<uint8_t> npf_steps, npb_steps;         // [N] by position
+    std::vector<int32_t> npf_pos, npb_pos;             // [N] by node
     std::vector<uint8_t> gap_stretch;            // [L-1]
     // level -> (sequence id, position) CSR, entries sorted by sequence id
     std::vector<int64_t> lp_off;                 // [L+1]

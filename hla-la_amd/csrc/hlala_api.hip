@@ -99,6 +99,7 @@ struct hlala_ctx {
     bool side_after_pair = false; // HLALA_SIDE_AFTER_PAIR=1: the side-stream classes are queued behind the main stream's stitch and pairing passes instead of beside them (measured: the pairing pass 20.9 -> 4.1 ms, but the next batch's projection 35.5 -> 54.8 ms beside the wide class instead; step 183.4 -> 185.5 ms)
     bool rows_all = false;        // HLALA_ROWS_ALL=1: column rows for every chain of a batch, the filters run with the projection (rounds 1-4)
     bool band_risky = false;      // HLALA_DP_BAND_RISKY=1 (tests: force fail-overs of the band kernel)
+    bool band_nodes = true;       // HLALA_DP_BAND_NODES=0: a call is listed for the band kernel by the linear run of its start LEVEL, not by the path of its start node (A/B and parity)
     int band_grid = 0, band_margin = 8;      // the band kernel in front of the 16-lane class (kernel_dp_band.hip): blocks (0: HLALA_DP_BAND=0) and the levels beyond the read bases left a call is taken to reach (HLALA_DP_BAND_MARGIN)
     // The DP classes by tier (0 DpTiny, 1 DpMid, 2 DpSmall, 3 DpWide, 4 DpBroad, 5 DpLarge, 6 DpHuge), filled once by hlala_create; dp_jf = the jump-free instantiation of
     // the 16-lane class, launched in front of tier 0 on tier 0's slabs.  INVARIANT: the slabs of the tiers >= DP_SIDE_TIER belong to the context, not to a batch, and are
@@ -473,7 +474,9 @@ int hlala_create(hlala_ctx** out, int device, void* stream, const hlala_graph_de
     UPG(jb_off, F.djb_off); UPG(jb_node, F.djb_node); UPG(jb_path, F.djb_path);
     UPG(jf_lvl, F.djf_lvl); UPG(jb_lvl, F.djb_lvl);
     UPG(jfree_out, F.jfree_out); UPG(jfree_in, F.jfree_in);
-    UPG(lin_label, F.lin_label); UPG(lin_out, F.lin_out); UPG(lin_in, F.lin_in); UPG(lin_eid, F.lin_eid);
+    UPG(lin_out, F.lin_out); UPG(lin_in, F.lin_in);
+    UPG(npf_label, F.npf_label); UPG(npf_eid, F.npf_eid); UPG(npf_node, F.npf_node); UPG(npf_steps, F.npf_steps); UPG(npf_pos, F.npf_pos);
+    UPG(npb_label, F.npb_label); UPG(npb_eid, F.npb_eid); UPG(npb_node, F.npb_node); UPG(npb_steps, F.npb_steps); UPG(npb_pos, F.npb_pos);
     UPG(out_prank, F.out_prank); UPG(in_prank, F.in_prank); UPG(jf_prank, F.jf_prank); UPG(jb_prank, F.jb_prank);
     { int* p_ = nullptr; rc = dev_upload(c, c->allocs, F.nrec_out.data(), F.nrec_out.size(), &p_); if(rc) return fail(rc); G.nrec_out = (const int4*)p_;
       rc = dev_upload(c, c->allocs, F.nrec_in.data(), F.nrec_in.size(), &p_); if(rc) return fail(rc); G.nrec_in = (const int4*)p_; }
@@ -512,6 +515,7 @@ int hlala_create(hlala_ctx** out, int device, void* stream, const hlala_graph_de
     c->band_grid = cus * 20;          // a few KB of LDS per block, five waves per SIMD (96 VGPRs, nothing spilled)
     if(const char* e = getenv("HLALA_DP_BAND")) { if(atoi(e) == 0) c->band_grid = 0; }      // (A/B and parity: every call in the hashed-frontier classes)
     if(const char* e = getenv("HLALA_DP_BAND_RISKY")) c->band_risky = atoi(e) != 0;
+    if(const char* e = getenv("HLALA_DP_BAND_NODES")) c->band_nodes = atoi(e) != 0;
     if(const char* e = getenv("HLALA_ROWS_ALL")) c->rows_all = atoi(e) != 0;
     if(const char* e = getenv("HLALA_SIDE_AFTER_PAIR")) c->side_after_pair = atoi(e) != 0;
     if(const char* e = getenv("HLALA_POOL_CAP_GB")) { const long g = atol(e); if(g >= 0 && g <= 1024) c->pool_cap = (size_t)g << 30; }
@@ -675,6 +679,7 @@ static int batch_alloc_outputs(hlala_ctx* c, hlala_batch* b)
     B.dp_jf = c->jf_margin + 1; B.dp_long = c->dp_long_bases;
     B.dp_band = c->band_grid > 0 ? c->band_margin + 1 : 0;
     B.dp_band_risky = c->band_risky ? 1 : 0;
+    B.dp_band_nodes = c->band_nodes ? 1 : 0;
     AL(dp_blk, (size_t)DPL_N * B.dp_nblk + 1, false); AL(dp_list, 2 * nc, false);
     if(!b->prepared) {
         B.chain_order = nullptr; B.chain_bucket = nullptr; B.order_hist = nullptr; B.order_shift = c->order_shift; B.order_nb = c->order_nb; B.order_cost = c->order_cost; B.long_chunk_nodes = c->long_chunk_nodes; B.long_max_segs = c->long_max_segs;
@@ -1043,9 +1048,9 @@ static int dp_band(hlala_ctx* c, hlala_batch* b)
     if(!b->band_used) return HLALA_OK;
     const DpItem* items = (const DpItem*)B.dp_items; const u32 seed = c->params.rng_seed + 2u * b->first_chain;
     HIP_TRY(c, hipEventRecord(b->ev[EV_DP_BAND_BEGIN], c->active));
-    hipLaunchKernelGGL((k_dp_band<16>), dim3(c->band_grid), dim3(64), 0, c->active, c->G, b->B, items, seed, (const uint8_t*)B.read_bases, c->G.lin_label, c->G.lin_eid);
-    hipLaunchKernelGGL((k_dp_band<32>), dim3(c->band_grid), dim3(64), 0, c->active, c->G, b->B, items, seed, (const uint8_t*)B.read_bases, c->G.lin_label, c->G.lin_eid);
-    hipLaunchKernelGGL((k_dp_band<64>), dim3(c->band_grid), dim3(64), 0, c->active, c->G, b->B, items, seed, (const uint8_t*)B.read_bases, c->G.lin_label, c->G.lin_eid);
+    hipLaunchKernelGGL((k_dp_band<16>), dim3(c->band_grid), dim3(64), 0, c->active, c->G, b->B, items, seed, (const uint8_t*)B.read_bases);
+    hipLaunchKernelGGL((k_dp_band<32>), dim3(c->band_grid), dim3(64), 0, c->active, c->G, b->B, items, seed, (const uint8_t*)B.read_bases);
+    hipLaunchKernelGGL((k_dp_band<64>), dim3(c->band_grid), dim3(64), 0, c->active, c->G, b->B, items, seed, (const uint8_t*)B.read_bases);
     STEP(check_launch(c, "k_dp_band"));
     HIP_TRY(c, hipEventRecord(b->ev[EV_DP_BAND_END], c->active)); return HLALA_OK;
 }
@@ -1944,7 +1949,7 @@ extern "C" int hlala_debug_memory(hlala_ctx* c, hlala_batch* b, unsigned long lo
 // the batch's work counters (diagnostics: item counts of the lists, fail-over reasons of the band kernel -- batch.h)
 extern "C" int hlala_debug_work_counters(hlala_ctx* c, hlala_batch* b, int* out, int capacity)
 {
-    static_assert(WC_N >= HLALA_DEBUG_WC_N && WC_BAND_FETCH == HLALA_DEBUG_WC_BAND_FETCH && WC_BAND_WHY == HLALA_DEBUG_WC_BAND_WHY && WC_BAND_TIED == HLALA_DEBUG_WC_BAND_TIED, "include/hlala_gpu.h: debug section");
+    static_assert(WC_N >= HLALA_DEBUG_WC_N && WC_BAND_FETCH == HLALA_DEBUG_WC_BAND_FETCH && WC_BAND_WHY == HLALA_DEBUG_WC_BAND_WHY && WC_BAND_TIED == HLALA_DEBUG_WC_BAND_TIED && WC_BAND_NODES == HLALA_DEBUG_WC_BAND_NODES, "include/hlala_gpu.h: debug section");
     DEV_GUARD(c);
     ReaderScope rscope_(c, b); if(rscope_.rc) return rscope_.rc;
     if(!c || !b || !out || capacity < 0) return HLALA_E_ARG;
@@ -1956,7 +1961,7 @@ extern "C" int hlala_debug_work_counters(hlala_ctx* c, hlala_batch* b, int* out,
 }
 
 // diagnostics (tools/tier_predict.py): the DP items of the batch's last extension stage ([2 * n_chains] records of 8 ints: item, read offset, read length, start offset,
-// start level, start node, class, linear run; item < 0: no call) and its retry lists ([16 * n_chains] slots of dp_items; counts in the work counters)
+// start level, start node, class | steps of the band run << 8, start position on the node path; item < 0: no call) and its retry lists ([16 * n_chains] slots of dp_items; counts in the work counters)
 extern "C" int hlala_debug_dp_items(hlala_ctx* c, hlala_batch* b, int* items_out, long long items_capacity_bytes, int* retry_out, long long retry_capacity_bytes)
 {
     DEV_GUARD(c);

@@ -58,6 +58,15 @@ int hlala_host_linear(const hlala::FlatGraph* F, uint32_t* lin_label, int32_t* l
     memcpy(lin_out, F->lin_out.data(), F->lin_out.size()); memcpy(lin_in, F->lin_in.data(), F->lin_in.size());
     return 0;
 }
+// node paths of one direction (flat_graph.hpp; kernel_dp_band.hip), [N] each: label word, first edge, node and steps by position, position by node
+int hlala_host_node_paths(const hlala::FlatGraph* F, int forward, uint32_t* label, int32_t* eid, int32_t* node, uint8_t* steps, int32_t* pos)
+{
+    const size_t n = (size_t)F->N;
+    memcpy(label, (forward ? F->npf_label : F->npb_label).data(), n * 4); memcpy(eid, (forward ? F->npf_eid : F->npb_eid).data(), n * 4);
+    memcpy(node, (forward ? F->npf_node : F->npb_node).data(), n * 4); memcpy(steps, (forward ? F->npf_steps : F->npb_steps).data(), n);
+    memcpy(pos, (forward ? F->npf_pos : F->npb_pos).data(), n * 4);
+    return 0;
+}
 // The DEFLATE decoder core of the device kernel (inflate_core.h) with a serial copy loop around it: raw DEFLATE bytes comp[0, clen) -> out[0, isize).
 // Returns a HLALA_INFLATE_* status; never reads or writes outside the two ranges.
 int hlala_host_inflate_model(const uint8_t* comp, uint32_t clen, uint8_t* out, uint32_t isize)

@@ -1582,19 +1582,29 @@ __global__ void k_dp_items(const DevGraph G, const DevBatch B, DpItem* items)
     //  at 6 + 2 per level; DP_JF_MARGIN on top.  B.dp_jf = the margin + 1, 0 = off.)
     if(needL && B.dp_jf) { const int reach = itL.start_seq + B.dp_jf - 1; jfL = reach < 255 && (int)G.jfree_in[itL.startLevel] > reach; }
     if(needR && B.dp_jf) { const int reach = itR.seqLen - itR.start_seq + B.dp_jf - 1; jfR = reach < 255 && (int)G.jfree_out[itR.startLevel] > reach; }
-    // Band calls (kernel_dp_band.hip): the levels the call can reach -- read bases left + dp_band - 1 -- are a run of LINEAR steps (FlatGraph::lin_out / lin_in: one
-    // node per level, one edge per step, no '_' label, no jump).  A call that walks further anyway fails over to the general list.
-    bool bdL = false, bdR = false;
-    int runL = 0, runR = 0;
+    // Band calls (kernel_dp_band.hip): the nodes the call can reach -- within read bases left + dp_band - 1 levels -- are a PATH: unary steps along consecutive
+    // positions of the start node's path order (FlatGraph::npf_steps / npb_steps: one successor per node, no '_' label, no jump).  With dp_band_nodes = 0 the run is
+    // that of the start LEVEL (lin_out / lin_in: one node per level), which the node path always covers.  A call that walks further anyway fails over to the general list.
+    bool bdL = false, bdR = false, newL = false, newR = false;      // new: listed through the node path where the level rule would not have listed it (statistics)
+    int runL = 0, runR = 0, posL = 0, posR = 0;
     int clsL = jfL ? 1 : 0, clsR = jfR ? 1 : 0;       // the list an item goes to: 0 general, 1 jump-free, 2 / 3 / 4 band kernel with 16 / 32 / 64 lanes per call
     // (levels a call is taken to reach: while it has read bases left a cell sits at most dp_band - 1 levels beyond them; afterwards the tail -- one sequence gap per
     //  iteration from the best complete cell, score <= 2 * bases, -6 then -2 per level down to the threshold of -16, at most 40 iterations -- walks up to bases + 6 more)
-    if(needL && B.dp_band) { const int jm = itL.start_seq, reach = jm + B.dp_band - 1; runL = (int)G.lin_in[itL.startLevel]; bdL = jm <= BAND_MAXJ64 && runL >= (B.dp_band_risky ? jm : reach + min(jm + 6, 40)); if(bdL) clsL = jm <= BAND_MAXJ16 ? 2 : (jm <= BAND_MAXJ32 ? 3 : 4); }
-    if(needR && B.dp_band) { const int jm = itR.seqLen - itR.start_seq, reach = jm + B.dp_band - 1; runR = (int)G.lin_out[itR.startLevel]; bdR = jm <= BAND_MAXJ64 && runR >= (B.dp_band_risky ? jm : reach + min(jm + 6, 40)); if(bdR) clsR = jm <= BAND_MAXJ16 ? 2 : (jm <= BAND_MAXJ32 ? 3 : 4); }
+    if(needL && B.dp_band) {
+        const int jm = itL.start_seq, reach = jm + B.dp_band - 1, need = B.dp_band_risky ? jm : reach + min(jm + 6, 40), lvlRun = (int)G.lin_in[itL.startLevel];
+        posL = G.npb_pos[itL.startNode]; runL = B.dp_band_nodes ? (int)G.npb_steps[posL] : lvlRun;
+        bdL = jm <= BAND_MAXJ64 && runL >= need; newL = bdL && lvlRun < need; if(bdL) clsL = jm <= BAND_MAXJ16 ? 2 : (jm <= BAND_MAXJ32 ? 3 : 4);
+    }
+    if(needR && B.dp_band) {
+        const int jm = itR.seqLen - itR.start_seq, reach = jm + B.dp_band - 1, need = B.dp_band_risky ? jm : reach + min(jm + 6, 40), lvlRun = (int)G.lin_out[itR.startLevel];
+        posR = G.npf_pos[itR.startNode]; runR = B.dp_band_nodes ? (int)G.npf_steps[posR] : lvlRun;
+        bdR = jm <= BAND_MAXJ64 && runR >= need; newR = bdR && lvlRun < need; if(bdR) clsR = jm <= BAND_MAXJ16 ? 2 : (jm <= BAND_MAXJ32 ? 3 : 4);
+    }
+    // (the last two words of an item: class | steps of the run << 8, start position on the node path -- the band kernel stages from there)
     if(t < nOrd) {
         int4* sl = (int4*)(items + t); int4* sr = (int4*)(items + (size_t)B.n_chains + t);
-        if(needL) { sl[0] = make_int4(itL.item, itL.rOff, itL.seqLen, itL.start_seq); sl[1] = make_int4(itL.startLevel, itL.startNode, clsL, runL); } else sl[0] = make_int4(-1, 0, 0, 0);
-        if(needR) { sr[0] = make_int4(itR.item, itR.rOff, itR.seqLen, itR.start_seq); sr[1] = make_int4(itR.startLevel, itR.startNode, clsR, runR); } else sr[0] = make_int4(-1, 0, 0, 0);
+        if(needL) { sl[0] = make_int4(itL.item, itL.rOff, itL.seqLen, itL.start_seq); sl[1] = make_int4(itL.startLevel, itL.startNode, clsL | (runL << 8), posL); } else sl[0] = make_int4(-1, 0, 0, 0);
+        if(needR) { sr[0] = make_int4(itR.item, itR.rOff, itR.seqLen, itR.start_seq); sr[1] = make_int4(itR.startLevel, itR.startNode, clsR | (runR << 8), posR); } else sr[0] = make_int4(-1, 0, 0, 0);
     }
     // ---- how many items of each of the fourteen lists (three band lists, left / right each; jump-free and general, long / short per direction: batch.h) this block holds: k_order_scan turns the counts of all
     // blocks into the blocks' places in the dense lists, k_dp_lists writes the slot numbers there -- in position order, nothing is left to the atomics.
@@ -1607,12 +1617,14 @@ __global__ void k_dp_items(const DevGraph G, const DevBatch B, DpItem* items)
     if(lane == 0 && nShared) atomicAdd(&B.counters[CNT_DP_SHARED], (u64)nShared);
     const u64 mL = __ballot(needL), mR = __ballot(needR);
     const int kL = needL ? dpl_list(clsL, 0, dp_is_long(B.dp_long, 0, itL.seqLen, itL.start_seq)) : -1, kR = needR ? dpl_list(clsR, 1, dp_is_long(B.dp_long, 1, itR.seqLen, itR.start_seq)) : -1;
+    const int mNew = __popcll(__ballot(newL)) + __popcll(__ballot(newR));
     const u64 mJL = __ballot(needL && clsL == 1), mJR = __ballot(needR && clsR == 1), mBL = __ballot(needL && clsL >= 2), mBR = __ballot(needR && clsR >= 2);
     if(lane == 0) {
         if(mL) atomicAdd(&B.work_counter[8], __popcll(mL));
         if(mR) atomicAdd(&B.work_counter[9], __popcll(mR));
         if(mJL | mJR) atomicAdd(&B.work_counter[6], __popcll(mJL) + __popcll(mJR));
         if(mBL | mBR) atomicAdd(&B.work_counter[WC_BAND_CALLS], __popcll(mBL) + __popcll(mBR));
+        if(mNew) atomicAdd(&B.work_counter[WC_BAND_NODES], mNew);
     }
 #pragma unroll
     for(int k = 0; k < DPL_N; k++) {
@@ -1634,8 +1646,8 @@ __global__ void k_dp_lists(const DevBatch B, const DpItem* __restrict__ items)
     if(t < nOrd) {
         const int4* sl = (const int4*)(items + t); const int4* sr = (const int4*)(items + (size_t)B.n_chains + t);
         const int4 a = sl[0], b = sr[0];          // (item, rOff, seqLen, start_seq)
-        if(a.x >= 0) kL = dpl_list(sl[1].z, 0, dp_is_long(B.dp_long, 0, a.z, a.w));
-        if(b.x >= 0) kR = dpl_list(sr[1].z, 1, dp_is_long(B.dp_long, 1, b.z, b.w));
+        if(a.x >= 0) kL = dpl_list(sl[1].z & 255, 0, dp_is_long(B.dp_long, 0, a.z, a.w));
+        if(b.x >= 0) kR = dpl_list(sr[1].z & 255, 1, dp_is_long(B.dp_long, 1, b.z, b.w));
     }
     __shared__ int waveCnt[DPL_N][4];      // [list][wave of the block]
     const int lane = lane_id(), wv = (int)(threadIdx.x >> 6);

@@ -1,8 +1,11 @@
-// kernel_dp_band.hip -- the extension DP on LINEAR stretches of the graph: anti-diagonals of score cells held in registers, one lane per read offset.
+// kernel_dp_band.hip -- the extension DP on UNBRANCHED NODE PATHS of the graph: anti-diagonals of score cells held in registers, one lane per read offset.
 //
 // extensionAligner::fullNeedleman_diagonal_extension_gapJumper (mapper/aligner/extensionAligner.cpp:335-1556) is a sparse frontier over cells
-// (level x, read offset y, node rank z) because the graph branches.  94 % of the levels of an MHC-scale graph hold ONE node, and from most start cells the
-// levels a call can reach are a run of such levels joined by single edges (FlatGraph::lin_out / lin_in): there z = 0 everywhere, the frontier is a plain band,
+// (level x, read offset y, node rank z) because the graph branches.  The cells a call can create sit on nodes REACHABLE from its start node, and from most start
+// nodes those are a path: every node within reach has one successor, joined by one to four parallel edges without '_' labels or gap-path jumps (FlatGraph::npf_* /
+// npb_*: such paths laid out at consecutive positions).  94 % of the levels of an MHC-scale graph hold one node and are such paths; in the gene windows a level holds
+// tens to hundreds of nodes, most of which still have one successor.  On a path every level within reach holds ONE reachable node -- its rank z is whatever the level's
+// other nodes make it, and it never enters the recurrence --, the frontier is a plain band,
 // and the whole machine of kernel_dp.hip -- target hash, compare-and-swap claims, cell table in HBM, early-cell hash, rank sort -- has nothing to do:
 //
 //   cell (i, j) = (levels walked from the start, read bases consumed); anti-diagonal d = i + j = the iteration that creates it (:531); no cell is met twice;
@@ -45,7 +48,7 @@ struct __align__(16) BandLds {
     u32 bt[C::MAXD / 8][C::GW];           // back pointers: 4 bits per (iteration, lane)
     unsigned short steps[C::MAXD];        // steps of the chosen path: kind | i << 2 | j << 9
     unsigned short tieD[BAND_TIES];       // iterations of the sequence-complete cells that equal the best one (entry 0 lives in a register)
-    u32 ls[C::REACH];                     // ls[t] = labels of the (one to four parallel) edges of the t-th step away from the start level (lin_label)
+    u32 ls[C::REACH];                     // ls[t] = labels of the (one to four parallel) edges of the t-th step away from the start node (npf_label / npb_label at the start position + t)
 };
 
 // the value lane l - 1 of the call's group holds (DP_NEG for its first lane)
@@ -65,8 +68,7 @@ template <int GW> __device__ __forceinline__ int band_prev(int v, int gl)
 
 template <class C, bool FWD, class DG, class DB>
 __device__ __forceinline__ void band_pass(const DG& G, const DB& B, const DpItem* __restrict__ items, const u32 rng_seed, const uint8_t* __restrict__ readBases,
-                                          const u32* __restrict__ linLabel, const int* __restrict__ linEid, BandLds<C>& S,
-                                          u64& accCalls, u64& accIters, u64& accCells, u64& accEdges)
+                                          BandLds<C>& S, u64& accCalls, u64& accIters, u64& accCells, u64& accEdges)
 {
     constexpr int GW = C::GW, NG = 64 / GW;
     const int lane = lane_id(), g = lane / GW, gl = lane & (GW - 1), rowBase = lane & ~(GW - 1);
@@ -98,14 +100,14 @@ __device__ __forceinline__ void band_pass(const DG& G, const DB& B, const DpItem
         int idx = 0; int4 a = make_int4(-1, 0, 0, 0), b4 = make_int4(0, 0, 0, 0);
         if(has) { idx = srcList[w]; const int4* ip = (const int4*)(items + idx); a = ip[0]; b4 = ip[1]; }
         const int item0 = a.x, rOff = a.y, seqLen = a.z, y0 = a.w, x0 = b4.x;
-        const int linRun = b4.w;                                          // linear steps ahead of the start level (FlatGraph::lin_out / lin_in, capped at 255)
+        const int linRun = (b4.z >> 8) & 255, pos0 = b4.w;                // unary steps ahead of the start node and its position on the node path (k_dp_items; FlatGraph::npf_steps / npb_steps, capped at 255)
         const int jmax = has ? (FWD ? seqLen - y0 : y0) : 0;              // read bases the call can consume (k_dp_items: <= C::MAXJ)
-        // the labels of every linear step ahead are staged (up to REACH): besides the cells that follow the read, the chains of sequence gaps that leave the
+        // the labels of every step of the path ahead are staged (up to REACH): besides the cells that follow the read, the chains of sequence gaps that leave the
         // best cells -- -6, then -2 per level down to the keep threshold of -16 (:949), for up to 40 iterations (:553) -- walk up to bases + 6 levels further
         const int reach = min(linRun, C::REACH);
         int myRc = 0;                                                     // the read base this lane's cells consume last: base j - 1 of the call
         if(has) {
-            for(int t = gl; t < reach; t += GW) S.ls[t] = linLabel[FWD ? x0 + t : x0 - 1 - t];
+            for(int t = gl; t < reach; t += GW) S.ls[t] = (FWD ? G.npf_label : G.npb_label)[pos0 + t];                // (positions pos0 .. pos0 + linRun - 1 exist: the steps are counted along consecutive positions)
             if(gl >= 1 && gl <= jmax) myRc = readBases[rOff + (FWD ? y0 + gl - 1 : y0 - gl)];
         }
         const u32 rcRep = (u32)myRc * 0x01010101u;
@@ -165,7 +167,7 @@ __device__ __forceinline__ void band_pass(const DG& G, const DB& B, const DpItem
                 }
                 if(keep) btAcc |= (u32)((dsel << 2) | (sbit ? 2 : 0) | (gbit ? 1 : 0)) << (4 * ((d - 1) & 7));
                 D2 = D1; D1 = survive ? Dv : DP_NEG; G1 = survive ? GGv : DP_NEG; S1 = survive ? SGv : DP_NEG;     // :1104-1105
-                if(survive && i >= reach) fail = (reach < linRun) ? 2 : 3;          // the next iteration would walk a level that is not staged / not linear
+                if(survive && i >= reach) fail = (reach < linRun) ? 2 : 3;          // the next iteration would walk a step that is not staged / not on the path
             }
             // back pointers of the last eight iterations into their word (every call of the wavefront, running or not: a call that stopped keeps its last bits until here)
             if((d & 7) == 0) { S.bt[(d - 1) >> 3][gl] = btAcc; btAcc = 0; }
@@ -198,7 +200,8 @@ __device__ __forceinline__ void band_pass(const DG& G, const DB& B, const DpItem
                 int pos = -1;
                 if(nTies == 1) pos = (tie0 << 6) | jmax;
                 if(__ballot(live && nTies > 1) != 0) {
-                    // the tie with exactly `sel` ties before it in the string order of "x/0" (std::set<std::string>, :493, :1431)
+                    // the tie with exactly `sel` ties before it in the string order of "x/z" (std::set<std::string>, :493, :1431).  The node rank z needs no look-up: the
+                    // sequence-complete cells of a call lie on distinct levels, and two keys with different x differ before the '/' of the shorter one is passed
                     u32 sd = rng_seed + (u32)item;
                     const int sel = glibc_rand_r(&sd) % (nTies > 0 ? nTies : 1);                                    // Utilities.cpp:922-927
                     const bool mine = nTies > 1 && gl < nTies && gl < BAND_TIES;
@@ -268,7 +271,9 @@ __device__ __forceinline__ void band_pass(const DG& G, const DB& B, const DpItem
                             if(kind == K_DIAG) { if(((lw >> 8) & 255u) == sc) par = 1; if(((lw >> 16) & 255u) == sc && par == 0) par = 2; if((lw >> 24) == sc && par == 0) par = 3; if((lw & 255u) == sc) par = 0; }
                             if(kind == K_GGAP) { oL[at] = -1; oE[at] = -1; oG[at] = '_'; oS[at] = sc; }
                             else {
-                                oL[at] = lvl; oE[at] = par == 0 ? linEid[lvl] : G.out_eid[G.out_off[G.level_off[lvl]] + par];
+                                // (the step's edges are those of the path node at position pos0 + i_ - 1: its out-edges forward, its in-edges backward, in CSR order)
+                                const int pp = pos0 + i_ - 1;
+                                oL[at] = lvl; oE[at] = par == 0 ? (FWD ? G.npf_eid : G.npb_eid)[pp] : (FWD ? G.out_eid[G.out_off[G.npf_node[pp]] + par] : G.in_eid[G.in_off[G.npb_node[pp]] + par]);
                                 oG[at] = (unsigned char)((lw >> (8 * par)) & 255u); oS[at] = (kind == K_DIAG) ? sc : (unsigned char)'_';
                             }
                         }
@@ -307,14 +312,14 @@ __device__ __forceinline__ void band_pass(const DG& G, const DB& B, const DpItem
 
 template <int GW>
 __global__ __launch_bounds__(64, BandCfg<GW>::WAVES) void k_dp_band(const DevGraph G, const DevBatch B, const DpItem* __restrict__ items, const u32 rng_seed,
-                                                                    const uint8_t* __restrict__ readBases, const u32* __restrict__ linLabel, const int* __restrict__ linEid)
+                                                                    const uint8_t* __restrict__ readBases)
 {
     typedef BandCfg<GW> C;
     __shared__ BandLds<C> SS[64 / GW];
     BandLds<C>& S = SS[lane_id() / GW];
     u64 accCalls = 0, accIters = 0, accCells = 0, accEdges = 0;          // first lane of every group: flushed once
-    band_pass<C, false>(G, B, items, rng_seed, readBases, linLabel, linEid, S, accCalls, accIters, accCells, accEdges);
-    band_pass<C, true>(G, B, items, rng_seed, readBases, linLabel, linEid, S, accCalls, accIters, accCells, accEdges);
+    band_pass<C, false>(G, B, items, rng_seed, readBases, S, accCalls, accIters, accCells, accEdges);
+    band_pass<C, true>(G, B, items, rng_seed, readBases, S, accCalls, accIters, accCells, accEdges);
     if((lane_id() & (GW - 1)) == 0 && accCalls) {
         atomicAdd(&B.counters[CNT_DP_CALLS], accCalls); atomicAdd(&B.counters[CNT_DP_ITERS], accIters);
         atomicAdd(&B.counters[CNT_DP_CELLS], accCells); atomicAdd(&B.counters[CNT_EDGES], accEdges);

@@ -1096,10 +1096,11 @@ int  hlala_abi_version(void);
 #define HLALA_DEBUG_WC_BAND_FETCH  48     /* [+0..5] items fetched by the 16 / 32 / 64-lane band kernels, left and right                               */
 #define HLALA_DEBUG_WC_BAND_WHY    62     /* [+2..5] band calls that failed over: past the staged levels, past the linear run, too many iterations, ties */
 #define HLALA_DEBUG_WC_BAND_TIED   68     /* band calls whose end cell was drawn among equal sequence-complete cells                                   */
+#define HLALA_DEBUG_WC_BAND_NODES  69     /* band calls listed through the path of their start node that the linear run of its level would not have listed */
 /* the first min(capacity, HLALA_DEBUG_WC_N) work counters of the batch's last stages */
 int  hlala_debug_work_counters(hlala_ctx* ctx, hlala_batch* batch, int* out, int capacity);
-/* the DP items of the batch's last extension stage ([2 * n_chains] records of 8 ints: item, read offset, read length, start offset, start level, start node, class,
- * linear run; item < 0: no call) and its retry / fail-over lists ([16 * n_chains] slots); either pointer may be NULL; capacities in bytes are checked */
+/* the DP items of the batch's last extension stage ([2 * n_chains] records of 8 ints: item, read offset, read length, start offset, start level, start node, class | steps
+ * of the band run << 8, start position on the node path; item < 0: no call) and its retry / fail-over lists ([16 * n_chains] slots); either pointer may be NULL; capacities in bytes are checked */
 int  hlala_debug_dp_items(hlala_ctx* ctx, hlala_batch* batch, int* items_out, long long items_capacity_bytes, int* retry_out, long long retry_capacity_bytes);
 /* counters[32] of a batch (stage statistics, timing builds), the phase-clock buffer of profile builds (8192 ints), device memory of a batch / its context (4 values) */
 int  hlala_debug_counters(hlala_ctx* ctx, hlala_batch* batch, unsigned long long* out32);
