@@ -346,6 +346,13 @@ class SeedBatch:
         self.lib.hlala_seed_batch_fill_counts(self.h, cnt)
         return tuple(int(x) for x in cnt)
 
+    def fill_wide_counts(self):
+        """(wide units the GPU filled, units beyond BAM_FILL_WIDE_MAX left to the host, the longest mate seen); all zero without SEEDS_GPU_FILL_WIDE"""
+        cnt = (C.c_int64 * 3)()
+        self.lib.hlala_seed_batch_fill_wide_counts.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        self.lib.hlala_seed_batch_fill_wide_counts(self.h, cnt)
+        return tuple(int(x) for x in cnt)
+
     def fill_ms(self):
         """device milliseconds of the window passes of SEEDS_GPU_FILL so far: (chain, cigar, names, bases, download)"""
         ms = (C.c_double * 5)()
@@ -381,6 +388,7 @@ SEEDS_VERIFY_CRC = 4      # HLALA_SEEDS_VERIFY_CRC (bam_open_seeds and Inflater.
 SEEDS_GPU_GROUP = 8       # HLALA_SEEDS_GPU_GROUP (with SEEDS_GPU_PARSE only): the records are grouped by read name on the GPU as well
 SEEDS_GPU_SORT = 16       # HLALA_SEEDS_GPU_SORT (with SEEDS_GPU_GROUP only): the units are put into read-name order on the GPU as well
 SEEDS_GPU_FILL = 32       # HLALA_SEEDS_GPU_FILL (with SEEDS_GPU_SORT only): the sample is laid out and its windows are filled on the GPU as well
+SEEDS_GPU_FILL_WIDE = 64  # HLALA_SEEDS_GPU_FILL_WIDE (with SEEDS_GPU_FILL only): units with a mate of 17 to BAM_FILL_WIDE_MAX alignments are filled on the GPU as well
 
 
 def bam_open_seeds(lib, path, intervals, long_read_mode=False, threads=0, flags=0) -> SeedBatch:
@@ -445,6 +453,7 @@ class BamFillStats(C.Structure):
 
 
 BAM_FILL_HOST, BAM_FILL_MAX_MATE = 0xFFFFFFFF, 16          # HLALA_BAM_FILL_HOST, HLALA_BAM_FILL_MAX_MATE
+BAM_FILL_WIDE_MAX = 4096                                   # HLALA_BAM_FILL_WIDE_MAX
 
 
 class BatchFillSrc(C.Structure):
@@ -518,6 +527,14 @@ class BamFill:
         if rc not in (0, -1):
             raise HlalaError(f"hlala_bam_fill_window failed ({rc}): {self.last_error()}")
         return rc, arrs, st
+
+    def wide_stats(self):
+        """hlala_bam_fill_wide_stats: (wide units, wide reads, the longest mate, device microseconds of the two wide kernels); zeros for a state of bam_fill_create"""
+        out = (C.c_int64 * 4)()
+        self.lib.hlala_bam_fill_wide_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        if self.lib.hlala_bam_fill_wide_stats(self.h, out) != 0:
+            raise HlalaError("hlala_bam_fill_wide_stats failed")
+        return tuple(int(x) for x in out)
 
     def last_error(self):
         return self.lib.hlala_bam_fill_last_error(self.h).decode(errors="replace")
@@ -664,6 +681,16 @@ class Inflater:
                                             C.byref(h), C.byref(st))
         if rc not in (0, -1):
             raise HlalaError(f"hlala_bam_fill_create failed ({rc}): {self.last_error()}")
+        return rc, (BamFill(self.lib, h, off, long_read_mode, packed) if rc == 0 and h.value else None), off, st
+
+    def bam_fill_create_wide(self, fill_in, n_units, long_read_mode=False, packed=False, max_mate=BAM_FILL_WIDE_MAX):
+        """hlala_bam_fill_create_wide: bam_fill_create with mates of up to max_mate alignments (in (BAM_FILL_MAX_MATE, BAM_FILL_WIDE_MAX]) laid out on the device as well"""
+        off = bam_fill_offsets(n_units, long_read_mode); st = BamFillStats(); h = C.c_void_p()
+        self.lib.hlala_bam_fill_create_wide.argtypes = [C.c_void_p, C.POINTER(BamFillIn), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(BamFillStats)]
+        rc = self.lib.hlala_bam_fill_create_wide(self.h, C.byref(fill_in), int(max_mate), off["read_off"].ctypes.data, off["chain_off"].ctypes.data, off["cigar_count"].ctypes.data,
+                                                 off["name_off"].ctypes.data, C.byref(h), C.byref(st))
+        if rc not in (0, -1):
+            raise HlalaError(f"hlala_bam_fill_create_wide failed ({rc}): {self.last_error()}")
         return rc, (BamFill(self.lib, h, off, long_read_mode, packed) if rc == 0 and h.value else None), off, st
 
     def last_error(self):
@@ -1067,6 +1094,7 @@ EXPORTED_SYMBOLS = [
     "hlala_bam_name_order", "hlala_seed_batch_sort_counts",
     "hlala_bam_fill_create", "hlala_bam_fill_window", "hlala_bam_fill_last_error", "hlala_bam_fill_destroy", "hlala_seed_batch_fill_counts", "hlala_seed_batch_fill_ms",
     "hlala_batch_create_from_fill", "hlala_debug_batch_inputs",
+    "hlala_bam_fill_create_wide", "hlala_bam_fill_wide_stats", "hlala_seed_batch_fill_wide_counts",
     "hlala_locus_cluster_kmers", "hlala_type_locus", "hlala_kmer_presence", "hlala_kmer_keep_reads", "hlala_kmer_presence_kept", "hlala_kmer_forget_reads", "hlala_unit_alignment_stats", "hlala_typer_write_summary", "hlala_typer_begin_output", "hlala_locus_write_files", "hlala_locus_write_pairs_file", "hlala_typer_end_output",
 ]
 

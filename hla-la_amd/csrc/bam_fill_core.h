@@ -64,8 +64,9 @@ HLALA_HD uint32_t fil_word(const uint8_t* bytes, uint64_t n_bytes, uint64_t p)
 
 // The arguments of hlala_bam_fill_create / hlala_host_bam_fill_model, checked before anything runs.  Returns null or what is wrong.  Reads the descriptors and the
 // unit arrays only, never `bytes`.
-inline const char* fil_check_args(const hlala_bam_fill_in* in, const int64_t* read_off, const int64_t* chain_off, const int64_t* cigar_count, const int64_t* name_off,
-                                  const hlala_bam_fill_stats* stats)
+// (fil_check_args_cap: the same checks with max_mate alignments on a mate allowed and `beyond` said of a mate with more -- bam_fill_wide_core.h)
+inline const char* fil_check_args_cap(const hlala_bam_fill_in* in, const int64_t* read_off, const int64_t* chain_off, const int64_t* cigar_count, const int64_t* name_off,
+                                      const hlala_bam_fill_stats* stats, uint32_t max_mate, const char* beyond)
 {
     if(!in || !stats) return "null argument";
     if(in->n < 0 || in->n_units < 0 || in->n_host_units < 0) return "negative count";
@@ -95,7 +96,7 @@ inline const char* fil_check_args(const hlala_bam_fill_in* in, const int64_t* re
             if(x.l_seq < 0) return "a record with a negative l_seq";
             if(x.rec_off > in->n_bytes || in->n_bytes - x.rec_off < fil_extent(x)) return "a record that lies beyond the byte buffer";
             mates[x.which]++; if(x.flags & 2) prim[x.which] = true;
-            if(mates[x.which] > FIL_MAX_MATE) return "a filled unit with more than 16 alignments on one mate";
+            if(mates[x.which] > max_mate) return beyond;
         }
         for(int m = 0; m < nm; m++) if(!prim[m]) return "a filled unit without a primary on a required mate";
         nChains += count;
@@ -103,6 +104,11 @@ inline const char* fil_check_args(const hlala_bam_fill_in* in, const int64_t* re
     }
     if(nHost != in->n_host_units) return "fewer host units than n_host_units";
     return nullptr;
+}
+inline const char* fil_check_args(const hlala_bam_fill_in* in, const int64_t* read_off, const int64_t* chain_off, const int64_t* cigar_count, const int64_t* name_off,
+                                  const hlala_bam_fill_stats* stats)
+{
+    return fil_check_args_cap(in, read_off, chain_off, cigar_count, name_off, stats, FIL_MAX_MATE, "a filled unit with more than 16 alignments on one mate");
 }
 
 }  // namespace hlala_bamfill

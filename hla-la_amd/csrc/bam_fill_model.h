@@ -2,13 +2,19 @@
 // chains' sources, then per window the chain scalars, CIGARs, names, bases and qualities -- a loop where the device has a grid.  What hlala_host_bam_fill_model
 // (host_check.cpp) exports, what the CPU suite holds against a plain-Python statement of the rule, what the device is held against bit for bit -- and, built with
 // sanitizers into tools/bam_fill_check.cpp, what shows the argument check refusing malformed inputs before a record byte is read.
+//
+// The wide layout (bam_fill_wide_core.h; hlala_host_bam_fill_model_wide): fill_model_create_wide orders both mates of a wide unit with fil_sort_wide, as k_fil_wide_rank
+// does, and every other unit as above; the window passes follow chain_src and are the same.  fil_adversary makes the scores that drive std::sort into its heap sort.
 #ifndef HLALA_BAM_FILL_MODEL_H_
 #define HLALA_BAM_FILL_MODEL_H_
+#include <algorithm>
 #include <chrono>
 #include <cstring>
+#include <numeric>
 #include <vector>
 
 #include "bam_fill_core.h"
+#include "bam_fill_wide_core.h"
 
 namespace hlala_bamfill {
 
@@ -32,10 +38,49 @@ inline uint32_t fil_rank_serial(const hlala_bam_rec* U, uint32_t count, int mate
     return n;
 }
 
-inline int fill_model_create(const hlala_bam_fill_in* in, int64_t* read_off, int64_t* chain_off, int64_t* cigar_count, int64_t* name_off, FillLayout* L, hlala_bam_fill_stats* stats,
-                             const char** why)
+// what a wide mate is sorted in: scores and places in file order, the stack of fil_sort_wide
+struct WideScratch { std::vector<int32_t> score; std::vector<uint16_t> place; uint32_t stack[FIL_WIDE_STACK_WORDS]; };
+// the mate's records of a wide unit in the order sortChainsInSeeds leaves, as k_fil_wide_rank finds it.  order[rank] = place in the unit; *heaps: heap sorts entered
+inline uint32_t fil_order_wide(const hlala_bam_rec* U, uint32_t count, int mate, WideScratch& X, std::vector<uint32_t>& order, uint32_t* heaps)
 {
-    const char* bad = fil_check_args(in, read_off, chain_off, cigar_count, name_off, stats);
+    X.score.clear(); X.place.clear();
+    for(uint32_t k = 0; k < count && X.score.size() < FIL_WIDE_MAX; k++) if(U[k].which == mate) { X.score.push_back(U[k].as); X.place.push_back((uint16_t)k); }
+    const uint32_t n = (uint32_t)X.score.size();
+    const uint32_t h = fil_sort_wide(X.score.data(), X.place.data(), n, X.stack);
+    if(heaps) *heaps = h;
+    order.resize(std::max<size_t>(order.size(), n));
+    for(uint32_t k = 0; k < n; k++) order[k] = X.place[k];
+    return n;
+}
+inline bool fil_unit_is_wide(const hlala_bam_rec* U, uint32_t count, uint32_t* longest)
+{
+    uint32_t m[2] = {0, 0};
+    for(uint32_t k = 0; k < count; k++) m[U[k].which & 1]++;
+    if(longest) *longest = std::max(m[0], m[1]);
+    return fil_is_wide(count, m[0], m[1]);
+}
+// McIlroy's adversary ("A Killer Adversary for Quicksort") run against std::sort itself on the places 0 .. n - 1: every element is undecided until a comparison needs
+// its value, and the one the sort seems to use as its pivot is given the next small value.  What is left in score[] makes std::sort's comparisons come out the same
+// way again: for n >= 64 they spend its depth limit and enter the heap sort.
+inline void fil_adversary(uint32_t n, int32_t* score)
+{
+    const int32_t gas = (int32_t)n;
+    std::vector<int32_t> val(n, gas); std::vector<uint32_t> idx(n); std::iota(idx.begin(), idx.end(), 0u);
+    int32_t solid = 0; uint32_t candidate = 0;
+    std::sort(idx.begin(), idx.end(), [&](uint32_t x, uint32_t y) {
+        if(val[x] == gas && val[y] == gas) val[x == candidate ? x : y] = solid++;
+        if(val[x] == gas) candidate = x; else if(val[y] == gas) candidate = y;
+        return val[x] < val[y];
+    });
+    for(uint32_t i = 0; i < n; i++) score[i] = val[i];
+}
+
+// max_mate 0: the layout of hlala_bam_fill_create; otherwise that of hlala_bam_fill_create_wide.  wide[4] (may be null): wide units, wide reads, the longest mate, 0
+inline int fill_model_create_any(const hlala_bam_fill_in* in, int32_t max_mate, int64_t* read_off, int64_t* chain_off, int64_t* cigar_count, int64_t* name_off, FillLayout* L,
+                                 hlala_bam_fill_stats* stats, int64_t* wide, const char** why)
+{
+    const char* bad = max_mate ? fil_check_args_wide(in, max_mate, read_off, chain_off, cigar_count, name_off, stats) : fil_check_args(in, read_off, chain_off, cigar_count, name_off, stats);
+    if(wide) wide[0] = wide[1] = wide[2] = wide[3] = 0;
     if(why) *why = bad;
     if(bad) return HLALA_E_ARG;
     memset(stats, 0, sizeof(*stats));
@@ -46,7 +91,8 @@ inline int fill_model_create(const hlala_bam_fill_in* in, int64_t* read_off, int
     // ---- rank + sizes, the sizes of host units
     read_off[0] = chain_off[0] = cigar_count[0] = name_off[0] = 0;
     int64_t host = 0;
-    uint32_t order[FIL_MAX_MATE];
+    std::vector<uint32_t> order(FIL_MAX_MATE); WideScratch X;
+    auto ordered = [&](const hlala_bam_rec* U, uint32_t count, int m, bool isWide) { return isWide ? fil_order_wide(U, count, m, X, order, nullptr) : fil_rank_serial(U, count, m, order.data()); };
     for(size_t u = 0; u < nU; u++) {
         if(in->unit_first[u] == FIL_HOST) {
             const int64_t* hs = in->host_sizes + host * (3 * nm + 1); host++;
@@ -56,9 +102,12 @@ inline int fill_model_create(const hlala_bam_fill_in* in, int64_t* read_off, int
         }
         const hlala_bam_rec* U = in->recs + in->unit_first[u]; const uint32_t count = in->unit_count[u];
         name_off[u + 1] = (int64_t)U[0].nameLen + 1;
+        uint32_t longest = 0;
+        const bool isWide = max_mate != 0 && fil_unit_is_wide(U, count, &longest);
+        if(isWide && wide) { wide[0]++; wide[1] += nm; wide[2] = std::max<int64_t>(wide[2], longest); }
         for(int m = 0; m < nm; m++) {
             const size_t r = u * (size_t)nm + (size_t)m;
-            const uint32_t n = fil_rank_serial(U, count, m, order);
+            const uint32_t n = ordered(U, count, m, isWide);
             int64_t cg = 0, ls = 0; bool found = false;
             for(uint32_t k = 0; k < n; k++) { cg += U[order[k]].n_cigar; if(!found && (U[order[k]].flags & 2)) { found = true; ls = U[order[k]].l_seq; } }
             read_off[r + 1] = ls; chain_off[r + 1] = n; cigar_count[r + 1] = cg;
@@ -73,9 +122,10 @@ inline int fill_model_create(const hlala_bam_fill_in* in, int64_t* read_off, int
     for(size_t u = 0; u < nU; u++) {
         if(in->unit_first[u] == FIL_HOST) continue;
         const hlala_bam_rec* U = in->recs + in->unit_first[u]; const uint32_t count = in->unit_count[u];
+        const bool isWide = max_mate != 0 && fil_unit_is_wide(U, count, nullptr);
         for(int m = 0; m < nm; m++) {
             const size_t r = u * (size_t)nm + (size_t)m;
-            const uint32_t n = fil_rank_serial(U, count, m, order);
+            const uint32_t n = ordered(U, count, m, isWide);
             int64_t cg = cigar_count[r]; bool found = false;
             for(uint32_t k = 0; k < n; k++) {
                 const size_t c = (size_t)chain_off[r] + k;
@@ -87,6 +137,18 @@ inline int fill_model_create(const hlala_bam_fill_in* in, int64_t* read_off, int
     stats->n_units = in->n_units; stats->n_host_units = in->n_host_units; stats->n_reads = (int64_t)nR; stats->n_chains = (int64_t)nC; stats->n_cigar = cigar_count[nR];
     stats->n_bases = read_off[nR]; stats->n_name_bytes = name_off[nU];
     return HLALA_OK;
+}
+
+inline int fill_model_create(const hlala_bam_fill_in* in, int64_t* read_off, int64_t* chain_off, int64_t* cigar_count, int64_t* name_off, FillLayout* L, hlala_bam_fill_stats* stats,
+                             const char** why)
+{
+    return fill_model_create_any(in, 0, read_off, chain_off, cigar_count, name_off, L, stats, nullptr, why);
+}
+inline int fill_model_create_wide(const hlala_bam_fill_in* in, int32_t max_mate, int64_t* read_off, int64_t* chain_off, int64_t* cigar_count, int64_t* name_off, FillLayout* L,
+                                  hlala_bam_fill_stats* stats, int64_t* wide, const char** why)
+{
+    if(max_mate == 0) { if(why) *why = "max_mate outside (16, 4096]"; return HLALA_E_ARG; }
+    return fill_model_create_any(in, max_mate, read_off, chain_off, cigar_count, name_off, L, stats, wide, why);
 }
 
 // the slices of units [u0, u0 + n); the offsets are those fill_model_create wrote

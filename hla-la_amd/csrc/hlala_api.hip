@@ -2602,11 +2602,13 @@ static int bam_group_hook(void* inflater, int64_t n, int32_t long_read_mode, uin
 static int bam_sort_hook(void* inflater, int64_t m, uint32_t* order, hlala_bam_name_order_stats* stats, bool* available, std::string* err);      // (behind hlala_bam_name_order, below)
 static int bam_fill_hook(void* inflater, const hlala_bam_fill_in* in, int64_t* read_off, int64_t* chain_off, int64_t* cigar_count, int64_t* name_off, hlala_host::bam_fill_handle* handle,
                          hlala_bam_fill_stats* stats, bool* available, std::string* err);      // (behind hlala_bam_fill_create, below)
+static int bam_fill_wide_hook(void* inflater, const hlala_bam_fill_in* in, int32_t max_mate, const uint32_t* wide_units, int64_t n_wide, int64_t longest, int64_t* read_off, int64_t* chain_off,
+                              int64_t* cigar_count, int64_t* name_off, hlala_host::bam_fill_handle* handle, hlala_bam_fill_stats* stats, bool* available, std::string* err);
 extern "C" int hlala_bam_extract_seeds_gpu(hlala_inflater* f, const char* path, int32_t n_intervals, const hlala_bam_interval* iv, int32_t long_read_mode, int32_t n_threads, int32_t flags,
                                            hlala_seed_batch** out)
 {
     static std::once_flag hookOnce;                  // (samples may decode on several threads)
-    std::call_once(hookOnce, []() { hlala_host::g_bam_inflate_hook = bam_inflate_hook; hlala_host::g_bam_inflate_crc_hook = bam_inflate_crc_hook; hlala_host::g_bam_scan_hook = bam_scan_hook; hlala_host::g_bam_group_hook = bam_group_hook; hlala_host::g_bam_sort_hook = bam_sort_hook; hlala_host::g_bam_fill_hook = bam_fill_hook; });
+    std::call_once(hookOnce, []() { hlala_host::g_bam_inflate_hook = bam_inflate_hook; hlala_host::g_bam_inflate_crc_hook = bam_inflate_crc_hook; hlala_host::g_bam_scan_hook = bam_scan_hook; hlala_host::g_bam_group_hook = bam_group_hook; hlala_host::g_bam_sort_hook = bam_sort_hook; hlala_host::g_bam_fill_hook = bam_fill_hook; hlala_host::g_bam_fill_wide_hook = bam_fill_wide_hook; });
     return hlala_host::bam_extract_seeds_impl(path, n_intervals, iv, long_read_mode, n_threads, flags, true, f, out);
 }
 
@@ -3175,7 +3177,9 @@ static int bam_sort_hook(void* inflater, int64_t m, uint32_t* order, hlala_bam_n
 
 // ---- the layout and the fill on the device (include/hlala_gpu.h; kernel_bamfill.hip).  A handle of its own: the sample's descriptors, bytes, permutation and unit
 // arrays, what the layout passes leave (offsets, chain sources, primaries), a stream, events, one device block and one page-locked block for a window's slices.
-enum { FIL_RECS, FIL_BYTES, FIL_PERM, FIL_UFIRST, FIL_UCOUNT, FIL_SIZES, FIL_OFFS, FIL_CHAINSRC, FIL_CHAINCIG, FIL_PRIMARY, FIL_WIN, FIL_NBUF };
+enum { FIL_RECS, FIL_BYTES, FIL_PERM, FIL_UFIRST, FIL_UCOUNT, FIL_SIZES, FIL_OFFS, FIL_CHAINSRC, FIL_CHAINCIG, FIL_PRIMARY, FIL_WIN, FIL_WIDE, FIL_NBUF };      // FIL_WIDE: only for a sample with wide units
+// the wide units of a sample as the host found them (hlala_bam_fill_create_wide from the descriptors, the decoder from its own records); null: the narrow layout
+struct FillWideIn { int32_t maxMate; const u32* units; size_t n; int64_t longest; };
 constexpr int FIL_NEV = 8;
 struct hlala_bam_fill {
     int device = 0; hipStream_t st = nullptr; hipEvent_t ev[FIL_NEV]{};
@@ -3183,6 +3187,7 @@ struct hlala_bam_fill {
     FilSample S{}; int packed = 0; u64 nReads = 0, nChains = 0;
     uint8_t* hStage = nullptr; size_t stageCap = 0; int64_t* hBounds = nullptr;
     std::vector<u32> hostUnit;       // the host units, ascending (hlala_batch_create_from_fill places their ranges)
+    hipEvent_t wev[4]{}; int64_t wideStats[4] = {0, 0, 0, 0};      // wide units, wide reads, the longest mate, device microseconds of k_fil_wide_rank + k_fil_wide_src
     std::string err;
     int64_t* off(int which) const { return (int64_t*)buf[FIL_OFFS].p + (size_t)which * (nReads + 1); }      // 0 read_off, 1 chain_off, 2 cigar_count, 3 name_off
 };
@@ -3193,6 +3198,7 @@ static void fill_free(hlala_bam_fill* H)
     if(H->st) (void)hipStreamSynchronize(H->st);
     for(ScanBuf& b : H->buf) if(b.p) (void)hipFree(b.p);
     for(hipEvent_t e : H->ev) if(e) (void)hipEventDestroy(e);
+    for(hipEvent_t e : H->wev) if(e) (void)hipEventDestroy(e);
     if(H->hStage) (void)hipHostFree(H->hStage);
     if(H->hBounds) (void)hipHostFree(H->hBounds);
     if(H->st) (void)hipStreamDestroy(H->st);
@@ -3210,7 +3216,9 @@ static hipError_t fill_alloc(hlala_bam_fill* H, int which, size_t bytes)
 }
 // The layout passes.  H holds FIL_RECS / FIL_BYTES (/ FIL_PERM) and S.n, S.nBytes; the unit arrays and the host units' sizes are host memory and are uploaded here.
 // *noMemory: a device allocation failed, nothing of the sample is laid out (the decoder's hook hands the sample back; the entry point fails).
-static int fill_layout(hlala_bam_fill* H, const hlala_bam_fill_in* in, int64_t* read_off, int64_t* chain_off, int64_t* cigar_count, int64_t* name_off, hlala_bam_fill_stats* stats, bool* noMemory)
+// wide (may be null): the sample's wide units, ascending; the scratch arrays, the bitmap and two more kernels exist only where it lists one.
+static int fill_layout(hlala_bam_fill* H, const hlala_bam_fill_in* in, int64_t* read_off, int64_t* chain_off, int64_t* cigar_count, int64_t* name_off, hlala_bam_fill_stats* stats, bool* noMemory,
+                       const FillWideIn* wide = nullptr)
 {
     using namespace hlala_bamfill;
     *noMemory = false;
@@ -3224,6 +3232,25 @@ static int fill_layout(hlala_bam_fill* H, const hlala_bam_fill_in* in, int64_t* 
     for(size_t u = 0; u < nU; u++) if(in->unit_first[u] == FIL_HOST) hostUnit.push_back((u32)u);
     if(hostUnit.size() != nHost) { H->err = "BAM fill: the host units marked are not n_host_units"; return HLALA_E_ARG; }
     H->hostUnit = hostUnit;
+    // ---- the wide units: list, slots per wide read (unit_count each), primaries, the bitmap, then the two scratch arrays -- one block of 32-bit words
+    const size_t nWide = wide ? wide->n : 0, nWR = nWide * nm;
+    std::vector<u32> wideWords; size_t wUnitAt = 0, wOffAt = 0, wPrimAt = 0, wMapAt = 0, wDescAt = 0, wCigAt = 0; u64 nSlots = 0;
+    if(nWide) {
+        const size_t mapWords = (nU + 31) / 32;
+        wUnitAt = 0; wOffAt = nWide; wPrimAt = wOffAt + nWR + 1; wMapAt = wPrimAt + nWR; wDescAt = wMapAt + mapWords;
+        wideWords.assign(wDescAt, 0u);
+        for(size_t w = 0; w < nWide; w++) {
+            const u32 u = wide->units[w];
+            if(u >= nU || in->unit_first[u] == FIL_HOST || (w && u <= wide->units[w - 1])) { H->err = "BAM fill: the wide units are not an ascending list of filled units"; return HLALA_E_ARG; }
+            wideWords[wUnitAt + w] = u; wideWords[wMapAt + (u >> 5)] |= 1u << (u & 31u);
+            for(u32 m = 0; m < nm; m++) { wideWords[wOffAt + w * nm + m] = (u32)nSlots; nSlots += in->unit_count[u]; }
+        }
+        if(nSlots >= ((u64)1 << 32)) { H->err = "BAM fill: 2^32 or more alignments in wide units"; return HLALA_E_ARG; }
+        wideWords[wOffAt + nWR] = (u32)nSlots; wCigAt = wDescAt + (size_t)nSlots;
+        if((e = fill_alloc(H, FIL_WIDE, (wCigAt + (size_t)nSlots) * 4)) != hipSuccess) { (void)hipGetLastError(); *noMemory = true; return HLALA_OK; }
+        for(hipEvent_t& ev : H->wev) if(!ev && (e = hipEventCreate(&ev)) != hipSuccess) { ev = nullptr; (void)hipGetLastError(); *noMemory = true; return HLALA_OK; }
+    }
+    FilWide Wd{};
     size_t cubBytes = 0;
     if((e = hipcub::DeviceScan::ExclusiveSum(nullptr, cubBytes, (int64_t*)nullptr, (int64_t*)nullptr, nR + 1, st)) != hipSuccess) return failed("hipcub::DeviceScan::ExclusiveSum");
     // FIL_SIZES: the four size arrays [nR + 1] each (name sizes use nU + 1 of theirs); behind them the host units' numbers and sizes, then the scan's scratch and the bad bits
@@ -3233,13 +3260,19 @@ static int fill_layout(hlala_bam_fill* H, const hlala_bam_fill_in* in, int64_t* 
     int64_t* dSize = (int64_t*)H->buf[FIL_SIZES].p;
     int64_t* dHostSizes = dSize + 4 * (nR + 1); u32* dHostUnit = (u32*)(dHostSizes + nHost * perHost); u32* dBad = dHostUnit + nHost + (nHost & 1);
     void* dCub = (void*)(((uintptr_t)(dBad + 2) + 15) & ~(uintptr_t)15);
-    H->S.unitFirst = (const u32*)H->buf[FIL_UFIRST].p; H->S.unitCount = (const u32*)H->buf[FIL_UCOUNT].p; H->S.nUnits = (u32)nU; H->S.nm = nm;
+    H->S.unitFirst = (const u32*)H->buf[FIL_UFIRST].p; H->S.unitCount = (const u32*)H->buf[FIL_UCOUNT].p; H->S.nUnits = (u32)nU; H->S.nm = nm; H->S.wide = nullptr;
+    if(nWide) {
+        u32* dW = (u32*)H->buf[FIL_WIDE].p;
+        H->S.wide = dW + wMapAt;
+        Wd.unit = dW + wUnitAt; Wd.off = dW + wOffAt; Wd.nUnits = (u32)nWide; Wd.maxMate = (u32)wide->maxMate; Wd.desc = dW + wDescAt; Wd.cig = dW + wCigAt; Wd.prim = dW + wPrimAt;
+    }
     auto ms = [&](int a, int b) { float t = 0; return hipEventElapsedTime(&t, H->ev[a], H->ev[b]) == hipSuccess ? (double)t : 0.0; };
     e = hipEventRecord(H->ev[0], st);
     if(e == hipSuccess) e = hipMemcpyAsync(H->buf[FIL_UFIRST].p, in->unit_first, nU * 4, hipMemcpyHostToDevice, st);
     if(e == hipSuccess) e = hipMemcpyAsync(H->buf[FIL_UCOUNT].p, in->unit_count, nU * 4, hipMemcpyHostToDevice, st);
     if(e == hipSuccess && nHost) e = hipMemcpyAsync(dHostSizes, in->host_sizes, nHost * perHost * 8, hipMemcpyHostToDevice, st);
     if(e == hipSuccess && nHost) e = hipMemcpyAsync(dHostUnit, hostUnit.data(), nHost * 4, hipMemcpyHostToDevice, st);
+    if(e == hipSuccess && nWide) e = hipMemcpyAsync(H->buf[FIL_WIDE].p, wideWords.data(), wideWords.size() * 4, hipMemcpyHostToDevice, st);      // (the stream is synchronised before wideWords goes)
     if(e == hipSuccess) e = hipMemsetAsync(dSize, 0, sizesBytes, st);
     if(e == hipSuccess) e = hipMemsetAsync(dBad, 0, 8, st);
     if(e == hipSuccess) e = hipMemsetAsync(H->buf[FIL_PRIMARY].p, 0, nR * 4, st);
@@ -3247,6 +3280,11 @@ static int fill_layout(hlala_bam_fill* H, const hlala_bam_fill_in* in, int64_t* 
     const u32 rankBlocks = (u32)((nR * 16 + 255) / 256);
     int64_t *sL = dSize, *sC = dSize + (nR + 1), *sG = dSize + 2 * (nR + 1), *sN = dSize + 3 * (nR + 1);
     if(e == hipSuccess) { hipLaunchKernelGGL(k_fil_rank, dim3(rankBlocks), dim3(256), 0, st, H->S, (u64)nR, sL, sC, sG, sN, dBad); e = hipGetLastError(); }
+    if(e == hipSuccess && nWide) {                       // (inside ms_rank, and timed on its own)
+        e = hipEventRecord(H->wev[0], st);
+        if(e == hipSuccess) { hipLaunchKernelGGL(k_fil_wide_rank, dim3((u32)nWR), dim3(64), 0, st, H->S, Wd, sL, sC, sG, sN, dBad); e = hipGetLastError(); }
+        if(e == hipSuccess) e = hipEventRecord(H->wev[1], st);
+    }
     if(e == hipSuccess) e = hipEventRecord(H->ev[2], st);
     if(e == hipSuccess && nHost) { hipLaunchKernelGGL(k_fil_host, dim3((u32)((nHost + 63) / 64)), dim3(64), 0, st, (u32)nHost, (u32)nU, nm, (const u32*)dHostUnit, (const int64_t*)dHostSizes, sL, sC, sG, sN); e = hipGetLastError(); }
     if(e == hipSuccess) e = hipEventRecord(H->ev[3], st);
@@ -3256,9 +3294,9 @@ static int fill_layout(hlala_bam_fill* H, const hlala_bam_fill_in* in, int64_t* 
     if(e == hipSuccess) e = hipMemcpyAsync(hBad, dBad, 8, hipMemcpyDeviceToHost, st);
     for(int w = 0; w < 4 && e == hipSuccess; w++) e = hipMemcpyAsync(&totals[w], H->off(w) + (w == 3 ? nU : nR), 8, hipMemcpyDeviceToHost, st);
     if(e == hipSuccess) e = hipStreamSynchronize(st);
-    if(e != hipSuccess) return failed("upload / k_fil_rank / k_fil_host / the scans");
+    if(e != hipSuccess) return failed("upload / k_fil_rank / k_fil_wide_rank / k_fil_host / the scans");
     if(hBad[0]) {
-        H->err = std::string("BAM fill: ") + ((hBad[0] & FIL_BAD_MATE) ? "a filled unit with more than 16 alignments on one mate" : (hBad[0] & FIL_BAD_PRIMARY) ? "a filled unit without a primary on a required mate"
+        H->err = std::string("BAM fill: ") + ((hBad[0] & FIL_BAD_MATE) ? (wide ? "a filled unit with more alignments on one mate than max_mate" : "a filled unit with more than 16 alignments on one mate") : (hBad[0] & FIL_BAD_PRIMARY) ? "a filled unit without a primary on a required mate"
                                                                        : "a unit whose records lie beyond the descriptors");
         return HLALA_E_ARG;
     }
@@ -3271,6 +3309,12 @@ static int fill_layout(hlala_bam_fill* H, const hlala_bam_fill_in* in, int64_t* 
     if(e == hipSuccess) e = hipEventRecord(H->ev[5], st);
     if(e == hipSuccess) { hipLaunchKernelGGL(k_fil_src, dim3(rankBlocks), dim3(256), 0, st, H->S, (u64)nR, (const int64_t*)H->off(1), (const int64_t*)H->off(2), (u64)nC, (u32*)H->buf[FIL_CHAINSRC].p,
                                              (int64_t*)H->buf[FIL_CHAINCIG].p, (int32_t*)H->buf[FIL_PRIMARY].p); e = hipGetLastError(); }
+    if(e == hipSuccess && nWide) {                       // (inside ms_src, and timed on its own)
+        e = hipEventRecord(H->wev[2], st);
+        if(e == hipSuccess) { hipLaunchKernelGGL(k_fil_wide_src, dim3((u32)((nSlots + 255) / 256)), dim3(256), 0, st, H->S, Wd, (u32)nWR, (u32)nSlots, (const int64_t*)H->off(1), (const int64_t*)H->off(2), (u64)nC,
+                                                 (u32*)H->buf[FIL_CHAINSRC].p, (int64_t*)H->buf[FIL_CHAINCIG].p, (int32_t*)H->buf[FIL_PRIMARY].p); e = hipGetLastError(); }
+        if(e == hipSuccess) e = hipEventRecord(H->wev[3], st);
+    }
     if(e == hipSuccess) e = hipEventRecord(H->ev[6], st);
     if(e == hipSuccess) e = hipMemcpyAsync(read_off, H->off(0), (nR + 1) * 8, hipMemcpyDeviceToHost, st);
     if(e == hipSuccess) e = hipMemcpyAsync(chain_off, H->off(1), (nR + 1) * 8, hipMemcpyDeviceToHost, st);
@@ -3278,7 +3322,14 @@ static int fill_layout(hlala_bam_fill* H, const hlala_bam_fill_in* in, int64_t* 
     if(e == hipSuccess) e = hipMemcpyAsync(name_off, H->off(3), (nU + 1) * 8, hipMemcpyDeviceToHost, st);
     if(e == hipSuccess) e = hipEventRecord(H->ev[7], st);
     if(e == hipSuccess) e = hipStreamSynchronize(st);
-    if(e != hipSuccess) return failed("k_fil_src / download");
+    if(e != hipSuccess) return failed("k_fil_src / k_fil_wide_src / download");
+    if(nWide) {
+        float a = 0, b = 0;
+        if(hipEventElapsedTime(&a, H->wev[0], H->wev[1]) != hipSuccess) a = 0;
+        if(hipEventElapsedTime(&b, H->wev[2], H->wev[3]) != hipSuccess) b = 0;
+        H->wideStats[0] = (int64_t)nWide; H->wideStats[1] = (int64_t)nWR; H->wideStats[2] = wide->longest; H->wideStats[3] = (int64_t)(((double)a + (double)b) * 1e3 + 0.5);
+        stats->bytes_h2d += (int64_t)(wideWords.size() * 4);
+    }
     stats->n_units = (int64_t)nU; stats->n_host_units = (int64_t)nHost; stats->n_reads = (int64_t)nR; stats->n_chains = totals[1]; stats->n_cigar = totals[2]; stats->n_bases = totals[0]; stats->n_name_bytes = totals[3];
     stats->ms_h2d += ms(0, 1); stats->ms_rank = ms(1, 2); stats->ms_host = ms(2, 3); stats->ms_scan = ms(3, 4); stats->ms_src = ms(5, 6); stats->ms_d2h = ms(6, 7);
     stats->bytes_h2d += (int64_t)(nU * 8 + nHost * (perHost * 8 + 4)); stats->bytes_d2h += (int64_t)((3 * (nR + 1) + nU + 1) * 8);
@@ -3380,14 +3431,26 @@ static int fill_window(hlala_bam_fill* H, int64_t first_unit, int64_t n_units, c
     stats->ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tWall).count();
     return HLALA_OK;
 }
-extern "C" int hlala_bam_fill_create(hlala_inflater* f, const hlala_bam_fill_in* in, int64_t* read_off, int64_t* chain_off, int64_t* cigar_count, int64_t* name_off, hlala_bam_fill** out,
-                                     hlala_bam_fill_stats* stats)
+// max_mate 0: hlala_bam_fill_create; otherwise hlala_bam_fill_create_wide, which looks for the wide units in the descriptors it has just checked
+static int fill_create(const char* fn, hlala_inflater* f, const hlala_bam_fill_in* in, int32_t max_mate, bool isWide, int64_t* read_off, int64_t* chain_off, int64_t* cigar_count, int64_t* name_off,
+                       hlala_bam_fill** out, hlala_bam_fill_stats* stats)
 {
     if(!f) { int ndev = 0; if(hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return HLALA_E_DEVICE; } return HLALA_E_ARG; }
     f->err.clear();
     if(out) *out = nullptr;
-    const char* bad = out ? hlala_bamfill::fil_check_args(in, read_off, chain_off, cigar_count, name_off, stats) : "null argument";
-    if(bad) { f->err = std::string("hlala_bam_fill_create: ") + bad; return HLALA_E_ARG; }
+    const char* bad = !out ? "null argument" : isWide ? hlala_bamfill::fil_check_args_wide(in, max_mate, read_off, chain_off, cigar_count, name_off, stats)
+                                                      : hlala_bamfill::fil_check_args(in, read_off, chain_off, cigar_count, name_off, stats);
+    if(bad) { f->err = std::string(fn) + ": " + bad; return HLALA_E_ARG; }
+    std::vector<u32> wideUnits; FillWideIn wide{max_mate, nullptr, 0, 0};
+    if(isWide) {
+        for(int64_t u = 0; u < in->n_units; u++) {
+            if(in->unit_first[u] == hlala_bamfill::FIL_HOST) continue;
+            u32 m[2] = {0, 0};
+            for(u32 k = 0; k < in->unit_count[u]; k++) m[in->recs[in->unit_first[u] + k].which & 1]++;
+            if(hlala_bamfill::fil_is_wide(in->unit_count[u], m[0], m[1])) { wideUnits.push_back((u32)u); wide.longest = std::max<int64_t>(wide.longest, std::max(m[0], m[1])); }
+        }
+        wide.units = wideUnits.data(); wide.n = wideUnits.size();
+    }
     const auto tWall = std::chrono::steady_clock::now();
     memset(stats, 0, sizeof(*stats));
     if(in->n_units == 0) return HLALA_OK;
@@ -3395,7 +3458,7 @@ extern "C" int hlala_bam_fill_create(hlala_inflater* f, const hlala_bam_fill_in*
     if(!H) return HLALA_E_DEVICE;
     DevGuard g(f->device);
     hipError_t e = hipSuccess;
-    auto failed = [&](const char* what) { f->err = std::string("hlala_bam_fill_create: ") + what + ": " + hipGetErrorString(e); (void)hipGetLastError(); fill_free(H); return HLALA_E_DEVICE; };
+    auto failed = [&](const char* what) { f->err = std::string(fn) + ": " + what + ": " + hipGetErrorString(e); (void)hipGetLastError(); fill_free(H); return HLALA_E_DEVICE; };
     const size_t recBytes = (size_t)in->n * sizeof(hlala_bam_rec);
     if((e = fill_alloc(H, FIL_RECS, recBytes)) != hipSuccess || (e = fill_alloc(H, FIL_BYTES, in->n_bytes)) != hipSuccess) return failed("hipMalloc");
     e = hipEventRecord(H->ev[0], H->st);
@@ -3408,10 +3471,26 @@ extern "C" int hlala_bam_fill_create(hlala_inflater* f, const hlala_bam_fill_in*
     stats->bytes_h2d = (int64_t)(recBytes + in->n_bytes);
     H->S.recs = (const hlala_bam_rec*)H->buf[FIL_RECS].p; H->S.n = (u32)in->n; H->S.bytes = (const uint8_t*)H->buf[FIL_BYTES].p; H->S.nBytes = (u64)in->n_bytes; H->S.perm = nullptr;
     bool noMemory = false;
-    const int rc = fill_layout(H, in, read_off, chain_off, cigar_count, name_off, stats, &noMemory);
-    if(rc != HLALA_OK || noMemory) { f->err = noMemory ? std::string("hlala_bam_fill_create: no device memory for the passes") : H->err; fill_free(H); return noMemory ? HLALA_E_DEVICE : rc; }
+    const int rc = fill_layout(H, in, read_off, chain_off, cigar_count, name_off, stats, &noMemory, isWide ? &wide : nullptr);
+    if(rc != HLALA_OK || noMemory) { f->err = noMemory ? std::string(fn) + ": no device memory for the passes" : H->err; fill_free(H); return noMemory ? HLALA_E_DEVICE : rc; }
     stats->ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tWall).count();
     *out = H;
+    return HLALA_OK;
+}
+extern "C" int hlala_bam_fill_create(hlala_inflater* f, const hlala_bam_fill_in* in, int64_t* read_off, int64_t* chain_off, int64_t* cigar_count, int64_t* name_off, hlala_bam_fill** out,
+                                     hlala_bam_fill_stats* stats)
+{
+    return fill_create("hlala_bam_fill_create", f, in, 0, false, read_off, chain_off, cigar_count, name_off, out, stats);
+}
+extern "C" int hlala_bam_fill_create_wide(hlala_inflater* f, const hlala_bam_fill_in* in, int32_t max_mate, int64_t* read_off, int64_t* chain_off, int64_t* cigar_count, int64_t* name_off,
+                                          hlala_bam_fill** out, hlala_bam_fill_stats* stats)
+{
+    return fill_create("hlala_bam_fill_create_wide", f, in, max_mate, true, read_off, chain_off, cigar_count, name_off, out, stats);
+}
+extern "C" int hlala_bam_fill_wide_stats(const hlala_bam_fill* h, int64_t out[4])
+{
+    if(!h || !out) return HLALA_E_ARG;
+    for(int k = 0; k < 4; k++) out[k] = h->wideStats[k];
     return HLALA_OK;
 }
 extern "C" int hlala_bam_fill_window(hlala_bam_fill* h, int64_t first_unit, int64_t n_units, const hlala_bam_fill_out* out, hlala_bam_fill_stats* stats)
@@ -3470,8 +3549,8 @@ static int fill_state_window(void* state, int64_t first_unit, int64_t n_units, c
     return rc;
 }
 static void fill_state_destroy(void* state) { fill_free((hlala_bam_fill*)state); }
-static int bam_fill_hook(void* inflater, const hlala_bam_fill_in* in, int64_t* read_off, int64_t* chain_off, int64_t* cigar_count, int64_t* name_off, hlala_host::bam_fill_handle* handle,
-                         hlala_bam_fill_stats* stats, bool* available, std::string* err)
+static int fill_hook_any(void* inflater, const hlala_bam_fill_in* in, const FillWideIn* wide, int64_t* read_off, int64_t* chain_off, int64_t* cigar_count, int64_t* name_off,
+                         hlala_host::bam_fill_handle* handle, hlala_bam_fill_stats* stats, bool* available, std::string* err)
 {
     hlala_inflater* f = (hlala_inflater*)inflater;
     if(!f || !in || !handle || !stats || !available) return HLALA_E_ARG;
@@ -3497,12 +3576,24 @@ static int bam_fill_hook(void* inflater, const hlala_bam_fill_in* in, int64_t* r
     if(e != hipSuccess) { f->err = std::string("BAM fill: the permutation: ") + hipGetErrorString(e); (void)hipGetLastError(); fill_free(H); return fail(HLALA_E_DEVICE); }
     H->S.perm = (const u32*)H->buf[FIL_PERM].p;
     bool noMemory = false;
-    const int rc = fill_layout(H, in, read_off, chain_off, cigar_count, name_off, stats, &noMemory);
+    const int rc = fill_layout(H, in, read_off, chain_off, cigar_count, name_off, stats, &noMemory, wide);
     if(rc != HLALA_OK) { f->err = H->err; fill_free(H); return fail(rc); }
     if(noMemory) { fill_free(H); *available = false; return HLALA_OK; }
     stats->ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tWall).count();
     handle->state = H; handle->window = fill_state_window; handle->destroy = fill_state_destroy;
     return HLALA_OK;
+}
+static int bam_fill_hook(void* inflater, const hlala_bam_fill_in* in, int64_t* read_off, int64_t* chain_off, int64_t* cigar_count, int64_t* name_off, hlala_host::bam_fill_handle* handle,
+                         hlala_bam_fill_stats* stats, bool* available, std::string* err)
+{
+    return fill_hook_any(inflater, in, nullptr, read_off, chain_off, cigar_count, name_off, handle, stats, available, err);
+}
+static int bam_fill_wide_hook(void* inflater, const hlala_bam_fill_in* in, int32_t max_mate, const uint32_t* wide_units, int64_t n_wide, int64_t longest, int64_t* read_off, int64_t* chain_off,
+                              int64_t* cigar_count, int64_t* name_off, hlala_host::bam_fill_handle* handle, hlala_bam_fill_stats* stats, bool* available, std::string* err)
+{
+    if(max_mate <= (int32_t)hlala_bamfill::FIL_MAX_MATE || max_mate > (int32_t)hlala_bamfill::FIL_WIDE_MAX || n_wide < 0 || (n_wide && !wide_units)) return HLALA_E_ARG;
+    const FillWideIn wide{max_mate, wide_units, (size_t)n_wide, longest};
+    return fill_hook_any(inflater, in, &wide, read_off, chain_off, cigar_count, name_off, handle, stats, available, err);
 }
 
 // ---- a batch from a window of a fill state, built on the device (include/hlala_gpu.h; kernel_bamresident.hip).  Everything runs on the context's upload stream: the

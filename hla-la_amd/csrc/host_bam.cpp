@@ -248,6 +248,7 @@ struct hlala_seed_batch {
     int64_t group_counts[3] = {0, 0, 0};        // HLALA_SEEDS_GPU_GROUP: records grouped on the GPU, collided runs the host regrouped, 1 = the whole sample was grouped by the host instead
     int64_t sort_counts[3] = {0, 0, 0};         // HLALA_SEEDS_GPU_SORT: units ordered on the GPU, units of collided runs the host merged in, 1 = the whole sample was ordered by the host instead
     int64_t fill_counts[3] = {0, 0, 0};         // HLALA_SEEDS_GPU_FILL: units the GPU fills, host units, 1 = the whole sample was laid out and filled by the host instead
+    int64_t fill_wide_counts[3] = {0, 0, 0};    // HLALA_SEEDS_GPU_FILL_WIDE: wide units the GPU fills, units beyond HLALA_BAM_FILL_WIDE_MAX left to the host, the longest mate seen
     double fill_window_ms = 0;                  // ... wall clock of its window calls so far (HLALA_BAM_DEBUG prints it)
     double fill_ms[5] = {0, 0, 0, 0, 0};        // ... device milliseconds of its window passes so far: chain, cigar, names, bases, download
     bool pinned = false;
@@ -437,6 +438,7 @@ bam_scan_hook_t g_bam_scan_hook = nullptr;                     // ... (HLALA_SEE
 bam_group_hook_t g_bam_group_hook = nullptr;                   // ... (HLALA_SEEDS_GPU_GROUP)
 bam_sort_hook_t g_bam_sort_hook = nullptr;                     // ... (HLALA_SEEDS_GPU_SORT)
 bam_fill_hook_t g_bam_fill_hook = nullptr;                     // ... (HLALA_SEEDS_GPU_FILL)
+bam_fill_wide_hook_t g_bam_fill_wide_hook = nullptr;           // ... (HLALA_SEEDS_GPU_FILL_WIDE)
 }  // namespace hlala_host
 
 // (host code: no device involved)
@@ -548,6 +550,8 @@ try {
     if(gpuSort && (!gpuGroup || !g_bam_sort_hook)) { g_bam_error = "HLALA_SEEDS_GPU_SORT needs HLALA_SEEDS_GPU_GROUP"; return HLALA_E_ARG; }
     const bool gpuFill = (flags & HLALA_SEEDS_GPU_FILL) != 0;
     if(gpuFill && (!gpuSort || !g_bam_fill_hook)) { g_bam_error = "HLALA_SEEDS_GPU_FILL needs HLALA_SEEDS_GPU_SORT"; return HLALA_E_ARG; }
+    const bool gpuFillWide = (flags & HLALA_SEEDS_GPU_FILL_WIDE) != 0;
+    if(gpuFillWide && !gpuFill) { g_bam_error = "HLALA_SEEDS_GPU_FILL_WIDE needs HLALA_SEEDS_GPU_FILL"; return HLALA_E_ARG; }
     int T = n_threads;
     // Default: at most 32 threads.  Measured on a 256-thread host (tools/gpu_decode_threads.sh, 8.4 M pairs, 2.6 GB of BAM): 5.2 s on 8 threads, 3.5 on 16, 2.85 on 32,
     // 3.0 on 64, 3.3-3.7 on 128 -- the phases are passes over ~12 GB of inflated records bound by memory latency and by the first touch of their
@@ -1126,31 +1130,57 @@ try {
     // which units it keeps for itself -- those it split out of collided runs (their records are no longer where the device's permutation says) and those with more
     // than HLALA_BAM_FILL_MAX_MATE alignments on a mate (at most 16 records: no look at the mates; 17 to 32: counted; more: a host unit) -- and computes their sizes
     // with its own sorted_mate.  Where the device has no answer the host lays out and fills the whole sample as without the flag.
+    // HLALA_SEEDS_GPU_FILL_WIDE: the limit on a mate is HLALA_BAM_FILL_WIDE_MAX instead; the units between the two limits (and those of more than 32 records) are listed
+    // as wide units for the sixth hook.  Where that hook is absent or has no answer, the units are marked again as without the flag, for the fifth.
     bool filledOnGpu = false;
     if(gpuFill) {
         if(fillKept && groupedOnGpu && sortedOnGpu && nU > 0 && nU < ((size_t)1 << 30) && groupedDesc < ((size_t)1 << 31)) {
             Buf<uint32_t> ufirst, ucount; ufirst.alloc(nU); ucount.alloc(nU);
-            parallel_for(nUChunks, T, [&](int64_t c, int) {
-                const size_t a = (size_t)(c * UCH), z = std::min(nU, a + (size_t)UCH);
-                for(size_t ui = a; ui < z; ui++) {
-                    const Unit& u = units[ui];
-                    bool host = u.host != 0 || u.count > 2 * HLALA_BAM_FILL_MAX_MATE;
-                    if(!host && u.count > HLALA_BAM_FILL_MAX_MATE) { uint32_t k0 = 0; const Rec* R = precs[u.part].data() + u.first; for(uint32_t k = 0; k < u.count; k++) k0 += R[k].which == 0; host = k0 > HLALA_BAM_FILL_MAX_MATE || u.count - k0 > HLALA_BAM_FILL_MAX_MATE; }
-                    ufirst[ui] = host ? HLALA_BAM_FILL_HOST : (uint32_t)(groupedPartStart[u.part] + u.first); ucount[ui] = u.count;
+            Buf<uint8_t> uwide; Buf<uint32_t> ulong;                  // (wide marking only) 1: a wide unit; the longer mate of a unit of more than 16 records
+            std::vector<uint32_t>& hostUnits = W->hostUnits; std::vector<int64_t> hostSizes; std::vector<uint32_t> wideUnits; int64_t longest = 0, longestBeyond = 0, beyond = 0;      // longest: among the wide units
+            auto mark = [&](const bool wide) {
+                const uint32_t cap = wide ? HLALA_BAM_FILL_WIDE_MAX : HLALA_BAM_FILL_MAX_MATE;
+                if(wide) { uwide.alloc(nU); ulong.alloc(nU); }
+                parallel_for(nUChunks, T, [&](int64_t c, int) {
+                    const size_t a = (size_t)(c * UCH), z = std::min(nU, a + (size_t)UCH);
+                    for(size_t ui = a; ui < z; ui++) {
+                        const Unit& u = units[ui];
+                        bool host = u.host != 0 || u.count > 2 * cap; uint32_t k0 = 0, k1 = 0;
+                        if(u.count > HLALA_BAM_FILL_MAX_MATE && (wide || !host)) { const Rec* R = precs[u.part].data() + u.first; for(uint32_t k = 0; k < u.count; k++) k0 += R[k].which == 0; k1 = u.count - k0; host = host || k0 > cap || k1 > cap; }
+                        ufirst[ui] = host ? HLALA_BAM_FILL_HOST : (uint32_t)(groupedPartStart[u.part] + u.first); ucount[ui] = u.count;
+                        if(wide) { ulong[ui] = std::max(k0, k1); uwide[ui] = !host && (u.count > 2 * HLALA_BAM_FILL_MAX_MATE || k0 > HLALA_BAM_FILL_MAX_MATE || k1 > HLALA_BAM_FILL_MAX_MATE); }
+                    }
+                });
+                hostUnits.clear(); hostSizes.clear(); wideUnits.clear(); longest = 0; longestBeyond = 0; beyond = 0;
+                for(size_t ui = 0; ui < nU; ui++) {
+                    if(wide && uwide[ui]) { wideUnits.push_back((uint32_t)ui); longest = std::max<int64_t>(longest, ulong[ui]); }
+                    if(ufirst[ui] != HLALA_BAM_FILL_HOST) continue;
+                    const Unit& u = units[ui]; const std::vector<Rec>& R = precs[u.part]; std::vector<uint32_t>& idx = order[0];
+                    hostUnits.push_back((uint32_t)ui);
+                    if(wide && ulong[ui] > cap) { beyond++; longestBeyond = std::max<int64_t>(longestBeyond, ulong[ui]); }
+                    for(int m = 0; m < nm; m++) { const size_t prim = sorted_mate(precs, u, m, idx); int64_t cg = 0; for(uint32_t k : idx) cg += R[k].n_cigar; hostSizes.push_back(R[idx[prim]].l_seq); hostSizes.push_back((int64_t)idx.size()); hostSizes.push_back(cg); }
+                    hostSizes.push_back((int64_t)u.nameLen + 1);
                 }
-            });
-            std::vector<uint32_t>& hostUnits = W->hostUnits; std::vector<int64_t> hostSizes;
-            for(size_t ui = 0; ui < nU; ui++) if(ufirst[ui] == HLALA_BAM_FILL_HOST) {
-                const Unit& u = units[ui]; const std::vector<Rec>& R = precs[u.part]; std::vector<uint32_t>& idx = order[0];
-                hostUnits.push_back((uint32_t)ui);
-                for(int m = 0; m < nm; m++) { const size_t prim = sorted_mate(precs, u, m, idx); int64_t cg = 0; for(uint32_t k : idx) cg += R[k].n_cigar; hostSizes.push_back(R[idx[prim]].l_seq); hostSizes.push_back((int64_t)idx.size()); hostSizes.push_back(cg); }
-                hostSizes.push_back((int64_t)u.nameLen + 1);
-            }
+            };
             hlala_bam_fill_in fin; memset(&fin, 0, sizeof(fin));
-            fin.n = (int64_t)groupedDesc; fin.unit_first = ufirst.data(); fin.unit_count = ucount.data(); fin.n_units = (int64_t)nU; fin.host_sizes = hostSizes.data(); fin.n_host_units = (int64_t)hostUnits.size();
-            fin.long_read_mode = long_read_mode ? 1 : 0; fin.packed = S->packed ? 1 : 0;
-            hlala_bam_fill_stats fs; bool available = false; std::string herr; bam_fill_handle handle;
-            const int rc = g_bam_fill_hook(gpuInflater, &fin, S->read_off.data(), S->chain_off.data(), cigCount.data(), S->name_off.data(), &handle, &fs, &available, &herr);
+            auto fill_in = [&]() {
+                fin.n = (int64_t)groupedDesc; fin.unit_first = ufirst.data(); fin.unit_count = ucount.data(); fin.n_units = (int64_t)nU; fin.host_sizes = hostSizes.data(); fin.n_host_units = (int64_t)hostUnits.size();
+                fin.long_read_mode = long_read_mode ? 1 : 0; fin.packed = S->packed ? 1 : 0;
+            };
+            hlala_bam_fill_stats fs; bool available = false, wideDone = false; std::string herr; bam_fill_handle handle;
+            int rc = HLALA_OK;
+            if(gpuFillWide && g_bam_fill_wide_hook) {
+                mark(true); fill_in();
+                rc = g_bam_fill_wide_hook(gpuInflater, &fin, HLALA_BAM_FILL_WIDE_MAX, wideUnits.data(), (int64_t)wideUnits.size(), longest, S->read_off.data(), S->chain_off.data(), cigCount.data(),
+                                          S->name_off.data(), &handle, &fs, &available, &herr);
+                if(rc != HLALA_OK) throw Fail("BAM fill on the GPU failed: " + herr);
+                wideDone = available;
+                if(wideDone) { S->fill_wide_counts[0] = (int64_t)wideUnits.size(); S->fill_wide_counts[1] = beyond; S->fill_wide_counts[2] = std::max(longest, longestBeyond); }
+            }
+            if(!wideDone) {
+                mark(false); fill_in();
+                rc = g_bam_fill_hook(gpuInflater, &fin, S->read_off.data(), S->chain_off.data(), cigCount.data(), S->name_off.data(), &handle, &fs, &available, &herr);
+            }
             if(rc != HLALA_OK) throw Fail("BAM fill on the GPU failed: " + herr);
             if(available) {
                 if(S->read_off[0] != 0 || S->chain_off[0] != 0 || cigCount[0] != 0 || S->name_off[0] != 0 || S->read_off[nR] < 0 || S->chain_off[nR] < 0 || cigCount[nR] < 0 || S->name_off[nU] < (int64_t)nU) {
@@ -1286,6 +1316,12 @@ extern "C" int hlala_seed_batch_sort_counts(const hlala_seed_batch* S, int64_t c
 {
     if(!S || !counts) return HLALA_E_ARG;
     for(int i = 0; i < 3; i++) counts[i] = S->sort_counts[i];
+    return HLALA_OK;
+}
+extern "C" int hlala_seed_batch_fill_wide_counts(const hlala_seed_batch* S, int64_t counts[3])
+{
+    if(!S || !counts) return HLALA_E_ARG;
+    for(int i = 0; i < 3; i++) counts[i] = S->fill_wide_counts[i];
     return HLALA_OK;
 }
 extern "C" int hlala_seed_batch_fill_counts(const hlala_seed_batch* S, int64_t counts[3])

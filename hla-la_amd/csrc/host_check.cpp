@@ -148,6 +148,35 @@ int hlala_host_bam_fill_model(const hlala_bam_fill_in* in, int64_t* read_off, in
     g_err = why ? std::string("hlala_host_bam_fill_model: ") + why : std::string();
     return rc;
 }
+// The same with the wide layout (bam_fill_wide_core.h): hlala_bam_fill_create_wide followed by one window.  wide[4] (may be null): what hlala_bam_fill_wide_stats
+// reports, the device time 0.  For a sample without wide units every output equals hlala_host_bam_fill_model's.
+int hlala_host_bam_fill_model_wide(const hlala_bam_fill_in* in, int32_t max_mate, int64_t* read_off, int64_t* chain_off, int64_t* cigar_count, int64_t* name_off, int64_t first_unit,
+                                   int64_t n_units, const hlala_bam_fill_out* out, hlala_bam_fill_stats* stats, int64_t* wide)
+{
+    const char* why = nullptr;
+    hlala_bamfill::FillLayout L;
+    int rc = hlala_bamfill::fill_model_create_wide(in, max_mate, read_off, chain_off, cigar_count, name_off, &L, stats, wide, &why);
+    if(rc == HLALA_OK && n_units >= 0 && in->n_units > 0) rc = hlala_bamfill::fill_model_window(in, &L, read_off, chain_off, cigar_count, name_off, first_unit, n_units, out, &why);
+    g_err = why ? std::string("hlala_host_bam_fill_model_wide: ") + why : std::string();
+    return rc;
+}
+// fil_sort_wide on scores in file order: order[rank] = place; returns the heap sorts entered, -1 for n beyond HLALA_BAM_FILL_WIDE_MAX
+int hlala_host_bam_fill_wide_order(const int32_t* score, int32_t n, uint32_t* order)
+{
+    if(n < 0 || n > (int32_t)hlala_bamfill::FIL_WIDE_MAX || (n && (!score || !order))) return -1;
+    std::vector<int32_t> s(score, score + n); std::vector<uint16_t> p((size_t)n); uint32_t stack[hlala_bamfill::FIL_WIDE_STACK_WORDS];
+    for(int32_t i = 0; i < n; i++) p[(size_t)i] = (uint16_t)i;
+    const uint32_t h = hlala_bamfill::fil_sort_wide(s.data(), p.data(), (uint32_t)n, stack);
+    for(int32_t i = 0; i < n; i++) order[i] = p[(size_t)i];
+    return h == hlala_bamfill::FIL_WIDE_OVERFLOW ? -1 : (int)h;
+}
+// scores that drive std::sort into its heap sort (bam_fill_model.h: fil_adversary), made against the library this was built with
+int hlala_host_bam_fill_wide_adversary(int32_t n, int32_t* score)
+{
+    if(n < 0 || (n && !score)) return -1;
+    hlala_bamfill::fil_adversary((uint32_t)n, score);
+    return 0;
+}
 // What hlala_batch_create / _unpaired does to a window before it uploads it, and so what hlala_batch_create_from_fill's kernels (kernel_bamresident.hip) must leave in
 // the batch: the five 32-bit arrays, the smallest index of every violation class, the return code and (hlala_host_last_error) its text, without a device.
 int hlala_host_batch_resident_model(const hlala_batch_in* in, int32_t n_contigs, int32_t unpaired, int32_t* read_off32, int32_t* chain_off32, int32_t* primary32, int32_t* chain_read,

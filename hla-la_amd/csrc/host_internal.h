@@ -92,6 +92,12 @@ struct bam_fill_handle {
 typedef int (*bam_fill_hook_t)(void* inflater, const hlala_bam_fill_in* in, int64_t* read_off, int64_t* chain_off, int64_t* cigar_count, int64_t* name_off, bam_fill_handle* handle,
                                hlala_bam_fill_stats* stats, bool* available, std::string* err);
 extern bam_fill_hook_t g_bam_fill_hook;
+// The same with the wide units on the device as well (HLALA_SEEDS_GPU_FILL_WIDE): the sixth hook, called in the fifth's place.  wide_units[n_wide]: the units, ascending,
+// with unit_count > 32 or a mate beyond 16 alignments (none beyond max_mate: those are host units); longest: the longest mate among them.  *available = false (with
+// HLALA_OK) BEFORE anything was taken over: the decoder marks its host units as without the flag and calls the fifth hook.
+typedef int (*bam_fill_wide_hook_t)(void* inflater, const hlala_bam_fill_in* in, int32_t max_mate, const uint32_t* wide_units, int64_t n_wide, int64_t longest, int64_t* read_off,
+                                    int64_t* chain_off, int64_t* cigar_count, int64_t* name_off, bam_fill_handle* handle, hlala_bam_fill_stats* stats, bool* available, std::string* err);
+extern bam_fill_wide_hook_t g_bam_fill_wide_hook;
 // hlala_bam_extract_seeds_opt (gpu = false) and hlala_bam_extract_seeds_gpu (gpu = true: the hook above inflates with `inflater`)
 int bam_extract_seeds_impl(const char* path, int32_t n_intervals, const hlala_bam_interval* iv, int32_t long_read_mode, int32_t n_threads, int32_t flags, bool gpu, void* inflater, hlala_seed_batch** out);
 

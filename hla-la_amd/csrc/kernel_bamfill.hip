@@ -15,21 +15,33 @@
 //   k_fil_names    a 16-lane group per unit, consecutive lanes on consecutive bytes, the NUL behind
 //   k_fil_bases    a wavefront per read, consecutive lanes on consecutive output bytes: bases (unpacked through the 16-letter code, or the packed bytes as they lie)
 //                  and qualities + 33
-// No kernel's serial depth depends on the sample; the loops of a lane run over 16 lanes, or over the bytes of one record's part in strides of the group.
+// and, only where hlala_bam_fill_create_wide or HLALA_SEEDS_GPU_FILL_WIDE found wide units (unit_count > 32 or a mate beyond 16; bam_fill_wide_core.h), which
+// k_fil_rank and k_fil_src then leave alone (FilSample::wide, a bit per unit):
+//   k_fil_wide_rank  a wavefront per wide read, drawn from the host's list of wide units: the lanes walk the unit's records in strides of 64 and keep the mate's by
+//                  ballot and prefix count, score and place into LDS in file order; lane 0 runs fil_sort_wide there (the idiom of k_bgzf_inflate: the serial part on
+//                  one lane, the wave places the result); the wave writes the sorted descriptor numbers and the exclusive prefix of their CIGAR counts into the
+//                  read's slots of two scratch arrays, finds the first primary by a ballot in sorted order and writes the sizes where k_fil_rank writes them
+//   k_fil_wide_src   behind the scans, a lane per slot: chain_src, chain_cig and read_primary from the scratch arrays (the sort is not run twice)
+// No narrow kernel's serial depth depends on the sample; the loops of a lane run over 16 lanes, or over the bytes of one record's part in strides of the group.
 //
 // Bounds: a unit's range is checked against n before a descriptor is read and a permutation value before it indexes; every byte of the buffer is read through
 // fil_byte (nothing at or beyond nBytes); chain numbers are checked against the chain count and every window offset against the window's size before a store.
-// What cannot be laid out (a mate beyond 16, no primary, a range outside the descriptors) sets a bit in *bad and is refused by the host before any window runs.
+// What cannot be laid out (a mate beyond 16, or beyond max_mate on the wide path, no primary, a range outside the descriptors) sets a bit in *bad and is refused by
+// the host before any window runs.  The wide kernels check the list entry against the unit count, the unit's range and every place taken from LDS against the unit's
+// count, the mate's count against max_mate before a slot of LDS is written, and every scratch offset against the read's slots.
 #pragma once
 #include <cstddef>
 #include "device_common.h"
 #include "bam_fill_core.h"
+#include "bam_fill_wide_core.h"
 
 namespace hlala {
 
 struct FilSample {
     const hlala_bam_rec* recs; u32 n; const uint8_t* bytes; u64 nBytes; const u32* perm; const u32* unitFirst; const u32* unitCount; u32 nUnits; u32 nm;
+    const u32* wide;      // a bit per unit: the wide kernels lay it out (null: no unit)
 };
+__device__ __forceinline__ bool fil_wide_unit(const FilSample& S, u64 u) { return S.wide && ((S.wide[u >> 5] >> (u & 31u)) & 1u); }
 enum { FIL_BAD_RANGE = 1, FIL_BAD_MATE = 2, FIL_BAD_PRIMARY = 4, FIL_BAD_PERM = 8 };
 
 __global__ __launch_bounds__(256) void k_fil_append(u32 n, const hlala_bam_rec* in, u64 base, hlala_bam_rec* out)
@@ -62,7 +74,7 @@ __device__ __forceinline__ FilLane fil_rank(const FilSample& S, u64 r, bool live
     const u32 l = threadIdx.x & 15u, grp = (u32)lane_id() >> 4;
     u32 first = FIL_HOST, count = 0, mate = 0;
     if(live) { const u64 u = r / S.nm; mate = (u32)(r % S.nm); first = S.unitFirst[u]; count = S.unitCount[u]; }
-    bool fill = live && first != FIL_HOST;
+    bool fill = live && first != FIL_HOST && !fil_wide_unit(S, r / S.nm);
     if(fill && (count == 0 || (u64)first + count > S.n)) { bad |= FIL_BAD_RANGE; fill = false; }
     if(fill && count > FIL_MAX_UNIT) { bad |= FIL_BAD_MATE; count = FIL_MAX_UNIT; }
     // records l and l + 16 of the unit: do they belong to this mate
@@ -108,7 +120,7 @@ __global__ __launch_bounds__(256) void k_fil_rank(FilSample S, u64 nReads, int64
     u32 bad = 0;
     const FilLane L = fil_rank(S, r, live, bad);
     if(bad) atomicOr(badOut, bad);
-    if(!live || (threadIdx.x & 15u) != 0 || S.unitFirst[r / S.nm] == hlala_bamfill::FIL_HOST) return;
+    if(!live || (threadIdx.x & 15u) != 0 || S.unitFirst[r / S.nm] == hlala_bamfill::FIL_HOST || fil_wide_unit(S, r / S.nm)) return;
     lSeq[r] = L.lSeq > 0 ? L.lSeq : 0; nChain[r] = L.cnt; nCig[r] = L.cigTotal;
     if(r % S.nm == 0) nameSize[r / S.nm] = (int64_t)L.nameLen + 1;
 }
@@ -137,6 +149,89 @@ __global__ __launch_bounds__(256) void k_fil_src(FilSample S, u64 nReads, const 
     if(c >= nChains || c >= (u64)chainOff[r + 1]) return;
     chainSrc[c] = L.g; chainCig[c] = cigCount[r] + (int64_t)L.cigBefore;
     if(L.isPrimary) readPrimary[r] = (int32_t)c;
+}
+
+// ---- the wide units.  unit[w]: wide unit w; wide read wr = w * nm + mate owns the slots [off[wr], off[wr + 1]) of desc / cig (unit_count of them: no mate has more)
+struct FilWide { const u32* unit; const u32* off; u32 nUnits, maxMate; u32 *desc, *cig, *prim; };
+constexpr u32 FIL_NO_PRIMARY = 0xFFFFFFFFu;
+
+__global__ __launch_bounds__(64) void k_fil_wide_rank(FilSample S, FilWide Wd, int64_t* lSeq, int64_t* nChain, int64_t* nCig, int64_t* nameSize, u32* badOut)
+{
+    using namespace hlala_bamfill;
+    __shared__ int32_t sScore[FIL_WIDE_MAX];
+    __shared__ uint16_t sPlace[FIL_WIDE_MAX];
+    __shared__ u32 sStack[FIL_WIDE_STACK_WORDS];
+    __shared__ u32 sHeaps;
+    const u32 wr = blockIdx.x, lane = (u32)lane_id(), w = wr / S.nm, mate = wr % S.nm;
+    if(w >= Wd.nUnits) return;
+    // (every condition that ends the wavefront early is wave-uniform)
+    const u32 u = Wd.unit[w];
+    if(u >= S.nUnits) { if(lane == 0) atomicOr(badOut, (u32)FIL_BAD_RANGE); return; }
+    const u32 first = S.unitFirst[u], count = S.unitCount[u], cap = Wd.maxMate < FIL_WIDE_MAX ? Wd.maxMate : FIL_WIDE_MAX;
+    const u32 off = Wd.off[wr], offEnd = Wd.off[wr + 1];
+    if(first == FIL_HOST || count == 0 || (u64)first + count > S.n || offEnd < off || offEnd - off < count) { if(lane == 0) atomicOr(badOut, (u32)FIL_BAD_RANGE); return; }
+    if(count > S.nm * cap) { if(lane == 0) atomicOr(badOut, (u32)FIL_BAD_MATE); return; }                // (so a place fits 16 bits: count <= 2 * 4096)
+    u32 bad = 0, n = 0;
+    for(u32 base = 0; base < count; base += 64u) {
+        const u32 k = base + lane;
+        bool mine = false; int32_t as = 0;
+        if(k < count) { const hlala_bam_rec& x = S.recs[fil_desc(S, (u64)first + k, bad)]; mine = x.which == mate; as = x.as; }
+        const u64 b = __ballot(mine);
+        const u32 at = n + (u32)__popcll(b & ((1ull << lane) - 1ull));
+        if(mine && at < cap) { sScore[at] = as; sPlace[at] = (uint16_t)k; }
+        n += (u32)__popcll(b);
+    }
+    if(n > cap) { if(lane == 0) atomicOr(badOut, (u32)FIL_BAD_MATE); return; }
+    WSYNC();
+    if(lane == 0) sHeaps = fil_sort_wide(sScore, sPlace, n, sStack);
+    WSYNC();
+    if(sHeaps == FIL_WIDE_OVERFLOW) { if(lane == 0) atomicOr(badOut, (u32)FIL_BAD_MATE); return; }
+    u32 cigBefore = 0, primAt = FIL_NO_PRIMARY; int32_t lseq = 0;
+    for(u32 base = 0; base < n; base += 64u) {
+        const u32 i = base + lane;
+        u32 g = 0, nc = 0; bool prim = false, ok = false; int32_t ls = 0;
+        if(i < n) {
+            const u32 k = sPlace[i];
+            if(k < count) { g = fil_desc(S, (u64)first + k, bad); const hlala_bam_rec& x = S.recs[g]; nc = x.n_cigar; prim = ((x.flags >> 1) & 1u) != 0; ls = x.l_seq; ok = true; }
+            else bad |= FIL_BAD_RANGE;
+        }
+        int total = 0;
+        const u32 before = (u32)wave_excl_scan((int)nc, total);
+        if(ok && i < offEnd - off) { Wd.desc[off + i] = g; Wd.cig[off + i] = cigBefore + before; }
+        const u64 pb = __ballot(prim);
+        if(primAt == FIL_NO_PRIMARY && pb) { const int src = __ffsll((unsigned long long)pb) - 1; primAt = base + (u32)src; lseq = __shfl(ls, src); }
+        cigBefore += (u32)total;
+    }
+    if(primAt == FIL_NO_PRIMARY) bad |= FIL_BAD_PRIMARY;
+    if(bad) atomicOr(badOut, bad);
+    if(lane != 0) return;
+    const u64 r = (u64)u * S.nm + mate;
+    lSeq[r] = lseq > 0 ? lseq : 0; nChain[r] = n; nCig[r] = cigBefore; Wd.prim[wr] = primAt;
+    if(mate == 0) { u32 b2 = 0; nameSize[u] = (int64_t)S.recs[fil_desc(S, first, b2)].nameLen + 1; }
+}
+
+// slot j of the scratch arrays: the wide read whose slots hold it, chain i of that read
+__global__ __launch_bounds__(256) void k_fil_wide_src(FilSample S, FilWide Wd, u32 nWideReads, u32 nSlots, const int64_t* chainOff, const int64_t* cigCount, u64 nChains, u32* chainSrc, int64_t* chainCig,
+                                                      int32_t* readPrimary)
+{
+    const u64 t = (u64)blockIdx.x * 256u + threadIdx.x;
+    if(t >= nSlots || nWideReads == 0) return;
+    const u32 j = (u32)t;
+    u32 lo = 0, hi = nWideReads;                            // off[lo] <= j < off[hi]
+    while(hi - lo > 1u) { const u32 mid = lo + (hi - lo) / 2u; if(Wd.off[mid] <= j) lo = mid; else hi = mid; }
+    if(Wd.off[lo] > j || j >= Wd.off[lo + 1]) return;
+    const u32 i = j - Wd.off[lo], w = lo / S.nm, mate = lo % S.nm;
+    if(w >= Wd.nUnits) return;
+    const u32 u = Wd.unit[w];
+    if(u >= S.nUnits) return;
+    const u64 r = (u64)u * S.nm + mate;
+    const int64_t c0 = chainOff[r], c1 = chainOff[r + 1];
+    if(c0 < 0 || c1 < c0 || (int64_t)i >= c1 - c0) return;
+    const u64 c = (u64)c0 + i;
+    const u32 g = Wd.desc[j];
+    if(c >= nChains || g >= S.n) return;
+    chainSrc[c] = g; chainCig[c] = cigCount[r] + (int64_t)Wd.cig[j];
+    if(i == Wd.prim[lo]) readPrimary[r] = (int32_t)c;
 }
 
 // ---- a window: chains [c0, c0 + nc), CIGAR words [g0, g0 + ng), units [u0, u0 + nu) with name bytes [n0, n0 + nn), reads [r0, r0 + nr) with bases [b0, b0 + nb)

@@ -10,7 +10,7 @@
 // terminate), this program prints the message to stderr and exits with a non-zero status -- HLA-LA.pl treats any non-zero status as
 // failure (:567-570).  Extra, optional arguments of this program: --devices <gpu,gpu,...> (or --device <gpu>): the batches of the sample are
 // dealt round-robin to one context per listed GPU (a GPU may be listed twice: two contexts on it), results do not depend on the list;
-// --decodeSlots <samples that decode at one time, default CPUs / 16>, --tailPool <k: GPU batches per launch of the widest DP classes>, --pairOverflow <MiB of device scratch for pairs beyond the pairing capacities, default 0: such pairs are refused>, --decodeThreads <host threads of the BAM decoder, default all>, --gpuInflate 0|1 <BGZF blocks inflated on the first listed GPU, default 0>, --gpuParse 0|1 <the BAM records found, filtered and parsed there as well, default 0; 1 implies --gpuInflate 1>, --gpuGroup 0|1 <the records grouped by read name there as well, default 0; 1 implies --gpuParse 1>, --gpuSort 0|1 <the units put into read-name order there as well, default 0; 1 implies --gpuGroup 1>, --gpuFill 0|1 <the sample laid out and its windows filled there as well, default 0; 1 implies --gpuSort 1>, --verifyCRC 0|1 <the CRC-32 of every BGZF block checked against its inflated bytes, on the GPU where they are inflated there, default 0>, --batchPairs <units per GPU batch>, --rngSeed <base of the end-cell draws>,
+// --decodeSlots <samples that decode at one time, default CPUs / 16>, --tailPool <k: GPU batches per launch of the widest DP classes>, --pairOverflow <MiB of device scratch for pairs beyond the pairing capacities, default 0: such pairs are refused>, --decodeThreads <host threads of the BAM decoder, default all>, --gpuInflate 0|1 <BGZF blocks inflated on the first listed GPU, default 0>, --gpuParse 0|1 <the BAM records found, filtered and parsed there as well, default 0; 1 implies --gpuInflate 1>, --gpuGroup 0|1 <the records grouped by read name there as well, default 0; 1 implies --gpuParse 1>, --gpuSort 0|1 <the units put into read-name order there as well, default 0; 1 implies --gpuGroup 1>, --gpuFill 0|1 <the sample laid out and its windows filled there as well, default 0; 1 implies --gpuSort 1>, --gpuFillWide 0|1 <units with a mate of 17 to 4096 alignments filled there as well, default 0; 1 implies --gpuFill 1>, --verifyCRC 0|1 <the CRC-32 of every BGZF block checked against its inflated bytes, on the GPU where they are inflated there, default 0>, --batchPairs <units per GPU batch>, --rngSeed <base of the end-cell draws>,
 // --loci A,B,... (default: the reference's 17 loci, hla/HLATyper.cpp:42).  Several samples in one call (BASELINE config 4): comma-separated lists of
 // equal length in --sampleID, --outputDirectory, --FASTQ1, --FASTQ2 (--FASTQU); sample i runs on device i % #devices, all samples side by side.
 // Not rebuilt: the --BAM entry (the Perl driver never uses it: it extracts reads itself and passes FASTQ files), read simulation /
@@ -250,6 +250,8 @@ int action_HLA_one(const std::map<std::string, std::string>& arguments, const st
     if(arguments.count("gpuSort") && std::atoi(arguments.at("gpuSort").c_str()) != 0) BAMprocessor.set_gpu_sort(true);
     // --gpuFill 1: the decoder's layout and fill run there as well (HLALA_SEEDS_GPU_FILL); it implies --gpuSort 1
     if(arguments.count("gpuFill") && std::atoi(arguments.at("gpuFill").c_str()) != 0) BAMprocessor.set_gpu_fill(true);
+    // --gpuFillWide 1: the units with a mate beyond 16 alignments are laid out and filled there as well (HLALA_SEEDS_GPU_FILL_WIDE); it implies --gpuFill 1
+    if(arguments.count("gpuFillWide") && std::atoi(arguments.at("gpuFillWide").c_str()) != 0) BAMprocessor.set_gpu_fill_wide(true);
     // --verifyCRC 1: the CRC-32 of every BGZF block is compared with that of its inflated bytes (HLALA_SEEDS_VERIFY_CRC), on the GPU where the blocks are inflated there
     BAMprocessor.set_verify_crc(arguments.count("verifyCRC") && std::atoi(arguments.at("verifyCRC").c_str()) != 0);
     const double loadSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - tStart).count();
@@ -276,6 +278,8 @@ int action_HLA_one(const std::map<std::string, std::string>& arguments, const st
                                           << (BAMprocessor.sort_counts[2] ? " (the whole sample ordered by the host)" : "") << "\n" << std::flush;
     if(BAMprocessor.gpu_fill()) std::cout << "BAM fill: " << BAMprocessor.fill_counts[0] << " units filled on the GPU, " << BAMprocessor.fill_counts[1] << " units filled by the host"
                                           << (BAMprocessor.fill_counts[2] ? " (the whole sample filled by the host)" : "") << "\n" << std::flush;
+    if(BAMprocessor.gpu_fill_wide()) std::cout << "BAM wide fill: " << BAMprocessor.fill_wide_counts[0] << " wide units filled on the GPU, " << BAMprocessor.fill_wide_counts[1]
+                                               << " units beyond " << HLALA_BAM_FILL_WIDE_MAX << " alignments on a mate left to the host, longest mate " << BAMprocessor.fill_wide_counts[2] << "\n" << std::flush;
     if(BAMprocessor.verify_crc()) std::cout << "BGZF CRC-32: " << BAMprocessor.crc_counts[0] << " blocks verified on the GPU, " << BAMprocessor.crc_counts[1] << " on the host\n" << std::flush;
     if(!longReads.length() && !borrowed) std::cout << "Insert size: mean " << BAMprocessor.IS_mean << ", sd " << BAMprocessor.IS_sd << "\n" << std::flush;
     // the G-group table is looked up in the working directory, as the reference does (hla/HLATyper.cpp:4160-4166; HLA-LA.pl chdirs to the source directory)

@@ -359,7 +359,7 @@ public:
         // (the decoder needs the reference intervals only: it starts while the graph directory may still be reading its graph and translation tables)
         tdec.start([&]() {
             // (the bases stay 4-bit packed as the BAM records hold them: a copy instead of an unpacking pass here, half the bytes to upload, unpacked on the device)
-            const int32_t seedFlags = (std::getenv("HLALA_SEEDS_ASCII") ? 0 : HLALA_SEEDS_PACKED) | (inflater.f && gpu_parse_ ? HLALA_SEEDS_GPU_PARSE : 0) | (inflater.f && gpu_parse_ && gpu_group_ ? HLALA_SEEDS_GPU_GROUP : 0) | (inflater.f && gpu_parse_ && gpu_group_ && gpu_sort_ ? HLALA_SEEDS_GPU_SORT : 0) | (inflater.f && gpu_parse_ && gpu_group_ && gpu_sort_ && gpu_fill_ ? HLALA_SEEDS_GPU_FILL : 0) | (verify_crc_ ? HLALA_SEEDS_VERIFY_CRC : 0);          // (HLALA_SEEDS_ASCII=1: the decoder unpacks the bases on the host, as before round 4 -- for A/B runs)
+            const int32_t seedFlags = (std::getenv("HLALA_SEEDS_ASCII") ? 0 : HLALA_SEEDS_PACKED) | (inflater.f && gpu_parse_ ? HLALA_SEEDS_GPU_PARSE : 0) | (inflater.f && gpu_parse_ && gpu_group_ ? HLALA_SEEDS_GPU_GROUP : 0) | (inflater.f && gpu_parse_ && gpu_group_ && gpu_sort_ ? HLALA_SEEDS_GPU_SORT : 0) | (inflater.f && gpu_parse_ && gpu_group_ && gpu_sort_ && gpu_fill_ ? HLALA_SEEDS_GPU_FILL : 0) | (inflater.f && gpu_parse_ && gpu_group_ && gpu_sort_ && gpu_fill_ && gpu_fill_wide_ ? HLALA_SEEDS_GPU_FILL_WIDE : 0) | (verify_crc_ ? HLALA_SEEDS_VERIFY_CRC : 0);          // (HLALA_SEEDS_ASCII=1: the decoder unpacks the bases on the host, as before round 4 -- for A/B runs)
             try {
                 const int rc = inflater.f ? hlala_bam_extract_seeds_gpu(inflater.f, BAM.c_str(), (int32_t)intervals_.size(), intervals_.data(), longReads ? 1 : 0, threads_, seedFlags, &seeds_)
                                           : hlala_bam_extract_seeds_opt(BAM.c_str(), (int32_t)intervals_.size(), intervals_.data(), longReads ? 1 : 0, threads_, seedFlags, &seeds_);
@@ -390,6 +390,7 @@ public:
         hlala_seed_batch_group_counts(seeds_, group_counts);
         hlala_seed_batch_sort_counts(seeds_, sort_counts);
         hlala_seed_batch_fill_counts(seeds_, fill_counts);
+        hlala_seed_batch_fill_wide_counts(seeds_, fill_wide_counts);
         n_units = hlala_seed_batch_units(seeds_); longReadsMode = longReads; BAM_ = BAM;
         batchPairs_ = batchPairs > 0 ? batchPairs : (n_units > 0 ? (n_units > 0x7FFFFFFF ? 0x7FFFFFFF : (int32_t)n_units) : 1);
         live_.assign((size_t)n_batches(), nullptr); aligned_.assign((size_t)n_batches(), 0);
@@ -405,11 +406,14 @@ public:
     bool gpu_sort() const { return gpu_sort_; }
     void set_gpu_fill(bool on) { gpu_fill_ = on; if(on) set_gpu_sort(true); }          // before openBAM; HLALA_SEEDS_GPU_FILL: the sample laid out and its windows filled on the GPU; it works on what the stages before leave there
     bool gpu_fill() const { return gpu_fill_; }
+    void set_gpu_fill_wide(bool on) { gpu_fill_wide_ = on; if(on) set_gpu_fill(true); }   // before openBAM; HLALA_SEEDS_GPU_FILL_WIDE: units with a mate of 17 to HLALA_BAM_FILL_WIDE_MAX alignments are filled on the GPU as well
+    bool gpu_fill_wide() const { return gpu_fill_wide_; }
     void set_verify_crc(bool on) { verify_crc_ = on; }         // before openBAM; HLALA_SEEDS_VERIFY_CRC: the CRC-32 of every BGZF block is checked, on whichever path inflates it
     bool verify_crc() const { return verify_crc_; }
     int64_t crc_counts[3] = {0, 0, 0};                         // hlala_seed_batch_crc_counts: blocks verified on the GPU, on the host, reported as mismatching by the GPU and checked again on the host
     int64_t group_counts[3] = {0, 0, 0};                       // hlala_seed_batch_group_counts: records grouped on the GPU, collided hash runs the host regrouped, 1 = the host grouped the whole sample
     int64_t sort_counts[3] = {0, 0, 0};                        // hlala_seed_batch_sort_counts: units ordered on the GPU, units of collided runs the host merged in, 1 = the host ordered the whole sample
+    int64_t fill_wide_counts[3] = {0, 0, 0};                   // hlala_seed_batch_fill_wide_counts: wide units the GPU filled, units beyond HLALA_BAM_FILL_WIDE_MAX left to the host, the longest mate seen
     int64_t fill_counts[3] = {0, 0, 0};                        // hlala_seed_batch_fill_counts: units the GPU fills, host units, 1 = the host laid out and filled the whole sample
     int64_t parse_counts[3] = {0, 0, 0};                       // hlala_seed_batch_parse_counts: records scanned on the GPU, rounds scanned there, rounds parsed again on the host
     int64_t inflate_counts[3] = {0, 0, 0};                     // hlala_seed_batch_inflate_counts of the sample: blocks inflated on the GPU, rejected there and redone on the host, host only
@@ -493,7 +497,7 @@ private:
         if(hlala_seed_batch_window(seeds_, u0, n, &in) != HLALA_OK) throw std::runtime_error(std::string("alignReads: ") + hlala_bam_last_error());
     }
     std::shared_ptr<GraphDirectory> gdir_;
-    std::string graphDir_; bool extended_; int max_columns_; uint32_t rng_seed_; std::vector<int> devices_; int threads_; bool gpu_inflate_ = false, gpu_parse_ = false, gpu_group_ = false, gpu_sort_ = false, gpu_fill_ = false, verify_crc_ = false;
+    std::string graphDir_; bool extended_; int max_columns_; uint32_t rng_seed_; std::vector<int> devices_; int threads_; bool gpu_inflate_ = false, gpu_parse_ = false, gpu_group_ = false, gpu_sort_ = false, gpu_fill_ = false, gpu_fill_wide_ = false, verify_crc_ = false;
     hlala_graph_file* graph_ = nullptr; hlala_contigs_file* contigs_ = nullptr; const std::vector<hlala_bam_interval>& intervals_;      // owned by gdir_
     hlala_seed_batch* seeds_ = nullptr; std::vector<hlala_ctx*> ctxs_; hlala_comm* comm_ = nullptr; int tail_pool_ = 1; int64_t pair_overflow_ = 0; bool owns_ctx_ = true; std::string BAM_;
     int32_t batchPairs_ = 1; std::vector<hlala_batch*> live_; std::vector<char> aligned_;       // aligned_[bi]: hlala_align_batch has been queued for live_[bi]

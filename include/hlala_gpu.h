@@ -707,6 +707,30 @@ int  hlala_seed_batch_fill_counts(const hlala_seed_batch* s, int64_t counts[3]);
 int  hlala_seed_batch_fill_ms(const hlala_seed_batch* s, double ms[5]);
 
 /* ------------------------------------------------------------------------------------------
+ * Mates beyond HLALA_BAM_FILL_MAX_MATE alignments on the device (opt-in; csrc/bam_fill_wide_core.h is the rule).  Beyond 16 elements libstdc++'s std::sort is an
+ * introsort, which is not stable: the order it leaves among equal scores has no closed form, so the device runs its steps (median of three, the two-cursor
+ * partition, heap sort once 2 * floor(log2 n) cuts are spent, a final insertion sort) and reverses.  A unit is WIDE when unit_count > 32 or a mate has more than 16
+ * alignments; both reads of a wide unit take the wide path, every other unit the path above, untouched.  k_fil_wide_rank: a wavefront per wide read, the mate's
+ * scores and places in LDS, the sort on lane 0, the sorted descriptors and the prefix of their CIGAR counts into scratch arrays that exist only when the sample has
+ * wide units; k_fil_wide_src scatters them behind the scans.  The window kernels and hlala_batch_create_from_fill follow chain_src and do not change: a wide unit is
+ * no host unit, nothing of it is staged.
+ * ---------------------------------------------------------------------------------------- */
+#define HLALA_BAM_FILL_WIDE_MAX 4096
+/* hlala_bam_fill_create with mates of up to max_mate alignments, max_mate in (HLALA_BAM_FILL_MAX_MATE, HLALA_BAM_FILL_WIDE_MAX] (HLALA_E_ARG otherwise, and for a
+ * filled unit with a mate beyond max_mate).  The handle is an hlala_bam_fill like any other.  For a sample without wide units it does what hlala_bam_fill_create does. */
+int  hlala_bam_fill_create_wide(hlala_inflater* inf, const hlala_bam_fill_in* in, int32_t max_mate, int64_t* read_off, int64_t* chain_off, int64_t* cigar_count,
+                                int64_t* name_off, hlala_bam_fill** out, hlala_bam_fill_stats* stats);
+/* out[4]: wide units, wide reads, the longest mate among them, device microseconds of k_fil_wide_rank + k_fil_wide_src (which ms_rank and ms_src of the create call's
+ * stats include); zeros for a handle of hlala_bam_fill_create */
+int  hlala_bam_fill_wide_stats(const hlala_bam_fill* h, int64_t out[4]);
+/* Flag of hlala_bam_extract_seeds_gpu (HLALA_E_ARG without HLALA_SEEDS_GPU_FILL): the fill state takes the wide units as well.  The host keeps for itself only the
+ * units it split out of collided hash runs and the units with a mate beyond HLALA_BAM_FILL_WIDE_MAX.  Where the library has no wide path or it answers "not
+ * available", the decoder marks its host units as with HLALA_SEEDS_GPU_FILL alone.  The sample is the same to the byte. */
+#define HLALA_SEEDS_GPU_FILL_WIDE 64
+/* counts[3]: wide units the device filled, units beyond HLALA_BAM_FILL_WIDE_MAX left to the host, the longest mate seen among both; (0, 0, 0) without the flag */
+int  hlala_seed_batch_fill_wide_counts(const hlala_seed_batch* s, int64_t counts[3]);
+
+/* ------------------------------------------------------------------------------------------
  * A batch from a device-filled window without leaving the GPU (opt-in): the device form of hlala_batch_create / _unpaired for a window of a fill state
  * (csrc/kernel_bamresident.hip; the rules are csrc/bam_resident_core.h, which the host runs as a model).  hlala_bam_fill_window brings a window down, the caller fills
  * its host units, hlala_batch_create checks and rebases it on the host and sends it up again.  Here k_fil_chain, k_fil_cigar and k_fil_bases write into the batch's own
@@ -1084,7 +1108,8 @@ int  hlala_abi_sizeof(const char* struct_name);
  * Symbols that are purely additive no longer change it (hlala_set_pair_overflow; hlala_bgzf_inflate_crc, HLALA_SEEDS_VERIFY_CRC, hlala_seed_batch_crc_counts;
  * hlala_bam_group / _rounds, HLALA_SEEDS_GPU_GROUP, hlala_seed_batch_group_counts; hlala_bam_name_order, HLALA_SEEDS_GPU_SORT, hlala_seed_batch_sort_counts;
  * hlala_bam_fill_create / _window / _destroy / _last_error, HLALA_SEEDS_GPU_FILL, hlala_seed_batch_fill_counts;
- * hlala_batch_create_from_fill, hlala_debug_batch_inputs): a caller
+ * hlala_batch_create_from_fill, hlala_debug_batch_inputs;
+ * hlala_bam_fill_create_wide, hlala_bam_fill_wide_stats, HLALA_SEEDS_GPU_FILL_WIDE, hlala_seed_batch_fill_wide_counts): a caller
  * detects them by the presence of the symbol.  A caller compares
  * hlala_abi_version() with the HLALA_ABI_VERSION it was compiled against and refuses to run on a mismatch (hla-la_amd/__init__.py and
  * hla-la_amd/host/hlala_host.hpp do). */

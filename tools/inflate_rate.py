@@ -20,7 +20,15 @@ phase and wall clock are read against the fourth path's of the same call, and hl
 time per pass and the rounds it took.
 The sixth path (its output is meant for profiles/bam_fill_gpu.txt): all of the fifth plus HLALA_SEEDS_GPU_FILL in the same alternation; its layout phase (layout + fill with
 HLALA_BAM_EAGER=1, which the caller sets for both) and wall clock are read against the fifth path's of the same call; every run prints the units the device filled and the
-host units, the device time of the window passes (hlala_seed_batch_fill_ms) and the bytes moved each way.  --paths a,b restricts the alternation to the named paths."""
+host units, the device time of the window passes (hlala_seed_batch_fill_ms) and the bytes moved each way.  --paths a,b restricts the alternation to the named paths.
+--wide-units N (its output is meant for profiles/bam_fill_wide_gpu.txt): one synthetic fill state of N pairs in which --wide-share of the units carry 17 to 200 alignments
+on mate 0 (uniform; the scores drawn from four values, 70 % of them the same one), laid out by hlala_bam_fill_create -- the wide units handed in as host units, which is
+what the decoder does with them without HLALA_SEEDS_GPU_FILL_WIDE -- and by hlala_bam_fill_create_wide, alternating; then every window through
+hlala_batch_create_from_fill on both states, the first with the host units' ranges staged, the second with nothing to stage.
+--wide-bam-pairs N (the same file): a BAM of N pairs written here, not by the generators above -- 2 x 100 bases on one reference, --wide-share of the pairs with 17 to 200
+alignments on mate 0 (uniform; AS 40 with probability 0.7, else 60 / 77 / 90), every other mate with 1 to 3, one primary per mate, records shuffled -- decoded with
+HLALA_SEEDS_GPU_FILL alone and with HLALA_SEEDS_GPU_FILL | HLALA_SEEDS_GPU_FILL_WIDE, alternating (the caller sets HLALA_BAM_EAGER=1 so that the fill lies inside the decode):
+host units, the layout + fill phase and the wall clock of each."""
 import argparse
 import os
 import sys
@@ -227,6 +235,144 @@ def resident_alone(P, lib, args):
     h.close(); inf.close()
 
 
+def wide_state(P, N, share, n_contigs, L=100, NAME=9):
+    """the descriptors of --wide-units: (recs, data, unit_first with every unit filled, unit_first with the wide units as host units, unit_count, their host sizes, wide)"""
+    rng = np.random.default_rng(17)
+    wide = rng.random(N) < share
+    c = np.stack([np.where(wide, rng.integers(17, 201, N), rng.integers(1, 4, N)), rng.integers(1, 4, N)], axis=1).astype(np.int64)        # alignments per unit and mate
+    per = c.reshape(-1); n = int(per.sum())
+    start = np.concatenate([[0], np.cumsum(per)])
+    mate_of = np.repeat(np.arange(2 * N), per); j = np.arange(n) - start[mate_of]                  # the read and the place in it of every record
+    prim = j == rng.integers(0, 1 << 30, 2 * N)[mate_of] % per[mate_of]
+    body = np.where(prim, 32 + NAME + 1 + 4 + (L + 1) // 2 + L, 32 + NAME + 1 + 4); body = (body + 7) & ~7
+    rec_off = np.concatenate([[0], np.cumsum(body)]).astype(np.uint64)
+    data = rng.integers(0, 64, int(rec_off[-1]), dtype=np.uint8)
+    recs = np.zeros(n, P.BAM_REC_DTYPE)
+    recs["order"] = np.arange(n); recs["rec_off"] = rec_off[:-1]; recs["contig"] = rng.integers(0, n_contigs, n); recs["pos"] = rng.integers(0, 3000, n)
+    recs["as"] = rng.choice(np.array([40, 40, 40, 40, 40, 40, 40, 60, 77, 90]), n); recs["l_seq"] = np.where(prim, L, 0); recs["n_cigar"] = 1; recs["nameLen"] = NAME
+    recs["which"] = mate_of % 2; recs["flags"] = np.where(prim, 2, 0).astype(np.uint8) | rng.integers(0, 2, n).astype(np.uint8); recs["l_read_name"] = NAME + 1
+    first_all = start[0:2 * N:2].astype(np.uint32); count = (c[:, 0] + c[:, 1]).astype(np.uint32)
+    first_narrow = np.where(wide, P.BAM_FILL_HOST, first_all).astype(np.uint32)
+    hs = np.stack([np.full(N, L), c[:, 0], c[:, 0], np.full(N, L), c[:, 1], c[:, 1], np.full(N, NAME + 1)], axis=1)[wide].astype(np.int64).reshape(-1)
+    return recs, data, first_all, first_narrow, count, hs, wide
+
+
+def wide_alone(P, lib, args):
+    """--wide-units N: see the module docstring.  The narrow state's host units are 'filled' from the wide state's download of the same window -- the bytes the host's own
+    sort and fill would leave; what that host fill costs is NOT in these figures."""
+    from tools import synth
+    N, share, Wn = args.wide_units, args.wide_share, args.resident_window
+    w = synth.make_world(seed=11, G=4000, k=1)
+    ctx = P.Context(w["graph"], w["contigs"], device=args.device)
+    inf = P.Inflater(lib, device=args.device, chunk_bytes=0)
+    recs, data, first_all, first_narrow, count, hs, wide = wide_state(P, N, share, int(w["contigs"]["n_contigs"]))
+    n = len(recs)
+    print("wide fill alone: %d pairs, %d of them wide (17 .. 200 alignments on mate 0, uniform; scores 40 with probability 0.7, else 60 / 77 / 90), %d descriptors, %.3f GB of record bytes; windows of %d units" % (
+        N, int(wide.sum()), n, data.size / 1e9, Wn))
+    fin_n, keep_n = P.bam_fill_in(recs, data, first_narrow, count, hs, False, True)
+    fin_w, keep_w = P.bam_fill_in(recs, data, first_all, count, np.zeros(0, np.int64), False, True)
+    lay = {"narrow": [], "wide": []}; dev = []
+    hn = hw = None
+    for run in range(args.runs + 1):
+        for path in ("narrow", "wide"):
+            rc, h, off, st = inf.bam_fill_create(fin_n, N, False, True) if path == "narrow" else inf.bam_fill_create_wide(fin_w, N, False, True)
+            assert rc == 0, inf.last_error()
+            if run:
+                lay[path].append((st.ms_wall, st.ms_rank + st.ms_host + st.ms_scan + st.ms_src))
+                if path == "wide":
+                    dev.append(h.wide_stats())
+            if run == args.runs:
+                if path == "narrow":
+                    hn, off_n = h, off
+                else:
+                    hw, off_w = h, off
+            else:
+                h.close()
+    assert all(np.array_equal(off_n[k], off_w[k]) for k in off_n), "the two layouts differ"
+    for path in ("narrow", "wide"):
+        v = [x[0] for x in lay[path]]; k = [x[1] for x in lay[path]]
+        print("layout (upload, passes, download of the offsets), %s state, host units %d: wall median %.2f ms, range %.2f .. %.2f of %d runs; of it layout kernels and scans on the device %.3f ms" % (
+            path, int(wide.sum()) if path == "narrow" else 0, float(np.median(v)), min(v), max(v), len(v), float(np.median(k))))
+    u = [x[3] for x in dev]
+    print("k_fil_wide_rank + k_fil_wide_src: median %.0f us, range %.0f .. %.0f of %d runs (%d wide units, %d wide reads, longest mate %d)" % ((float(np.median(u)), min(u), max(u), len(u)) + dev[0][:3]))
+    wins = [(a, min(Wn, N - a)) for a in range(0, N, Wn)]
+    host_slices = {}
+    for u0, k in wins:                                      # what the host would have filled: taken from the wide state, outside the timed part
+        rc, arrs, _ = hw.window(u0, k); assert rc == 0, hw.last_error()
+        host_slices[u0] = arrs
+    res = {"narrow": [], "wide": []}; moved = {}
+    for run in range(args.runs + 1):
+        for path, h in (("narrow", hn), ("wide", hw)):
+            total = 0.0; pieces = up = 0
+            for u0, k in wins:
+                t = time.perf_counter()
+                rc, b, rs = ctx.batch_from_fill(h, u0, k, host_slices[u0] if path == "narrow" and wide[u0:u0 + k].any() else None)
+                assert rc == 0, ctx.last_error()
+                total += time.perf_counter() - t
+                pieces += rs.n_pieces; up += rs.bytes_h2d
+                b.close()
+            if run:
+                res[path].append(total * 1e3); moved[path] = (pieces, up)
+    for path in ("narrow", "wide"):
+        v = res[path]
+        print("hlala_batch_create_from_fill, %s state, all %d windows: median %.1f ms, range %.1f .. %.1f of %d runs; %d pieces staged, %.3f GB up per run" % (
+            path, len(wins), float(np.median(v)), min(v), max(v), len(v), moved[path][0], moved[path][1] / 1e9))
+    hn.close(); hw.close(); inf.close()
+
+
+def wide_bam(P, lib, args):
+    """--wide-bam-pairs N: see the module docstring"""
+    import struct
+    import zlib
+    N, share = args.wide_bam_pairs, args.wide_share
+    rng = np.random.default_rng(23)
+    L = 100
+    wide = rng.random(N) < share
+    c0 = np.where(wide, rng.integers(17, 201, N), rng.integers(1, 4, N)); c1 = rng.integers(1, 4, N)
+    t0 = time.time()
+    seq = bytes(rng.integers(0, 256, (L + 1) // 2, dtype=np.uint8)) + bytes(rng.integers(2, 41, L, dtype=np.uint8).tolist())      # (one sequence for every primary: the fill copies it, whatever it holds)
+    cig = struct.pack("<I", (L << 4) | 0)
+    out = []
+    for u in range(N):
+        name = b"p%07d\0" % u
+        for mate, k in ((0, int(c0[u])), (1, int(c1[u]))):
+            prim = int(rng.integers(0, k)); AS = rng.choice((40, 40, 40, 40, 40, 40, 40, 60, 77, 90), k); pos = rng.integers(1000, 40000, k); rev = rng.integers(0, 2, k)
+            for j in range(k):
+                flag = 1 | (64 if mate == 0 else 128) | (16 if rev[j] else 0) | (0 if j == prim else 256)
+                body = struct.pack("<iiBBHHHiiii", 0, int(pos[j]), len(name), 60, 0, 1, flag, L, -1, -1, 0) + name + cig + seq + b"ASC" + bytes([int(AS[j])])
+                out.append(struct.pack("<i", len(body)) + body)
+    n_rec = len(out)
+    order = rng.permutation(n_rec)
+    raw = b"BAM\x01" + struct.pack("<ii", 0, 1) + struct.pack("<i", 5) + b"chr6\0" + struct.pack("<i", 50000) + b"".join(out[i] for i in order)
+    tmp = tempfile.mkdtemp(prefix="hlala_wide_bam_"); bam = os.path.join(tmp, "wide.bam")
+    with open(bam, "wb") as f:
+        for i in list(range(0, len(raw), 60000)) + [len(raw)]:
+            d = raw[i:i + 60000]
+            co = zlib.compressobj(1, zlib.DEFLATED, -15); comp = co.compress(d) + co.flush()
+            f.write(struct.pack("<BBBBIBBH", 31, 139, 8, 4, 0, 0, 255, 6) + b"BC" + struct.pack("<HH", 2, len(comp) + 25) + comp + struct.pack("<II", zlib.crc32(d) & 0xFFFFFFFF, len(d)))
+    print("wide BAM: %d pairs, %d of them wide (17 .. 200 alignments on mate 0, uniform; AS 40 with probability 0.7, else 60 / 77 / 90), %d records, %.3f GB inflated; written in %.1f s; HLALA_BAM_EAGER=%s" % (
+        N, int(wide.sum()), n_rec, len(raw) / 1e9, time.time() - t0, os.environ.get("HLALA_BAM_EAGER", "unset")))
+    intervals = [("chr6", 0, 49999, 0)]
+    inf = P.Inflater(lib, device=args.device, chunk_bytes=args.chunk_mb << 20)
+    base = P.SEEDS_PACKED | P.SEEDS_GPU_PARSE | P.SEEDS_GPU_GROUP | P.SEEDS_GPU_SORT | P.SEEDS_GPU_FILL
+    res = {"fill": [], "fill+wide": []}
+    for run in range(args.runs + 1):
+        for path, fl in (("fill", base), ("fill+wide", base | P.SEEDS_GPU_FILL_WIDE)):
+            t = time.time(); S = inf.bam_open_seeds(bam, intervals, threads=args.threads, flags=fl); wall = time.time() - t
+            tm = S.timing(); fc = S.fill_counts(); wc = S.fill_wide_counts(); fm = S.fill_ms(); units = S.n_units; S.close()
+            if run:
+                res[path].append((tm["layout"], wall, fc, wc, sum(fm[:4])))
+                print("%-10s wall %.3f s  layout + fill %.4f s  units %d: filled on the GPU %d, host units %d, whole sample by the host %d; wide units on the GPU %d, beyond the cap %d, longest mate %d; window kernels %.3f ms" % (
+                    path, wall, tm["layout"], units, fc[0], fc[1], fc[2], wc[0], wc[1], wc[2], sum(fm[:4])))
+    for path in ("fill", "fill+wide"):
+        for j, what in ((0, "layout + fill phase"), (1, "decode, wall")):
+            v = [x[j] for x in res[path]]
+            print("%s, %s: median %.4f s, range %.4f .. %.4f of %d runs; host units %d" % (what, path, float(np.median(v)), min(v), max(v), len(v), res[path][0][2][1]))
+    inf.close()
+    import shutil
+    shutil.rmtree(tmp, ignore_errors=True)
+
+
 def out_bytes(off, r0, r1):
     """the bytes hlala_batch_create uploads for reads [r0, r1) of a packed sample: packed bases, qualities, 17 bytes per chain + its CIGAR, the 32-bit offset arrays"""
     nb = int(off["read_off"][r1] - off["read_off"][r0]); nc = int(off["chain_off"][r1] - off["chain_off"][r0]); ng = int(off["cigar_count"][r1] - off["cigar_count"][r0])
@@ -237,6 +383,9 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--resident-units", type=int, default=0, help="only hlala_batch_create_from_fill against hlala_bam_fill_window + hlala_batch_create, on a synthetic fill state of this many pairs")
     ap.add_argument("--resident-window", type=int, default=262144, help="units per window of --resident-units")
+    ap.add_argument("--wide-units", type=int, default=0, help="only hlala_bam_fill_create_wide against hlala_bam_fill_create with the wide units as host units, on a synthetic fill state of this many pairs")
+    ap.add_argument("--wide-bam-pairs", type=int, default=0, help="only the decoder with HLALA_SEEDS_GPU_FILL against HLALA_SEEDS_GPU_FILL | HLALA_SEEDS_GPU_FILL_WIDE on a BAM of this many pairs written here")
+    ap.add_argument("--wide-share", type=float, default=0.05, help="share of the units of --wide-units / --wide-bam-pairs that carry 17 to 200 alignments on mate 0")
     ap.add_argument("--pairs", type=int, default=1 << 20, help="pairs per generated chunk of the sample")
     ap.add_argument("--levels", type=int, default=5_000_000, help="levels of the Graph M world (bench.py --levels)")
     ap.add_argument("--min-inflated-gb", type=float, default=1.0, help="chunks are added until the BAM holds this much inflated")
@@ -258,6 +407,12 @@ def main():
     lib.hlala_bam_inflate_engine.restype = __import__("ctypes").c_char_p
     if args.resident_units > 0:
         resident_alone(P, lib, args)
+        return
+    if args.wide_units > 0:
+        wide_alone(P, lib, args)
+        return
+    if args.wide_bam_pairs > 0:
+        wide_bam(P, lib, args)
         return
     t0 = time.time()
     w = synth.make_world_m(seed=2, n_levels=args.levels)
