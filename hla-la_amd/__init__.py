@@ -572,10 +572,36 @@ def bam_scan_in(n_ref, ref_intervals, intervals, long_read_mode=False, hash_mask
 
 INFLATE_MIN_CHUNK, INFLATE_DEFAULT_CHUNK = 1 << 17, 32 << 20          # HLALA_INFLATE_MIN_CHUNK, HLALA_INFLATE_DEFAULT_CHUNK
 INFLATE_STATUS = ("ok", "reserved block type", "stored LEN != ~NLEN", "bad code lengths", "invalid symbol", "distance too far", "input exhausted", "output size", "crc mismatch")
+INFLATE_KERNEL_HBM, INFLATE_KERNEL_LDS = 0, 1                          # HLALA_INFLATE_KERNEL_*: k_bgzf_inflate (the default), k_bgzf_inflate_lds
+HOST_LIB_PATH = os.path.join(_HERE, "libhlala_host.so")               # the host models of the kernels (csrc/host_check.cpp); needs no device
+
+
+def _host_lib():
+    if not os.path.exists(HOST_LIB_PATH):
+        raise HlalaError(f"{HOST_LIB_PATH} has not been built (make -C hla-la_amd/csrc)")
+    h = C.CDLL(HOST_LIB_PATH)
+    h.hlala_host_inflate_lds_model.argtypes = [C.c_char_p, C.c_uint32, C.c_void_p, C.c_uint32]
+    h.hlala_host_inflate_lds_params.argtypes = [c_i32p, c_i32p, c_i32p]; h.hlala_host_inflate_lds_params.restype = None
+    return h
+
+
+def host_inflate_lds_params():
+    """hlala_host_inflate_lds_params: (R, B, batch_tokens) of k_bgzf_inflate_lds -- bytes of the ring, most bytes and most tokens of one batch"""
+    r, b, t = C.c_int32(), C.c_int32(), C.c_int32()
+    _host_lib().hlala_host_inflate_lds_params(C.byref(r), C.byref(b), C.byref(t))
+    return r.value, b.value, t.value
+
+
+def host_inflate_lds_model(stream, isize):
+    """hlala_host_inflate_lds_model: (HLALA_INFLATE_* status, the isize bytes) of one raw DEFLATE stream through the serial model of k_bgzf_inflate_lds"""
+    out = np.zeros(int(isize) + 1, np.uint8)
+    st = _host_lib().hlala_host_inflate_lds_model(bytes(stream), len(stream), out.ctypes.data, int(isize))
+    return int(st), out[:int(isize)].tobytes()
 
 
 class Inflater:
-    """hlala_inflater: BGZF blocks (raw DEFLATE streams) inflated on the GPU, one wavefront per block.  Its own light handle: no graph, no Context."""
+    """hlala_inflater: BGZF blocks (raw DEFLATE streams) inflated on the GPU, one wavefront per block (set_kernel(INFLATE_KERNEL_LDS): one workgroup of two per block,
+    the history in LDS).  Its own light handle: no graph, no Context."""
 
     def __init__(self, lib=None, device=0, chunk_bytes=0):
         self.lib = lib or load_library(); self.h = None
@@ -592,6 +618,18 @@ class Inflater:
         if rc != 0:
             raise HlalaError(f"hlala_inflater_create failed ({rc}): {lib.hlala_inflater_last_error(None).decode(errors='replace')}")
         self.h = h
+        lib.hlala_inflater_set_kernel.argtypes = [C.c_void_p, C.c_int32]
+        lib.hlala_inflater_get_kernel.argtypes = [C.c_void_p]; lib.hlala_inflater_get_kernel.restype = C.c_int32
+
+    def set_kernel(self, kind):
+        """hlala_inflater_set_kernel: INFLATE_KERNEL_HBM or _LDS for every later call on this handle; an unknown kind raises and leaves the choice as it was"""
+        rc = self.lib.hlala_inflater_set_kernel(self.h, int(kind))
+        if rc != 0:
+            raise HlalaError(f"hlala_inflater_set_kernel failed ({rc}): {self.lib.hlala_inflater_last_error(self.h).decode(errors='replace')}")
+
+    @property
+    def kernel(self):
+        return int(self.lib.hlala_inflater_get_kernel(self.h))
 
     def inflate(self, comp, blocks, out, crc=None, want_crc=False):
         """comp, out: contiguous uint8 arrays; blocks = [(coff, clen, isize, uoff)].  Writes the accepted blocks into `out`; returns (int32 status per block, InflateStats).
@@ -1088,7 +1126,7 @@ EXPORTED_SYMBOLS = [
     "hlala_typer_open", "hlala_typer_close", "hlala_typer_last_error", "hlala_typer_n_levels", "hlala_typer_level_name", "hlala_typer_level_of", "hlala_typer_n_genes",
     "hlala_typer_gene", "hlala_typer_load_g_groups", "hlala_typer_g_translate", "hlala_typer_locus", "hlala_locus_free", "hlala_locus_get", "hlala_locus_cluster_id", "hlala_locus_type_cluster",
     "hlala_inflater_create", "hlala_inflater_destroy", "hlala_inflater_last_error", "hlala_bgzf_inflate", "hlala_bam_extract_seeds_gpu", "hlala_seed_batch_inflate_counts",
-    "hlala_bgzf_inflate_crc", "hlala_seed_batch_crc_counts",
+    "hlala_bgzf_inflate_crc", "hlala_seed_batch_crc_counts", "hlala_inflater_set_kernel", "hlala_inflater_get_kernel",
     "hlala_bam_scan", "hlala_bam_scan_status_text", "hlala_seed_batch_parse_counts", "hlala_seed_batch_transfer_bytes",
     "hlala_bam_group", "hlala_bam_group_rounds", "hlala_seed_batch_group_counts",
     "hlala_bam_name_order", "hlala_seed_batch_sort_counts",

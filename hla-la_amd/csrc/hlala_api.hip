@@ -31,6 +31,7 @@
 #include "kernel_kmer.hip"
 #include "kernel_dp_band.hip"
 #include "kernel_inflate.hip"
+#include "kernel_inflate_lds.hip"
 #include "kernel_crc32.hip"
 #include "kernel_bamscan.hip"
 #include "kernel_bamgroup.hip"
@@ -2402,6 +2403,7 @@ struct NameOrderState { ScanBuf buf[NAM_NBUF]; hipEvent_t ev[NAM_NEV]{}; bool ev
 struct FillKeep { ScanBuf recs, bytes; int64_t n = 0; uint64_t nBytes = 0; bool ok = false; };
 struct hlala_inflater {
     int device = 0; size_t chunk = 0, outCap = 0; int64_t maxBlocks = 0;
+    int32_t kernel = HLALA_INFLATE_KERNEL_HBM;      // hlala_inflater_set_kernel: read at the one launch site of inflate_run
     InflateSlot slot[3];
     ScanBuf scan[SCAN_NBUF]; hipEvent_t scanEv[SCAN_NEV]{}; bool scanEvReady = false;
     size_t roundBytes = 0;          // bytes of the decoder's last round in scan[SCAN_DATA] (hlala_host::bam_scan_round: their tail is the next round's carry)
@@ -2413,6 +2415,13 @@ struct hlala_inflater {
 static thread_local std::string g_inflater_create_error;
 
 extern "C" const char* hlala_inflater_last_error(const hlala_inflater* f) { return f ? f->err.c_str() : g_inflater_create_error.c_str(); }
+extern "C" int hlala_inflater_set_kernel(hlala_inflater* f, int32_t kind)
+{
+    if(!f || (kind != HLALA_INFLATE_KERNEL_HBM && kind != HLALA_INFLATE_KERNEL_LDS)) { if(f) f->err = "hlala_inflater_set_kernel: unknown kind " + std::to_string(kind); return HLALA_E_ARG; }
+    f->kernel = kind;
+    return HLALA_OK;
+}
+extern "C" int32_t hlala_inflater_get_kernel(const hlala_inflater* f) { return f ? f->kernel : -1; }
 extern "C" void hlala_inflater_destroy(hlala_inflater* f)
 {
     if(!f) return;
@@ -2552,7 +2561,12 @@ static int inflate_run(hlala_inflater* f, const uint8_t* comp, size_t comp_bytes
         if(e == hipSuccess) e = hipMemcpyAsync(s.dDesc, s.hDesc, (size_t)cnt * sizeof(hlala_bgzf_block), hipMemcpyHostToDevice, s.stream);
         if(e == hipSuccess && crcExpect) e = hipMemcpyAsync(s.dCrcIn, s.hCrcIn, (size_t)cnt * sizeof(uint32_t), hipMemcpyHostToDevice, s.stream);
         if(e == hipSuccess) e = hipEventRecord(s.ev[1], s.stream);
-        if(e == hipSuccess) { hipLaunchKernelGGL(k_bgzf_inflate, dim3((unsigned)cnt), dim3(64), 0, s.stream, (const uint8_t*)s.dComp, (const hlala_bgzf_block*)s.dDesc, (int)cnt, dOutBase ? dOutBase + blocks[s.first].uoff : s.dOut, s.dStatus); e = hipGetLastError(); }
+        if(e == hipSuccess) {
+            uint8_t* dst = dOutBase ? dOutBase + blocks[s.first].uoff : s.dOut;
+            if(f->kernel == HLALA_INFLATE_KERNEL_LDS) hipLaunchKernelGGL(k_bgzf_inflate_lds, dim3((unsigned)cnt), dim3(64 * INF_LDS_WAVES), 0, s.stream, (const uint8_t*)s.dComp, (const hlala_bgzf_block*)s.dDesc, (int)cnt, dst, s.dStatus);
+            else hipLaunchKernelGGL(k_bgzf_inflate, dim3((unsigned)cnt), dim3(64), 0, s.stream, (const uint8_t*)s.dComp, (const hlala_bgzf_block*)s.dDesc, (int)cnt, dst, s.dStatus);
+            e = hipGetLastError();
+        }
         if(e == hipSuccess) e = hipEventRecord(s.ev[2], s.stream);
         if(e == hipSuccess && wantCrc) {
             hipLaunchKernelGGL(k_bgzf_crc32, dim3((unsigned)cnt), dim3(64), 0, s.stream, (const uint8_t*)(dOutBase ? dOutBase + blocks[s.first].uoff : s.dOut), (const hlala_bgzf_block*)s.dDesc, (int)cnt, s.dStatus,

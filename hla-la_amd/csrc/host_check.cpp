@@ -5,6 +5,7 @@
 
 #include "flat_graph.hpp"
 #include "inflate_core.h"
+#include "inflate_lds_model.h"
 #include "crc32_core.h"
 #include "bam_scan_model.h"
 #include "bam_group_model.h"
@@ -101,6 +102,19 @@ int hlala_host_inflate_model(const uint8_t* comp, uint32_t clen, uint8_t* out, u
         if(final) return produced == isize ? HLALA_INFLATE_OK : HLALA_INFLATE_OUTPUT_SIZE;
     }
 }
+// k_bgzf_inflate_lds (kernel_inflate_lds.hip) run serially over the same core (inflate_lds_model.h): same contract as hlala_host_inflate_model; _rounds also says how
+// many rounds (workgroup barriers) the kernel takes for the stream.
+int hlala_host_inflate_lds_model(const uint8_t* comp, uint32_t clen, uint8_t* out, uint32_t isize) { return hlala_inflate::lds_model(comp, clen, out, isize, nullptr); }
+int hlala_host_inflate_lds_rounds(const uint8_t* comp, uint32_t clen, uint8_t* out, uint32_t isize, int32_t* rounds) { return hlala_inflate::lds_model(comp, clen, out, isize, rounds); }
+// the constants the vectors of tests/inflate_lds_vectors.py are built from: bytes of the ring, most bytes and most tokens of one batch
+void hlala_host_inflate_lds_params(int32_t* R, int32_t* B, int32_t* batch_tokens)
+{
+    if(R) *R = (int32_t)hlala_inflate::LDS_RING;
+    if(B) *B = (int32_t)hlala_inflate::LDS_BATCH_BYTES;
+    if(batch_tokens) *batch_tokens = (int32_t)hlala_inflate::LDS_BATCH_TOKENS;
+}
+// token() and token_w() side by side along the first DEFLATE block of comp (inflate_lds_model.h: lds_token_steps)
+int hlala_host_inflate_lds_token_steps(const uint8_t* comp, uint32_t clen, int32_t cap, uint32_t* tok, int32_t* rc, uint64_t* bits) { return hlala_inflate::lds_token_steps(comp, clen, cap, tok, rc, bits); }
 // The CRC-32 split of the device kernel (kernel_crc32.hip; crc32_core.h) run serially, the 64 lanes in a loop: the CRC-32 (RFC 1952) of data[0, n).  Reads nothing else.
 uint32_t hlala_host_crc32_model(const uint8_t* data, uint32_t n)
 {

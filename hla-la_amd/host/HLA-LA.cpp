@@ -10,7 +10,7 @@
 // terminate), this program prints the message to stderr and exits with a non-zero status -- HLA-LA.pl treats any non-zero status as
 // failure (:567-570).  Extra, optional arguments of this program: --devices <gpu,gpu,...> (or --device <gpu>): the batches of the sample are
 // dealt round-robin to one context per listed GPU (a GPU may be listed twice: two contexts on it), results do not depend on the list;
-// --decodeSlots <samples that decode at one time, default CPUs / 16>, --tailPool <k: GPU batches per launch of the widest DP classes>, --pairOverflow <MiB of device scratch for pairs beyond the pairing capacities, default 0: such pairs are refused>, --decodeThreads <host threads of the BAM decoder, default all>, --gpuInflate 0|1 <BGZF blocks inflated on the first listed GPU, default 0>, --gpuParse 0|1 <the BAM records found, filtered and parsed there as well, default 0; 1 implies --gpuInflate 1>, --gpuGroup 0|1 <the records grouped by read name there as well, default 0; 1 implies --gpuParse 1>, --gpuSort 0|1 <the units put into read-name order there as well, default 0; 1 implies --gpuGroup 1>, --gpuFill 0|1 <the sample laid out and its windows filled there as well, default 0; 1 implies --gpuSort 1>, --gpuFillWide 0|1 <units with a mate of 17 to 4096 alignments filled there as well, default 0; 1 implies --gpuFill 1>, --verifyCRC 0|1 <the CRC-32 of every BGZF block checked against its inflated bytes, on the GPU where they are inflated there, default 0>, --batchPairs <units per GPU batch>, --rngSeed <base of the end-cell draws>,
+// --decodeSlots <samples that decode at one time, default CPUs / 16>, --tailPool <k: GPU batches per launch of the widest DP classes>, --pairOverflow <MiB of device scratch for pairs beyond the pairing capacities, default 0: such pairs are refused>, --decodeThreads <host threads of the BAM decoder, default all>, --gpuInflate 0|1 <BGZF blocks inflated on the first listed GPU, default 0>, --gpuInflateKernel 0|1 <which kernel inflates them there: 0 matches resolved in the output buffer, 1 the block's history in LDS; default 0; read only where blocks are inflated on the GPU>, --gpuParse 0|1 <the BAM records found, filtered and parsed there as well, default 0; 1 implies --gpuInflate 1>, --gpuGroup 0|1 <the records grouped by read name there as well, default 0; 1 implies --gpuParse 1>, --gpuSort 0|1 <the units put into read-name order there as well, default 0; 1 implies --gpuGroup 1>, --gpuFill 0|1 <the sample laid out and its windows filled there as well, default 0; 1 implies --gpuSort 1>, --gpuFillWide 0|1 <units with a mate of 17 to 4096 alignments filled there as well, default 0; 1 implies --gpuFill 1>, --verifyCRC 0|1 <the CRC-32 of every BGZF block checked against its inflated bytes, on the GPU where they are inflated there, default 0>, --batchPairs <units per GPU batch>, --rngSeed <base of the end-cell draws>,
 // --loci A,B,... (default: the reference's 17 loci, hla/HLATyper.cpp:42).  Several samples in one call (BASELINE config 4): comma-separated lists of
 // equal length in --sampleID, --outputDirectory, --FASTQ1, --FASTQ2 (--FASTQU); sample i runs on device i % #devices, all samples side by side.
 // Not rebuilt: the --BAM entry (the Perl driver never uses it: it extracts reads itself and passes FASTQ files), read simulation /
@@ -242,6 +242,8 @@ int action_HLA_one(const std::map<std::string, std::string>& arguments, const st
     mapper::processBAM BAMprocessor(graphDirectory, longReads.length() ? 16384 : 384, rngSeed, devices, decodeThreads);
     // --gpuInflate 1: the BGZF blocks of the BAM are inflated on the sample's first device instead of on the host's threads (include/hlala_gpu.h: hlala_bam_extract_seeds_gpu); the sample is the same
     BAMprocessor.set_gpu_inflate(arguments.count("gpuInflate") && std::atoi(arguments.at("gpuInflate").c_str()) != 0);
+    // --gpuInflateKernel 1: k_bgzf_inflate_lds inflates them (hlala_inflater_set_kernel); it has meaning only with --gpuInflate 1 or anything that implies it
+    if(arguments.count("gpuInflateKernel")) BAMprocessor.set_gpu_inflate_kernel(std::atoi(arguments.at("gpuInflateKernel").c_str()));
     // --gpuParse 1: the record pass of the decoder runs there as well (HLALA_SEEDS_GPU_PARSE); it implies --gpuInflate 1
     if(arguments.count("gpuParse") && std::atoi(arguments.at("gpuParse").c_str()) != 0) BAMprocessor.set_gpu_parse(true);
     // --gpuGroup 1: the decoder's group phase runs there as well (HLALA_SEEDS_GPU_GROUP); it implies --gpuParse 1
@@ -270,6 +272,7 @@ int action_HLA_one(const std::map<std::string, std::string>& arguments, const st
               << " s -- the decoder starts with them --, graph read after " << graphDirectory->graph_seconds << " s, translation tables after " << graphDirectory->contigs_seconds << " s, typer files beside them); seed extraction in all " << openSeconds << " s\n" << std::flush;
     if(BAMprocessor.gpu_inflate()) std::cout << "BGZF inflate: " << BAMprocessor.inflate_counts[0] << " blocks on the GPU, " << BAMprocessor.inflate_counts[1] << " rejected there and inflated again on the host, "
                                              << BAMprocessor.inflate_counts[2] << " on the host only\n" << std::flush;
+    if(BAMprocessor.gpu_inflate() && BAMprocessor.gpu_inflate_kernel() == HLALA_INFLATE_KERNEL_LDS) std::cout << "BGZF inflate kernel: k_bgzf_inflate_lds (the history of a block in LDS)\n" << std::flush;
     if(BAMprocessor.gpu_parse()) std::cout << "BAM records: " << BAMprocessor.parse_counts[0] << " scanned on the GPU in " << BAMprocessor.parse_counts[1] << " rounds, " << BAMprocessor.parse_counts[2]
                                            << " rounds parsed again on the host\n" << std::flush;
     if(BAMprocessor.gpu_group()) std::cout << "BAM grouping: " << BAMprocessor.group_counts[0] << " records grouped on the GPU, " << BAMprocessor.group_counts[1] << " hash runs regrouped on the host"

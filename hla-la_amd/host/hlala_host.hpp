@@ -355,6 +355,7 @@ public:
         // the contexts that are being created); made before the decoder thread starts, destroyed after the decode
         struct InflaterOwner { hlala_inflater* f = nullptr; ~InflaterOwner() { if(f) hlala_inflater_destroy(f); } } inflater;
         if(gpu_inflate_ && hlala_inflater_create(devices_[0], 0, &inflater.f) != HLALA_OK) throw std::runtime_error(std::string("hlala_inflater_create: ") + hlala_inflater_last_error(nullptr));
+        if(inflater.f && hlala_inflater_set_kernel(inflater.f, gpu_inflate_kernel_) != HLALA_OK) throw std::runtime_error(std::string("--gpuInflateKernel: ") + hlala_inflater_last_error(inflater.f));
         ThreadJoiner tdec, th;
         // (the decoder needs the reference intervals only: it starts while the graph directory may still be reading its graph and translation tables)
         tdec.start([&]() {
@@ -398,6 +399,8 @@ public:
     }
     void set_gpu_inflate(bool on) { gpu_inflate_ = on; }       // before openBAM
     bool gpu_inflate() const { return gpu_inflate_; }
+    void set_gpu_inflate_kernel(int kind) { gpu_inflate_kernel_ = kind; }       // before openBAM; HLALA_INFLATE_KERNEL_*: read only where an inflater is made
+    int gpu_inflate_kernel() const { return gpu_inflate_kernel_; }
     void set_gpu_parse(bool on) { gpu_parse_ = on; if(on) gpu_inflate_ = true; }       // before openBAM; the record pass on the GPU works on blocks inflated there
     bool gpu_parse() const { return gpu_parse_; }
     void set_gpu_group(bool on) { gpu_group_ = on; if(on) set_gpu_parse(true); }       // before openBAM; HLALA_SEEDS_GPU_GROUP: the records grouped by read name on the GPU; it works on what the record pass leaves there
@@ -497,7 +500,7 @@ private:
         if(hlala_seed_batch_window(seeds_, u0, n, &in) != HLALA_OK) throw std::runtime_error(std::string("alignReads: ") + hlala_bam_last_error());
     }
     std::shared_ptr<GraphDirectory> gdir_;
-    std::string graphDir_; bool extended_; int max_columns_; uint32_t rng_seed_; std::vector<int> devices_; int threads_; bool gpu_inflate_ = false, gpu_parse_ = false, gpu_group_ = false, gpu_sort_ = false, gpu_fill_ = false, gpu_fill_wide_ = false, verify_crc_ = false;
+    std::string graphDir_; bool extended_; int max_columns_; uint32_t rng_seed_; std::vector<int> devices_; int threads_; bool gpu_inflate_ = false, gpu_parse_ = false, gpu_group_ = false, gpu_sort_ = false, gpu_fill_ = false, gpu_fill_wide_ = false, verify_crc_ = false; int gpu_inflate_kernel_ = HLALA_INFLATE_KERNEL_HBM;
     hlala_graph_file* graph_ = nullptr; hlala_contigs_file* contigs_ = nullptr; const std::vector<hlala_bam_interval>& intervals_;      // owned by gdir_
     hlala_seed_batch* seeds_ = nullptr; std::vector<hlala_ctx*> ctxs_; hlala_comm* comm_ = nullptr; int tail_pool_ = 1; int64_t pair_overflow_ = 0; bool owns_ctx_ = true; std::string BAM_;
     int32_t batchPairs_ = 1; std::vector<hlala_batch*> live_; std::vector<char> aligned_;       // aligned_[bi]: hlala_align_batch has been queued for live_[bi]

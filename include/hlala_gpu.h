@@ -497,6 +497,15 @@ typedef struct { int64_t n_blocks, n_ok, n_rejected; double ms_h2d, ms_kernel, m
 int  hlala_inflater_create(int32_t device, size_t chunk_bytes /* compressed bytes staged per launch; 0 = default */, hlala_inflater** out);
 void hlala_inflater_destroy(hlala_inflater* inf);
 const char* hlala_inflater_last_error(const hlala_inflater* inf);
+/* Which kernel inflates the blocks of every later call on this handle -- hlala_bgzf_inflate, hlala_bgzf_inflate_crc and hlala_bam_extract_seeds_gpu with every flag, the
+ * device destination of HLALA_SEEDS_GPU_PARSE included: they share one launch site.  HBM (the default of a new handle): k_bgzf_inflate, one wavefront per block, matches
+ * resolved in the output buffer.  LDS: k_bgzf_inflate_lds (csrc/kernel_inflate_lds.hip; rules in csrc/inflate_lds_core.h), one workgroup of two wavefronts per block, the
+ * block's history in a ring in LDS, one wavefront decoding a batch while the other places the batch before.  Statuses, outputs, counters, chunks and the host retry of
+ * rejected blocks are the same.  set: HLALA_E_ARG for a null handle or an unknown kind (the choice stays as it was); get: the kind, -1 for a null handle. */
+#define HLALA_INFLATE_KERNEL_HBM 0
+#define HLALA_INFLATE_KERNEL_LDS 1
+int     hlala_inflater_set_kernel(hlala_inflater* inf, int32_t kind);
+int32_t hlala_inflater_get_kernel(const hlala_inflater* inf);
 /* comp, blocks, out and status are host memory.  The descriptors are checked before anything is launched (HLALA_E_ARG: a range outside comp or out, isize
  * beyond 65536, a block larger than a chunk, output ranges that overlap).  status[i] receives the HLALA_INFLATE_* status of block i; the output range of a
  * rejected block holds unspecified bytes, nothing else of out is written.  Returns HLALA_OK whenever the call itself worked. */
@@ -1109,7 +1118,8 @@ int  hlala_abi_sizeof(const char* struct_name);
  * hlala_bam_group / _rounds, HLALA_SEEDS_GPU_GROUP, hlala_seed_batch_group_counts; hlala_bam_name_order, HLALA_SEEDS_GPU_SORT, hlala_seed_batch_sort_counts;
  * hlala_bam_fill_create / _window / _destroy / _last_error, HLALA_SEEDS_GPU_FILL, hlala_seed_batch_fill_counts;
  * hlala_batch_create_from_fill, hlala_debug_batch_inputs;
- * hlala_bam_fill_create_wide, hlala_bam_fill_wide_stats, HLALA_SEEDS_GPU_FILL_WIDE, hlala_seed_batch_fill_wide_counts): a caller
+ * hlala_bam_fill_create_wide, hlala_bam_fill_wide_stats, HLALA_SEEDS_GPU_FILL_WIDE, hlala_seed_batch_fill_wide_counts;
+ * hlala_inflater_set_kernel / _get_kernel): a caller
  * detects them by the presence of the symbol.  A caller compares
  * hlala_abi_version() with the HLALA_ABI_VERSION it was compiled against and refuses to run on a mismatch (hla-la_amd/__init__.py and
  * hla-la_amd/host/hlala_host.hpp do). */

@@ -28,7 +28,10 @@ hlala_batch_create_from_fill on both states, the first with the host units' rang
 --wide-bam-pairs N (the same file): a BAM of N pairs written here, not by the generators above -- 2 x 100 bases on one reference, --wide-share of the pairs with 17 to 200
 alignments on mate 0 (uniform; AS 40 with probability 0.7, else 60 / 77 / 90), every other mate with 1 to 3, one primary per mate, records shuffled -- decoded with
 HLALA_SEEDS_GPU_FILL alone and with HLALA_SEEDS_GPU_FILL | HLALA_SEEDS_GPU_FILL_WIDE, alternating (the caller sets HLALA_BAM_EAGER=1 so that the fill lies inside the decode):
-host units, the layout + fill phase and the wall clock of each."""
+host units, the layout + fill phase and the wall clock of each.
+--inflate-kernels hbm,lds (its output is meant for profiles/inflate_lds_gpu.txt): the named inflate kernels (hlala_inflater_set_kernel) alternate on ONE inflater -- in the
+decoder paths `gpu` and `gpu+parse`, which run once per kernel beside the host decoder in every round, and in hlala_bgzf_inflate on all blocks in one call, which prints
+upload / kernel / download / wall, blocks/s and GB/s per kernel and run (one warm-up each) and checks that the kernels leave the same bytes.  Nothing else runs."""
 import argparse
 import os
 import sys
@@ -395,6 +398,7 @@ def main():
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--scan-mb", type=int, default=256, help="inflated MiB handed to hlala_bam_scan alone (below 4096)")
     ap.add_argument("--verify-crc", action="store_true", help="every decoder with and without HLALA_SEEDS_VERIFY_CRC in the same alternation; k_bgzf_crc32's device time beside the inflate kernel's")
+    ap.add_argument("--inflate-kernels", default="", help="comma-separated inflate kernels (hbm, lds) that alternate on one inflater: decoder paths gpu and gpu+parse, and all blocks in one call")
     ap.add_argument("--bam", default="", help="use this BAM (reference names PRG_<n>) instead of generating one; needs --levels of the world it was made from")
     ap.add_argument("--paths", default="", help="comma-separated paths that alternate (default: all), e.g. gpu+parse+group+sort,gpu+parse+group+sort+fill")
     ap.add_argument("--no-gpu", action="store_true", help="host engine only (a box without a GPU: checks the generator and the host figures)")
@@ -466,6 +470,21 @@ def main():
     if args.paths:
         order = [k for k in order if k in args.paths.split(",")]
     res = {k: [] for k in order}
+    kinds = {"hbm": P.INFLATE_KERNEL_HBM, "lds": P.INFLATE_KERNEL_LDS}
+    kernels = [k for k in args.inflate_kernels.split(",") if k]
+    assert all(k in kinds for k in kernels), "--inflate-kernels: hbm and lds are the kernels"
+    if kernels and inf:
+        def with_kernel(kind, opener):
+            def f():
+                inf.set_kernel(kind)
+                return opener()
+            return f
+        order = ["host"] if "host" in order else []
+        for pth, opener in (("gpu", gpu), ("gpu+parse", gpu_parse)):
+            if not args.paths or pth in args.paths.split(","):
+                for kn in kernels:
+                    openers["%s[%s]" % (pth, kn)] = with_kernel(kinds[kn], opener); order.append("%s[%s]" % (pth, kn))
+        res = {k: [] for k in order}
     if args.verify_crc:
         V = P.SEEDS_PACKED | P.SEEDS_VERIFY_CRC
         openers["host+crc"] = lambda: P.bam_open_seeds(lib, bam, intervals, threads=args.threads, flags=V)                 # noqa: E731
@@ -510,6 +529,40 @@ def main():
         out = np.empty(n_inflated, np.uint8); desc = []; u = 0
         for off, clen_, isize in blocks:
             desc.append((off, clen_, isize, u)); u += isize
+        if kernels:
+            # the kernels alternate on the one inflater: every block of the file in one call, one warm-up call each, then --runs calls each
+            per = {kn: [] for kn in kernels}; ref = None
+            for i in range(args.runs + 1):
+                for kn in kernels:
+                    inf.set_kernel(kinds[kn])
+                    status, st = inf.inflate(raw, desc, out)
+                    assert int((status != 0).sum()) == 0 and st.n_rejected == 0, "the GPU rejected blocks of a valid file"
+                    if i == 0:
+                        if ref is None:
+                            ref = out.copy()
+                        else:
+                            assert np.array_equal(ref, out), "the kernels leave different bytes"
+                        continue
+                    per[kn].append((st.ms_kernel, st.ms_wall))
+                    print("hlala_bgzf_inflate [%s], all blocks in one call, run %d: upload %.1f ms, kernel %.1f ms, download %.1f ms (device times summed over the chunks; they overlap), "
+                          "wall %.1f ms: %.0f blocks/s, %.2f GB/s inflated; kernel alone %.2f GB/s" % (kn, i, st.ms_h2d, st.ms_kernel, st.ms_d2h, st.ms_wall, st.n_blocks / (st.ms_wall / 1e3),
+                                                                                                    n_inflated / 1e9 / (st.ms_wall / 1e3), n_inflated / 1e9 / (st.ms_kernel / 1e3)))
+            print("the kernels left the same %d bytes (compared after the warm-up calls)" % out.size)
+            for kn in kernels:
+                for j, what in ((0, "kernel ms summed over the chunks"), (1, "wall ms")):
+                    v = [x[j] for x in per[kn]]
+                    print("%s, %s: median %.1f, range %.1f .. %.1f of %d runs" % (kn, what, float(np.median(v)), min(v), max(v), len(v)))
+            if len(kernels) == 2:
+                a, b = kernels
+                for j, what in ((0, "kernel"), (1, "wall")):
+                    va = [x[j] for x in per[a]]; vb = [x[j] for x in per[b]]
+                    print("%s against %s, %s: slowest %s run %.1f ms, fastest %s run %.1f ms: every %s run is %s than every %s run; ratio of the medians %.2f" % (
+                        b, a, what, b, max(vb), a, min(va), b, "faster" if max(vb) < min(va) else "NOT faster", a, float(np.median(va)) / float(np.median(vb))))
+            inf.close()
+            if tmp:
+                import shutil
+                shutil.rmtree(tmp, ignore_errors=True)
+            return
         for i in range(2):
             status, st = inf.inflate(raw, desc, out)
         assert int((status != 0).sum()) == 0 and st.n_rejected == 0, "the GPU rejected blocks of a valid file"
