@@ -259,10 +259,13 @@ class SeedBatch:
         lib.hlala_seed_batch_counts(h, cnt)          # (hlala_seed_batch_desc would fill in the whole sample: the windows are filled as they are handed out)
         self.counts = dict(examined=int(cnt[0]), seeds=int(cnt[1]), incomplete=int(cnt[2]))
 
-    def window(self, first_unit, n_units) -> "BatchIn":
-        """units [first_unit, first_unit + n_units) as a batch descriptor pointing into the handle (no copy; valid while the handle lives)"""
+    def window(self, first_unit, n_units, peek=False) -> "BatchIn":
+        """units [first_unit, first_unit + n_units) as a batch descriptor pointing into the handle (no copy; valid while the handle lives).  peek: hlala_seed_batch_peek_window
+        -- on a sample that can build resident windows the units do not count as handed out"""
         d = BatchIn()
-        if self.lib.hlala_seed_batch_window(self.h, int(first_unit), int(n_units), C.byref(d)) != 0:
+        f = self.lib.hlala_seed_batch_peek_window if peek else self.lib.hlala_seed_batch_window
+        f.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(BatchIn)]
+        if f(self.h, int(first_unit), int(n_units), C.byref(d)) != 0:
             raise HlalaError(self.lib.hlala_bam_last_error().decode(errors="replace"))
         return d
 
@@ -351,6 +354,29 @@ class SeedBatch:
         cnt = (C.c_int64 * 3)()
         self.lib.hlala_seed_batch_fill_wide_counts.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
         self.lib.hlala_seed_batch_fill_wide_counts(self.h, cnt)
+        return tuple(int(x) for x in cnt)
+
+    def create_resident(self, ctx, first_unit, n_units):
+        """hlala_seed_batch_create_resident: units [first_unit, first_unit + n_units) as a batch of `ctx` built on the device from the sample's own fill state, without the
+        window coming down and going up again.  Returns (return code, Batch or None, BatchFillStats): HLALA_E_STATE (-5, with ctx.last_error() starting "not available:":
+        take window() + Context.batch_window instead), HLALA_E_ARG (-1) and HLALA_E_CAPACITY (-4) are returned, not raised."""
+        st = BatchFillStats(); b = C.c_void_p()
+        self.lib.hlala_seed_batch_create_resident.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(BatchFillStats)]
+        rc = self.lib.hlala_seed_batch_create_resident(self.h, ctx.h, int(first_unit), int(n_units), C.byref(b), C.byref(st))
+        if rc not in (0, -1, -4, -5):
+            ctx._check(rc, "hlala_seed_batch_create_resident")
+        if rc != 0:
+            return rc, None, st
+        bt = Batch(ctx, b, int(st.n_chains), int(n_units))
+        if self.long_read_mode:
+            bt.unpaired = True
+        return rc, bt, st
+
+    def resident_counts(self):
+        """(windows built by create_resident, units in them, pieces of host units staged for them, calls that answered "not available")"""
+        cnt = (C.c_int64 * 4)()
+        self.lib.hlala_seed_batch_resident_counts.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        self.lib.hlala_seed_batch_resident_counts(self.h, cnt)
         return tuple(int(x) for x in cnt)
 
     def fill_ms(self):
@@ -1131,7 +1157,7 @@ EXPORTED_SYMBOLS = [
     "hlala_bam_group", "hlala_bam_group_rounds", "hlala_seed_batch_group_counts",
     "hlala_bam_name_order", "hlala_seed_batch_sort_counts",
     "hlala_bam_fill_create", "hlala_bam_fill_window", "hlala_bam_fill_last_error", "hlala_bam_fill_destroy", "hlala_seed_batch_fill_counts", "hlala_seed_batch_fill_ms",
-    "hlala_batch_create_from_fill", "hlala_debug_batch_inputs",
+    "hlala_batch_create_from_fill", "hlala_debug_batch_inputs", "hlala_seed_batch_create_resident", "hlala_seed_batch_peek_window", "hlala_seed_batch_resident_counts",
     "hlala_bam_fill_create_wide", "hlala_bam_fill_wide_stats", "hlala_seed_batch_fill_wide_counts",
     "hlala_locus_cluster_kmers", "hlala_type_locus", "hlala_kmer_presence", "hlala_kmer_keep_reads", "hlala_kmer_presence_kept", "hlala_kmer_forget_reads", "hlala_unit_alignment_stats", "hlala_typer_write_summary", "hlala_typer_begin_output", "hlala_locus_write_files", "hlala_locus_write_pairs_file", "hlala_typer_end_output",
 ]

@@ -3563,6 +3563,21 @@ static int fill_state_window(void* state, int64_t first_unit, int64_t n_units, c
     return rc;
 }
 static void fill_state_destroy(void* state) { fill_free((hlala_bam_fill*)state); }
+// a window of the decoder's fill state as a batch of ctx (hlala_seed_batch_create_resident): hlala_batch_create_from_fill; a context on another device is no error of
+// the sample -- the caller takes the host route for it
+static int fill_state_resident(void* state, hlala_ctx* c, int64_t first_unit, int64_t n_units, const hlala_batch_fill_src* src, hlala_batch** out, hlala_batch_fill_stats* stats, std::string* err)
+{
+    hlala_bam_fill* H = (hlala_bam_fill*)state;
+    if(!H || !c) { if(err) *err = "hlala_seed_batch_create_resident: null argument"; return HLALA_E_ARG; }
+    if(c->device != H->device) {
+        c->err = "not available: the context is on device " + std::to_string(c->device) + ", the sample's fill state on device " + std::to_string(H->device);
+        if(err) *err = c->err;
+        return HLALA_E_STATE;
+    }
+    const int rc = hlala_batch_create_from_fill(c, H, first_unit, n_units, src, out, stats);
+    if(rc != HLALA_OK && err) *err = c->err;
+    return rc;
+}
 static int fill_hook_any(void* inflater, const hlala_bam_fill_in* in, const FillWideIn* wide, int64_t* read_off, int64_t* chain_off, int64_t* cigar_count, int64_t* name_off,
                          hlala_host::bam_fill_handle* handle, hlala_bam_fill_stats* stats, bool* available, std::string* err)
 {
@@ -3594,7 +3609,7 @@ static int fill_hook_any(void* inflater, const hlala_bam_fill_in* in, const Fill
     if(rc != HLALA_OK) { f->err = H->err; fill_free(H); return fail(rc); }
     if(noMemory) { fill_free(H); *available = false; return HLALA_OK; }
     stats->ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tWall).count();
-    handle->state = H; handle->window = fill_state_window; handle->destroy = fill_state_destroy;
+    handle->state = H; handle->window = fill_state_window; handle->destroy = fill_state_destroy; handle->resident = fill_state_resident;
     return HLALA_OK;
 }
 static int bam_fill_hook(void* inflater, const hlala_bam_fill_in* in, int64_t* read_off, int64_t* chain_off, int64_t* cigar_count, int64_t* name_off, hlala_host::bam_fill_handle* handle,
@@ -3767,6 +3782,18 @@ extern "C" int hlala_batch_create_from_fill(hlala_ctx* c, hlala_bam_fill* H, int
     stats->ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tWall).count();
     *out = b;
     return HLALA_OK;
+}
+
+extern "C" int hlala_seed_batch_create_resident(hlala_seed_batch* S, hlala_ctx* c, int64_t first_unit, int32_t n_units, hlala_batch** out, hlala_batch_fill_stats* stats)
+{
+    if(!c) return HLALA_E_ARG;
+    if(out) *out = nullptr;
+    if(!S || !out || !stats) { c->err = "hlala_seed_batch_create_resident: null argument"; return HLALA_E_ARG; }
+    memset(stats, 0, sizeof(*stats));
+    std::string err;
+    const int rc = hlala_host::seed_batch_resident(S, c, first_unit, first_unit + (int64_t)n_units, out, stats, &err);
+    if(rc != HLALA_OK) c->err = err;
+    return rc;
 }
 
 extern "C" int hlala_debug_batch_inputs(hlala_ctx* c, hlala_batch* b, hlala_batch_inputs_out* out)

@@ -48,6 +48,7 @@
 
 #include "../../include/hlala_gpu.h"
 #include "host_internal.h"
+#include "bam_resident_cover.h"
 
 namespace {
 
@@ -219,6 +220,9 @@ struct Work { std::vector<Arena> arenas; std::vector<std::vector<Rec>> precs; st
               int nm = 2, T = 1; int64_t UCH = 1, nUChunks = 0, remaining = 0; std::vector<uint8_t> done;
               // ---- HLALA_SEEDS_GPU_FILL: the device's fill state (null: the host fills every unit) and the units it leaves to the host, ascending
               hlala_host::bam_fill_handle gpuFill; std::vector<uint32_t> hostUnits;
+              // ---- resident windows (seed_batch_resident): the units handed out so far, by either route; empty (nChunks == 0) until the first resident window -- until
+              // then every chunk is handed out whole by ensure_filled, and `done` says all there is to say
+              hlala_bamres::ResidentCover cover;
               void release_gpu() { if(gpuFill.state && gpuFill.destroy) gpuFill.destroy(gpuFill.state); gpuFill = hlala_host::bam_fill_handle(); }
               ~Work() { release_gpu(); } };
 
@@ -256,7 +260,14 @@ struct hlala_seed_batch {
     bool pin_lazy = false; std::mutex pin_mu; std::vector<size_t> pin_cursor; std::vector<std::pair<void*, size_t>> pin_regions;
     // the decoder's working memory while units remain to be filled (hlala_seed_batch_window fills what it hands out); null once every unit is filled
     Work* work = nullptr; double fill_seconds = 0; std::mutex fill_mu;       // (the mutex lives here, not in the working memory it outlives)
-    ~hlala_seed_batch() { if(work) { Work* w = work; work = nullptr; w->release_gpu(); try { std::thread([w]() { delete w; }).detach(); } catch(...) { delete w; } } }
+    // resident windows (hlala_seed_batch_create_resident): windows built on the device, units in them, pieces of host units staged, windows that fell back
+    int64_t resident_counts[4] = {0, 0, 0, 0};
+    // ... per unit: its name is in place in name_chars, copied there by a resident window (null until the first one; hlala_seed_batch_name reads it without the mutex)
+    std::atomic<std::atomic<uint8_t>*> name_mark{nullptr};
+    // ... once the working memory is released after resident windows: per chunk of host_uch units, whether the host arrays of its units were ever written.  A chunk
+    // that was not went out resident only: hlala_seed_batch_window / _desc over it answer HLALA_E_STATE.  Empty: every chunk was written (or units remain to be filled)
+    std::vector<uint8_t> host_done; int64_t host_uch = 1;
+    ~hlala_seed_batch() { delete[] name_mark.load(); if(work) { Work* w = work; work = nullptr; w->release_gpu(); try { std::thread([w]() { delete w; }).detach(); } catch(...) { delete w; } } }
 };
 
 namespace {
@@ -321,7 +332,8 @@ void fill_units(hlala_seed_batch* S, const Work& W, const size_t a, const size_t
 
 // HLALA_SEEDS_GPU_FILL: the units [a, z) by the device's fill state -- one slice per array, written by its window call where they belong in the sample's arrays
 constexpr size_t GPU_FILL_RANGE = 65536;
-void fill_range_gpu(hlala_seed_batch* S, Work& W, const size_t a, const size_t z)
+// the slices of a window that starts at unit a: where its part of every array of the sample begins (include/hlala_gpu.h: hlala_bam_fill_out)
+hlala_bam_fill_out window_slices(hlala_seed_batch* S, const Work& W, const size_t a)
 {
     static uint8_t none[16];                                   // (an array of the sample without an element: the window call takes no null pointer)
     auto at = [](auto& buf, size_t i) { return buf.size() ? buf.data() + i : (decltype(buf.data()))(void*)none; };
@@ -331,6 +343,11 @@ void fill_range_gpu(hlala_seed_batch* S, Work& W, const size_t a, const size_t z
     if(S->packed) out.read_bases_packed = at(S->read_bases_packed, (b0 + r0 + 1) >> 1); else out.read_bases = at(S->read_bases, b0);
     out.chain_contig = at(S->chain_contig, c0); out.chain_pos = at(S->chain_pos, c0); out.chain_offset = at(S->chain_offset, c0); out.chain_as = at(S->chain_as, c0); out.chain_reverse = at(S->chain_reverse, c0);
     out.cigar_off_end = at(S->cigar_off, c0 + 1); out.cigar = at(S->cigar, (size_t)W.cigCount[r0]); out.name_chars = at(S->name_chars, (size_t)S->name_off[a]);
+    return out;
+}
+void fill_range_gpu(hlala_seed_batch* S, Work& W, const size_t a, const size_t z)
+{
+    const hlala_bam_fill_out out = window_slices(S, W, a);
     hlala_bam_fill_stats st; std::string herr;
     const int rc = W.gpuFill.window(W.gpuFill.state, (int64_t)a, (int64_t)(z - a), &out, &st, &herr);
     if(rc != HLALA_OK) throw Fail("BAM fill on the GPU failed: " + herr);
@@ -339,9 +356,26 @@ void fill_range_gpu(hlala_seed_batch* S, Work& W, const size_t a, const size_t z
     S->fill_window_ms += st.ms_wall;
 }
 
+// Once no unit is left to hand out the working memory and the fill state are released (the caller holds fill_mu through g; released on the way out).  After
+// resident windows the sample keeps which chunks the host has written.
+void release_if_handed_out(hlala_seed_batch* S, Work* W, std::unique_lock<std::mutex>& g)
+{
+    if(W->remaining > 0) return;
+    S->work = nullptr;
+    if(W->cover.nChunks) { S->host_done = std::move(W->done); S->host_uch = W->UCH; }
+    const bool onGpu = W->gpuFill.state != nullptr; const Clock::time_point tR = Clock::now();
+    W->release_gpu();
+    if(onGpu && getenv("HLALA_BAM_DEBUG")) fprintf(stderr, "bam-debug: fill on the GPU: window calls %.3f s (device: chain %.3f, cigar %.3f, names %.3f, bases %.3f, download %.3f ms), all fills %.3f s, state released in %.3f s\n",
+                                                   S->fill_window_ms / 1e3, S->fill_ms[0], S->fill_ms[1], S->fill_ms[2], S->fill_ms[3], S->fill_ms[4], S->fill_seconds, since(tR));
+    g.unlock();
+    try { std::thread([W]() { delete W; }).detach(); } catch(...) { delete W; }
+}
+
 // The units [u0, u1) are filled before this returns (whichever thread asks first fills them, on the decoder's thread count; the others wait).  Once no unit is left
 // the working memory is released on a thread of its own (unmapping a dozen GB takes about a second that the caller need not wait for).
-void ensure_filled(const hlala_seed_batch* Sc, int64_t u0, int64_t u1)
+// peek (hlala_seed_batch_peek_window), for a sample that can build resident windows: the units are filled but do not count as handed out -- the caller looks at them
+// (the insert-size estimate) and hands them out later, by either route.  For any other sample a peek is a window like every other.
+void ensure_filled(const hlala_seed_batch* Sc, int64_t u0, int64_t u1, const bool peek = false)
 {
     hlala_seed_batch* S = const_cast<hlala_seed_batch*>(Sc);
     if(u1 <= u0) return;
@@ -349,6 +383,12 @@ void ensure_filled(const hlala_seed_batch* Sc, int64_t u0, int64_t u1)
     Work* W = S->work;
     if(!W) return;
     const Clock::time_point t0 = Clock::now();
+    const bool peeking = peek && W->gpuFill.state && W->gpuFill.resident;
+    if(peeking && !W->cover.nChunks) {
+        hlala_bamres::ResidentCover cv; cv.init((int64_t)W->units.size(), W->UCH);
+        for(int64_t c = 0; c < W->nUChunks; c++) if(W->done[(size_t)c]) (void)cv.mark_chunk(c);        // (handed out whole, and counted, so far)
+        W->cover = std::move(cv);
+    }
     std::vector<int64_t> todo;
     for(int64_t c = u0 / W->UCH; c <= (u1 - 1) / W->UCH && c < W->nUChunks; c++) if(!W->done[(size_t)c]) todo.push_back(c);
     if(!todo.empty() && W->gpuFill.state) {
@@ -367,7 +407,7 @@ void ensure_filled(const hlala_seed_batch* Sc, int64_t u0, int64_t u1)
             i = j;
         }
         for(int64_t c : todo) W->done[(size_t)c] = 1;
-        W->remaining -= (int64_t)todo.size();
+        if(!W->cover.nChunks) W->remaining -= (int64_t)todo.size();
     } else if(!todo.empty()) {
         std::vector<std::vector<uint32_t>> order((size_t)W->T);
         const size_t nU = W->units.size();
@@ -378,18 +418,87 @@ void ensure_filled(const hlala_seed_batch* Sc, int64_t u0, int64_t u1)
         for(int64_t c : todo) W->done[(size_t)c] = 1;
         W->remaining -= (int64_t)todo.size();
     }
+    // (resident windows or peeks have been there: a chunk counts once -- one whose units all went out resident has counted already, one that was only peeked at counts now)
+    if(W->cover.nChunks && !peeking) for(int64_t c = u0 / W->UCH; c <= (u1 - 1) / W->UCH && c < W->nUChunks; c++) W->remaining -= W->cover.mark_chunk(c);
     const double dt = since(t0);
     S->fill_seconds += dt; S->seconds[5] += dt;
-    if(W->remaining <= 0) {
-        S->work = nullptr;
-        const bool onGpu = W->gpuFill.state != nullptr; const Clock::time_point tR = Clock::now();
-        W->release_gpu();
-        if(onGpu && getenv("HLALA_BAM_DEBUG")) fprintf(stderr, "bam-debug: fill on the GPU: window calls %.3f s (device: chain %.3f, cigar %.3f, names %.3f, bases %.3f, download %.3f ms), all fills %.3f s, state released in %.3f s\n",
-                                                       S->fill_window_ms / 1e3, S->fill_ms[0], S->fill_ms[1], S->fill_ms[2], S->fill_ms[3], S->fill_ms[4], S->fill_seconds, since(tR));
-        g.unlock();
-        try { std::thread([W]() { delete W; }).detach(); } catch(...) { delete W; }
-    }
+    release_if_handed_out(S, W, g);
 }
+}  // namespace
+
+// hlala_seed_batch_create_resident's side of the decoder (host_internal.h)
+int hlala_host::seed_batch_resident(hlala_seed_batch* S, hlala_ctx* ctx, int64_t u0, int64_t u1, hlala_batch** out_batch, hlala_batch_fill_stats* stats, std::string* err)
+{
+    auto say = [&](const std::string& t) { if(err) *err = t; };
+    if(out_batch) *out_batch = nullptr;
+    if(!S || !out_batch || !stats || u0 < 0 || u1 < u0 || u1 > S->n_units) { say("hlala_seed_batch_create_resident: units outside the sample"); return HLALA_E_ARG; }
+    std::unique_lock<std::mutex> g(S->fill_mu);
+    Work* W = S->work;
+    const char* why = !W ? "the sample's working memory is released (every unit has been handed out)" : !W->gpuFill.state ? "the sample has no fill state on the device"
+                    : !W->gpuFill.resident ? "the fill state builds no resident windows" : nullptr;
+    if(why) { S->resident_counts[3]++; say(std::string("not available: ") + why); return HLALA_E_STATE; }
+    const Clock::time_point t0 = Clock::now();
+    const std::vector<uint32_t>& H = W->hostUnits;
+    const size_t ha = (size_t)(std::lower_bound(H.begin(), H.end(), (uint32_t)u0) - H.begin()), hz = (size_t)(std::lower_bound(H.begin(), H.end(), (uint32_t)u1) - H.begin());
+    std::atomic<uint8_t>* mark = S->name_mark.load(std::memory_order_relaxed);
+    try {
+        // (what is allocated on the first resident window, in front of the call: nothing behind it can fail for want of memory)
+        if(!mark) { mark = new std::atomic<uint8_t>[(size_t)S->n_units + 1]; for(int64_t u = 0; u <= S->n_units; u++) mark[u].store(0, std::memory_order_relaxed); S->name_mark.store(mark, std::memory_order_release); }
+        if(!W->cover.nChunks) {
+            hlala_bamres::ResidentCover cv; cv.init((int64_t)W->units.size(), W->UCH);
+            for(int64_t c = 0; c < W->nUChunks; c++) if(W->done[(size_t)c]) (void)cv.mark_chunk(c);        // (handed out whole by ensure_filled, and counted there)
+            W->cover = std::move(cv);
+        }
+        // ---- the window's host units: filled by the host into the sample's own arrays (their ranges only), handed over as the window's slices
+        if(hz > ha) {
+            std::vector<std::vector<uint32_t>> order((size_t)W->T);
+            parallel_for((int64_t)(hz - ha), W->T, [&](int64_t k, int t) { const size_t u = H[ha + (size_t)k]; fill_units(S, *W, u, u + 1, order[(size_t)t]); });
+        }
+    } catch(const std::exception& e_) { say(std::string("hlala_seed_batch_create_resident: ") + e_.what()); return HLALA_E_ARG; }
+    hlala_bam_fill_out slices; hlala_batch_fill_src src;
+    src.read_off = S->read_off.data(); src.chain_off = S->chain_off.data(); src.cigar_count = W->cigCount.data(); src.host = nullptr;
+    if(hz > ha) { slices = window_slices(S, *W, (size_t)u0); src.host = &slices; }
+    std::string herr;
+    const int rc = W->gpuFill.resident(W->gpuFill.state, ctx, u0, u1 - u0, &src, out_batch, stats, &herr);
+    if(rc != HLALA_OK) {
+        if(rc == HLALA_E_STATE && herr.compare(0, 14, "not available:") == 0) S->resident_counts[3]++;
+        say(herr);
+        return rc;
+    }
+    // ---- the names: the host holds every unit's name in its working memory, where fill_units takes it from
+    auto names = [&](int64_t a, int64_t z) {
+        for(int64_t ui = a; ui < z; ui++) {
+            if(mark[ui].load(std::memory_order_relaxed)) continue;
+            const Unit& u = W->units[(size_t)ui];
+            memcpy(S->name_chars.data() + S->name_off[(size_t)ui], u.name, (size_t)u.nameLen); S->name_chars[(size_t)S->name_off[(size_t)ui] + u.nameLen] = 0;
+            mark[ui].store(1, std::memory_order_release);
+        }
+    };
+    constexpr int64_t NCH = 4096;
+    try { parallel_for((u1 - u0 + NCH - 1) / NCH, W->T, [&](int64_t k, int) { names(u0 + k * NCH, std::min(u1, u0 + (k + 1) * NCH)); }); }
+    catch(const std::exception&) { names(u0, u1); }        // (no thread to be had: the batch exists, the copy is finished here)
+    // ---- the units are handed out
+    W->remaining -= W->cover.mark(u0, u1);
+    S->resident_counts[0]++; S->resident_counts[1] += u1 - u0; S->resident_counts[2] += stats->n_pieces;
+    S->transfer_bytes[0] += stats->bytes_h2d; S->transfer_bytes[1] += stats->bytes_d2h;
+    const double dt = since(t0);
+    S->fill_seconds += dt; S->seconds[5] += dt;
+    release_if_handed_out(S, W, g);
+    return HLALA_OK;
+}
+
+namespace {
+// after the release: true when [u0, u1) touches a chunk whose units only ever went out as resident windows -- their host arrays were never written
+bool resident_only(const hlala_seed_batch* Sc, int64_t u0, int64_t u1)
+{
+    hlala_seed_batch* S = const_cast<hlala_seed_batch*>(Sc);
+    if(u1 <= u0) return false;
+    std::lock_guard<std::mutex> g(S->fill_mu);
+    if(S->work || S->host_done.empty()) return false;
+    for(int64_t c = u0 / S->host_uch; c <= (u1 - 1) / S->host_uch && c < (int64_t)S->host_done.size(); c++) if(!S->host_done[(size_t)c]) return true;
+    return false;
+}
+const char* const RESIDENT_ONLY_TEXT = "units that were only handed out as resident windows (hlala_seed_batch_create_resident): the sample's working memory is released and their host arrays were never filled";
 }  // namespace
 
 namespace hlala_host {
@@ -1238,12 +1347,16 @@ try {
     return HLALA_OK;
 } catch(const std::exception& e_) { g_bam_error = dynamic_cast<const Fail*>(&e_) ? std::string(e_.what()) : std::string("hlala_bam_extract_seeds: ") + e_.what(); return HLALA_E_ARG; }
 
-extern "C" int hlala_seed_batch_window(const hlala_seed_batch* S, int64_t first_unit, int32_t n_units, hlala_batch_in* in)
+static int seed_batch_window(const hlala_seed_batch* S, int64_t first_unit, int32_t n_units, hlala_batch_in* in, bool peek);
+extern "C" int hlala_seed_batch_window(const hlala_seed_batch* S, int64_t first_unit, int32_t n_units, hlala_batch_in* in) { return seed_batch_window(S, first_unit, n_units, in, false); }
+extern "C" int hlala_seed_batch_peek_window(const hlala_seed_batch* S, int64_t first_unit, int32_t n_units, hlala_batch_in* in) { return seed_batch_window(S, first_unit, n_units, in, true); }
+static int seed_batch_window(const hlala_seed_batch* S, int64_t first_unit, int32_t n_units, hlala_batch_in* in, const bool peek)
 {
     if(!S || !in || first_unit < 0 || n_units < 0 || first_unit + n_units > S->n_units) { g_bam_error = "hlala_seed_batch_window: units outside the sample"; return HLALA_E_ARG; }
     const int per = S->unpaired ? 1 : 2;
     const size_t r0 = (size_t)first_unit * (size_t)per, nr = (size_t)n_units * (size_t)per;
-    try { ensure_filled(S, first_unit, first_unit + n_units); } catch(const std::exception& e_) { g_bam_error = std::string("hlala_seed_batch_window: ") + e_.what(); return HLALA_E_ARG; }
+    try { ensure_filled(S, first_unit, first_unit + n_units, peek); } catch(const std::exception& e_) { g_bam_error = std::string("hlala_seed_batch_window: ") + e_.what(); return HLALA_E_ARG; }
+    if(resident_only(S, first_unit, first_unit + n_units)) { g_bam_error = std::string("hlala_seed_batch_window: ") + RESIDENT_ONLY_TEXT; return HLALA_E_STATE; }
     if(S->pin_lazy && hlala_host::g_seed_batch_pin_upto) hlala_host::g_seed_batch_pin_upto(const_cast<hlala_seed_batch*>(S), first_unit + n_units);      // (filled first: the pages exist when they are locked)
     const int64_t nb = S->read_off[r0 + nr] - S->read_off[r0], nc = S->chain_off[r0 + nr] - S->chain_off[r0];
     const int64_t ng = S->cigar_off[(size_t)S->chain_off[r0 + nr]] - S->cigar_off[(size_t)S->chain_off[r0]];
@@ -1264,6 +1377,7 @@ extern "C" int hlala_seed_batch_desc(const hlala_seed_batch* S, hlala_batch_in* 
     if(!S || !in) return HLALA_E_ARG;
     if(S->n_units > 0x7FFFFFFFll) { g_bam_error = "hlala_seed_batch_desc: more than 2^31 - 1 units"; return HLALA_E_CAPACITY; }
     try { ensure_filled(S, 0, S->n_units); } catch(const std::exception& e_) { g_bam_error = std::string("hlala_seed_batch_desc: ") + e_.what(); return HLALA_E_ARG; }
+    if(resident_only(S, 0, S->n_units)) { g_bam_error = std::string("hlala_seed_batch_desc: ") + RESIDENT_ONLY_TEXT; return HLALA_E_STATE; }
     // the whole sample: n_chains saturates when the sample holds more than one batch can (hlala_batch_create refuses such a descriptor;
     // hlala_seed_batch_window cuts batches)
     in->n_pairs = (int32_t)S->n_units; in->read_off = S->read_off.data(); in->read_bases = S->read_bases.data(); in->read_quals = S->read_quals.data();
@@ -1285,6 +1399,7 @@ extern "C" int hlala_seed_batch_counts(const hlala_seed_batch* S, int64_t* count
 extern "C" const char* hlala_seed_batch_name(const hlala_seed_batch* S, int64_t unit)
 {
     if(!S || unit < 0 || unit >= S->n_units) return nullptr;
+    if(const std::atomic<uint8_t>* mark = S->name_mark.load(std::memory_order_acquire)) if(mark[unit].load(std::memory_order_acquire)) return S->name_chars.data() + S->name_off[(size_t)unit];      // (in place since a resident window)
     try { ensure_filled(S, unit, unit + 1); } catch(...) { return nullptr; }
     return S->name_chars.data() + S->name_off[(size_t)unit];
 }
@@ -1328,6 +1443,14 @@ extern "C" int hlala_seed_batch_fill_counts(const hlala_seed_batch* S, int64_t c
 {
     if(!S || !counts) return HLALA_E_ARG;
     for(int i = 0; i < 3; i++) counts[i] = S->fill_counts[i];
+    return HLALA_OK;
+}
+extern "C" int hlala_seed_batch_resident_counts(const hlala_seed_batch* Sc, int64_t counts[4])
+{
+    if(!Sc || !counts) return HLALA_E_ARG;
+    hlala_seed_batch* S = const_cast<hlala_seed_batch*>(Sc);
+    std::lock_guard<std::mutex> g(S->fill_mu);
+    for(int i = 0; i < 4; i++) counts[i] = S->resident_counts[i];
     return HLALA_OK;
 }
 // the device milliseconds of the window passes of HLALA_SEEDS_GPU_FILL so far: chain, cigar, names, bases, download

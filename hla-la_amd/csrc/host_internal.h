@@ -88,7 +88,14 @@ struct bam_fill_handle {
     void* state = nullptr;
     int (*window)(void* state, int64_t first_unit, int64_t n_units, const hlala_bam_fill_out* out, hlala_bam_fill_stats* stats, std::string* err) = nullptr;
     void (*destroy)(void* state) = nullptr;
+    // the units as a batch of ctx built on the device (hlala_batch_create_from_fill on the state); HLALA_E_STATE with a text that starts "not available:" where the
+    // context cannot take it (another device): the caller takes the host route.  Null: a library that knows no resident windows.
+    int (*resident)(void* state, hlala_ctx* ctx, int64_t first_unit, int64_t n_units, const hlala_batch_fill_src* src, hlala_batch** out_batch, hlala_batch_fill_stats* stats, std::string* err) = nullptr;
 };
+// The decoder's side of hlala_seed_batch_create_resident (host_bam.cpp): the units [u0, u1) of a sample whose fill state is alive, handed to handle.resident -- the host
+// units inside them filled by the host into the sample's own arrays and passed as slices, the names copied by the host from its working memory, the units accounted as
+// handed out (bam_resident_cover.h).  HLALA_E_STATE with "not available: ..." in *err and nothing changed: no working memory, no live fill state, no resident function.
+int seed_batch_resident(hlala_seed_batch* S, hlala_ctx* ctx, int64_t u0, int64_t u1, hlala_batch** out_batch, hlala_batch_fill_stats* stats, std::string* err);
 typedef int (*bam_fill_hook_t)(void* inflater, const hlala_bam_fill_in* in, int64_t* read_off, int64_t* chain_off, int64_t* cigar_count, int64_t* name_off, bam_fill_handle* handle,
                                hlala_bam_fill_stats* stats, bool* available, std::string* err);
 extern bam_fill_hook_t g_bam_fill_hook;

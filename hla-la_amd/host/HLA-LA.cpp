@@ -10,7 +10,7 @@
 // terminate), this program prints the message to stderr and exits with a non-zero status -- HLA-LA.pl treats any non-zero status as
 // failure (:567-570).  Extra, optional arguments of this program: --devices <gpu,gpu,...> (or --device <gpu>): the batches of the sample are
 // dealt round-robin to one context per listed GPU (a GPU may be listed twice: two contexts on it), results do not depend on the list;
-// --decodeSlots <samples that decode at one time, default CPUs / 16>, --tailPool <k: GPU batches per launch of the widest DP classes>, --pairOverflow <MiB of device scratch for pairs beyond the pairing capacities, default 0: such pairs are refused>, --decodeThreads <host threads of the BAM decoder, default all>, --gpuInflate 0|1 <BGZF blocks inflated on the first listed GPU, default 0>, --gpuInflateKernel 0|1 <which kernel inflates them there: 0 matches resolved in the output buffer, 1 the block's history in LDS; default 0; read only where blocks are inflated on the GPU>, --gpuParse 0|1 <the BAM records found, filtered and parsed there as well, default 0; 1 implies --gpuInflate 1>, --gpuGroup 0|1 <the records grouped by read name there as well, default 0; 1 implies --gpuParse 1>, --gpuSort 0|1 <the units put into read-name order there as well, default 0; 1 implies --gpuGroup 1>, --gpuFill 0|1 <the sample laid out and its windows filled there as well, default 0; 1 implies --gpuSort 1>, --gpuFillWide 0|1 <units with a mate of 17 to 4096 alignments filled there as well, default 0; 1 implies --gpuFill 1>, --verifyCRC 0|1 <the CRC-32 of every BGZF block checked against its inflated bytes, on the GPU where they are inflated there, default 0>, --batchPairs <units per GPU batch>, --rngSeed <base of the end-cell draws>,
+// --decodeSlots <samples that decode at one time, default CPUs / 16>, --tailPool <k: GPU batches per launch of the widest DP classes>, --pairOverflow <MiB of device scratch for pairs beyond the pairing capacities, default 0: such pairs are refused>, --decodeThreads <host threads of the BAM decoder, default all>, --gpuInflate 0|1 <BGZF blocks inflated on the first listed GPU, default 0>, --gpuInflateKernel 0|1 <which kernel inflates them there: 0 matches resolved in the output buffer, 1 the block's history in LDS; default 0; read only where blocks are inflated on the GPU>, --gpuParse 0|1 <the BAM records found, filtered and parsed there as well, default 0; 1 implies --gpuInflate 1>, --gpuGroup 0|1 <the records grouped by read name there as well, default 0; 1 implies --gpuParse 1>, --gpuSort 0|1 <the units put into read-name order there as well, default 0; 1 implies --gpuGroup 1>, --gpuFill 0|1 <the sample laid out and its windows filled there as well, default 0; 1 implies --gpuSort 1>, --gpuFillWide 0|1 <units with a mate of 17 to 4096 alignments filled there as well, default 0; 1 implies --gpuFill 1>, --gpuResident 0|1 <the windows of the batches built on the GPU from the filled sample instead of coming down and going up again, default 0; 1 implies --gpuFill 1>, --verifyCRC 0|1 <the CRC-32 of every BGZF block checked against its inflated bytes, on the GPU where they are inflated there, default 0>, --batchPairs <units per GPU batch>, --rngSeed <base of the end-cell draws>,
 // --loci A,B,... (default: the reference's 17 loci, hla/HLATyper.cpp:42).  Several samples in one call (BASELINE config 4): comma-separated lists of
 // equal length in --sampleID, --outputDirectory, --FASTQ1, --FASTQ2 (--FASTQU); sample i runs on device i % #devices, all samples side by side.
 // Not rebuilt: the --BAM entry (the Perl driver never uses it: it extracts reads itself and passes FASTQ files), read simulation /
@@ -254,6 +254,9 @@ int action_HLA_one(const std::map<std::string, std::string>& arguments, const st
     if(arguments.count("gpuFill") && std::atoi(arguments.at("gpuFill").c_str()) != 0) BAMprocessor.set_gpu_fill(true);
     // --gpuFillWide 1: the units with a mate beyond 16 alignments are laid out and filled there as well (HLALA_SEEDS_GPU_FILL_WIDE); it implies --gpuFill 1
     if(arguments.count("gpuFillWide") && std::atoi(arguments.at("gpuFillWide").c_str()) != 0) BAMprocessor.set_gpu_fill_wide(true);
+    // --gpuResident 1: the windows of the batches are built on the device from the sample's fill state, without coming down and going up again
+    // (hlala_seed_batch_create_resident); it implies --gpuFill 1.  A window the device cannot build (no fill state, a context on another device) goes through the host
+    if(arguments.count("gpuResident") && std::atoi(arguments.at("gpuResident").c_str()) != 0) BAMprocessor.set_gpu_resident(true);
     // --verifyCRC 1: the CRC-32 of every BGZF block is compared with that of its inflated bytes (HLALA_SEEDS_VERIFY_CRC), on the GPU where the blocks are inflated there
     BAMprocessor.set_verify_crc(arguments.count("verifyCRC") && std::atoi(arguments.at("verifyCRC").c_str()) != 0);
     const double loadSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - tStart).count();
@@ -304,6 +307,7 @@ int action_HLA_one(const std::map<std::string, std::string>& arguments, const st
     const auto tInfer = std::chrono::steady_clock::now();
     std::vector<hla::HLATyper::bestGuess> calls = HLAtyper.HLATypeInference(BAMprocessor, outputDirectory_for_HLA, loci, &alignSeconds, &chainErrors);
     const double inferSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - tInfer).count();
+    if(BAMprocessor.gpu_resident()) std::cout << "BAM windows: " << BAMprocessor.windows_resident.load() << " built on the GPU, " << BAMprocessor.windows_host.load() << " through the host\n" << std::flush;
     if(pairOverflow > 0) std::cout << "Pairs beyond the pairing capacities: " << HLAtyper.pair_overflow_counts[1] << " scored in the overflow class, " << HLAtyper.pair_overflow_counts[2] << " refused\n" << std::flush;
     const size_t pairs = longReads.length() ? 0 : (size_t)BAMprocessor.n_units, unpaired = longReads.length() ? (size_t)BAMprocessor.n_units : 0;
     std::cout << timestamp() << "Processed " << pairs << " protoSeeds (read pairs) / " << unpaired << " protoSeeds (unpaired long reads)\n" << std::flush;

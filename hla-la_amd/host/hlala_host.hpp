@@ -411,6 +411,9 @@ public:
     bool gpu_fill() const { return gpu_fill_; }
     void set_gpu_fill_wide(bool on) { gpu_fill_wide_ = on; if(on) set_gpu_fill(true); }   // before openBAM; HLALA_SEEDS_GPU_FILL_WIDE: units with a mate of 17 to HLALA_BAM_FILL_WIDE_MAX alignments are filled on the GPU as well
     bool gpu_fill_wide() const { return gpu_fill_wide_; }
+    void set_gpu_resident(bool on) { gpu_resident_ = on; if(on) set_gpu_fill(true); }     // before openBAM; acquire() builds a batch's window on the device (hlala_seed_batch_create_resident) where the sample's fill state allows it
+    bool gpu_resident() const { return gpu_resident_; }
+    std::atomic<int64_t> windows_resident{0}, windows_host{0};      // batches acquire() created from a window built on the GPU / from a window handed out by the host (the insert-size window is not counted)
     void set_verify_crc(bool on) { verify_crc_ = on; }         // before openBAM; HLALA_SEEDS_VERIFY_CRC: the CRC-32 of every BGZF block is checked, on whichever path inflates it
     bool verify_crc() const { return verify_crc_; }
     int64_t crc_counts[3] = {0, 0, 0};                         // hlala_seed_batch_crc_counts: blocks verified on the GPU, on the host, reported as mismatching by the GPU and checked again on the host
@@ -429,7 +432,8 @@ public:
         (void)hlala_seed_batch_pin(seeds_, std::getenv("HLALA_PIN_WHOLE") ? 1 : 2);
         if(!longReads && n_units == 0) throw std::runtime_error("estimateInsertSize: no complete read pair in " + BAM);
         if(!longReads) {                                                              // insert size from this sample
-            hlala_batch_in first; window(0, n_units < 4000 ? (int32_t)n_units : 4000, first);
+            // (--gpuResident 1: a look at the units, which the batches hand out later -- the fill state outlives this window also where it covers a small sample whole)
+            hlala_batch_in first; window(0, n_units < 4000 ? (int32_t)n_units : 4000, first, gpu_resident_);
             hlala_insert_size_out is; int rc = hlala_estimate_insert_size(ctxs_[0], &first, &is);
             if(rc) throw std::runtime_error(std::string("estimateInsertSize: ") + hlala_last_error(ctxs_[0]));
             IS_mean = is.mean; IS_sd = is.sd;
@@ -454,9 +458,21 @@ public:
         hlala_batch* b = live_.at((size_t)bi);
         int rc = HLALA_OK;
         if(!b) {
-            hlala_batch_in in; window(batch_first_unit(bi), batch_units(bi), in);            // (fills the window's units if nobody asked for them yet)
-            rc = longReadsMode ? hlala_batch_create_unpaired(c, &in, &b) : hlala_batch_create(c, &in, &b);       // (chain_off[0] of the window is the batch's first absolute chain number)
-            if(rc != HLALA_OK) { std::string e = hlala_last_error(c); if(b) hlala_batch_destroy(b); throw std::runtime_error("alignReads: " + e); }
+            // --gpuResident 1: the window is built on the device from the sample's fill state, where there is one on this context's device (it is never page-locked:
+            // its host arrays are not written); "not available": the host route below, as without the switch
+            bool resident = false;
+            if(gpu_resident_) {
+                hlala_batch_fill_stats fs;
+                rc = hlala_seed_batch_create_resident(seeds_, c, batch_first_unit(bi), batch_units(bi), &b, &fs);
+                resident = rc == HLALA_OK;
+                if(!resident && !(rc == HLALA_E_STATE && std::strncmp(hlala_last_error(c), "not available:", 14) == 0)) { std::string e = hlala_last_error(c); if(b) hlala_batch_destroy(b); throw std::runtime_error("alignReads: " + e); }
+                (resident ? windows_resident : windows_host)++;
+            } else windows_host++;
+            if(!resident) {
+                hlala_batch_in in; window(batch_first_unit(bi), batch_units(bi), in);            // (fills the window's units if nobody asked for them yet)
+                rc = longReadsMode ? hlala_batch_create_unpaired(c, &in, &b) : hlala_batch_create(c, &in, &b);       // (chain_off[0] of the window is the batch's first absolute chain number)
+                if(rc != HLALA_OK) { std::string e = hlala_last_error(c); if(b) hlala_batch_destroy(b); throw std::runtime_error("alignReads: " + e); }
+            }
             live_[(size_t)bi] = b; aligned_[(size_t)bi] = 0;
         }
         if(align && !aligned_[(size_t)bi]) {
@@ -495,12 +511,12 @@ public:
     double directory_wait_seconds = 0;      // ... of which waiting for the graph directory's readers
 
 private:
-    void window(int64_t u0, int32_t n, hlala_batch_in& in) const
+    void window(int64_t u0, int32_t n, hlala_batch_in& in, bool peek = false) const
     {
-        if(hlala_seed_batch_window(seeds_, u0, n, &in) != HLALA_OK) throw std::runtime_error(std::string("alignReads: ") + hlala_bam_last_error());
+        if((peek ? hlala_seed_batch_peek_window(seeds_, u0, n, &in) : hlala_seed_batch_window(seeds_, u0, n, &in)) != HLALA_OK) throw std::runtime_error(std::string("alignReads: ") + hlala_bam_last_error());
     }
     std::shared_ptr<GraphDirectory> gdir_;
-    std::string graphDir_; bool extended_; int max_columns_; uint32_t rng_seed_; std::vector<int> devices_; int threads_; bool gpu_inflate_ = false, gpu_parse_ = false, gpu_group_ = false, gpu_sort_ = false, gpu_fill_ = false, gpu_fill_wide_ = false, verify_crc_ = false; int gpu_inflate_kernel_ = HLALA_INFLATE_KERNEL_HBM;
+    std::string graphDir_; bool extended_; int max_columns_; uint32_t rng_seed_; std::vector<int> devices_; int threads_; bool gpu_inflate_ = false, gpu_parse_ = false, gpu_group_ = false, gpu_sort_ = false, gpu_fill_ = false, gpu_fill_wide_ = false, gpu_resident_ = false, verify_crc_ = false; int gpu_inflate_kernel_ = HLALA_INFLATE_KERNEL_HBM;
     hlala_graph_file* graph_ = nullptr; hlala_contigs_file* contigs_ = nullptr; const std::vector<hlala_bam_interval>& intervals_;      // owned by gdir_
     hlala_seed_batch* seeds_ = nullptr; std::vector<hlala_ctx*> ctxs_; hlala_comm* comm_ = nullptr; int tail_pool_ = 1; int64_t pair_overflow_ = 0; bool owns_ctx_ = true; std::string BAM_;
     int32_t batchPairs_ = 1; std::vector<hlala_batch*> live_; std::vector<char> aligned_;       // aligned_[bi]: hlala_align_batch has been queued for live_[bi]

@@ -766,6 +766,25 @@ typedef struct {
  * device.  Neither handle may be in another call meanwhile: a handle serves one call at a time.  Without this call nothing of it is allocated or launched. */
 int  hlala_batch_create_from_fill(hlala_ctx* ctx, hlala_bam_fill* fill, int64_t first_unit, int64_t n_units, const hlala_batch_fill_src* src, hlala_batch** out,
                                   hlala_batch_fill_stats* stats);
+/* The same for a sample decoded with HLALA_SEEDS_GPU_FILL, whose fill state is the decoder's own: units [first_unit, first_unit + n_units) of the sample as a batch of
+ * the context, without the window coming down (hlala_seed_batch_window) and going up again (hlala_batch_create).  The decoder fills the window's host units into the
+ * sample's own arrays and hands their ranges over as hlala_batch_create_from_fill takes them; it copies the names of the window's units into place itself, from its
+ * working memory (hlala_seed_batch_name then needs no fill), and counts the units as handed out: the working memory and the fill state are released once every unit
+ * has been handed out, by this call or by hlala_seed_batch_window / _desc, in any order and mixture; a window may be asked for twice.  chain_off[0] of the window is the
+ * batch's first absolute chain number, as with hlala_batch_create.
+ * HLALA_E_STATE with a text (hlala_last_error(ctx)) that starts "not available:" and nothing changed where the sample has no live fill state -- decoded without the
+ * flag, handed back to the host by an earlier stage, every unit already handed out -- or the context sits on another device than the fill state: the caller takes
+ * hlala_seed_batch_window + hlala_batch_create; this is no error of the sample.  Everything hlala_batch_create refuses comes back with its code and text.
+ * After the release hlala_seed_batch_window / _desc over units that only ever went out through this call answer HLALA_E_STATE (hlala_bam_last_error says so): their host
+ * arrays were never written.  Before the release they fill the units as always.  A sample serves one such call at a time (others wait). */
+int  hlala_seed_batch_create_resident(hlala_seed_batch* s, hlala_ctx* ctx, int64_t first_unit, int32_t n_units, hlala_batch** out, hlala_batch_fill_stats* stats);
+/* hlala_seed_batch_window for a caller that only looks at the units -- the insert-size estimate over the first 4000 -- and hands them out later: on a sample that can build
+ * resident windows the units are filled into the host arrays but do not count as handed out, so the fill state outlives a window that covers the whole of a small
+ * sample, and a later hlala_seed_batch_create_resident (or hlala_seed_batch_window, which then counts them) over the same units is legal and gives the same batch.  On
+ * any other sample it is hlala_seed_batch_window. */
+int  hlala_seed_batch_peek_window(const hlala_seed_batch* s, int64_t first_unit, int32_t n_units, hlala_batch_in* in);
+/* counts[4]: windows built by hlala_seed_batch_create_resident, units in them, pieces of host units staged for them, calls that answered "not available" */
+int  hlala_seed_batch_resident_counts(const hlala_seed_batch* s, int64_t counts[4]);
 /* The input arrays of any batch that hlala_batch_create / _unpaired / _from_fill made, downloaded: the offsets as the batch holds them (32-bit, rebased), bases
  * (unpacked), qualities, primaries, chain_read, the five chain arrays, cigar_off and cigar.  The four counts are always written; any pointer may be NULL (that array
  * is then not transferred), so a first call with NULL pointers sizes the arrays: read_off, chain_off [n_reads + 1], read_primary [n_reads], read_bases, read_quals
@@ -1117,7 +1136,7 @@ int  hlala_abi_sizeof(const char* struct_name);
  * Symbols that are purely additive no longer change it (hlala_set_pair_overflow; hlala_bgzf_inflate_crc, HLALA_SEEDS_VERIFY_CRC, hlala_seed_batch_crc_counts;
  * hlala_bam_group / _rounds, HLALA_SEEDS_GPU_GROUP, hlala_seed_batch_group_counts; hlala_bam_name_order, HLALA_SEEDS_GPU_SORT, hlala_seed_batch_sort_counts;
  * hlala_bam_fill_create / _window / _destroy / _last_error, HLALA_SEEDS_GPU_FILL, hlala_seed_batch_fill_counts;
- * hlala_batch_create_from_fill, hlala_debug_batch_inputs;
+ * hlala_batch_create_from_fill, hlala_debug_batch_inputs; hlala_seed_batch_create_resident, hlala_seed_batch_peek_window, hlala_seed_batch_resident_counts;
  * hlala_bam_fill_create_wide, hlala_bam_fill_wide_stats, HLALA_SEEDS_GPU_FILL_WIDE, hlala_seed_batch_fill_wide_counts;
  * hlala_inflater_set_kernel / _get_kernel): a caller
  * detects them by the presence of the symbol.  A caller compares

@@ -31,7 +31,11 @@ HLALA_SEEDS_GPU_FILL alone and with HLALA_SEEDS_GPU_FILL | HLALA_SEEDS_GPU_FILL_
 host units, the layout + fill phase and the wall clock of each.
 --inflate-kernels hbm,lds (its output is meant for profiles/inflate_lds_gpu.txt): the named inflate kernels (hlala_inflater_set_kernel) alternate on ONE inflater -- in the
 decoder paths `gpu` and `gpu+parse`, which run once per kernel beside the host decoder in every round, and in hlala_bgzf_inflate on all blocks in one call, which prints
-upload / kernel / download / wall, blocks/s and GB/s per kernel and run (one warm-up each) and checks that the kernels leave the same bytes.  Nothing else runs."""
+upload / kernel / download / wall, blocks/s and GB/s per kernel and run (one warm-up each) and checks that the kernels leave the same bytes.  Nothing else runs.
+--resident-decoder (the seventh path; its output is meant for profiles/bam_resident_decoder_gpu.txt): the generated BAM decoded with all of the sixth path's flags plus
+HLALA_SEEDS_GPU_FILL_WIDE and HLALA_BAM_EAGER unset, then "window asked for -> batch created" summed over the sample's windows of --resident-window units on a context of the
+sample's world: hlala_seed_batch_window + hlala_batch_create (the sixth path) against hlala_seed_batch_create_resident, alternating in one call, one warm-up and --runs timed
+runs each, a fresh decode per run; PCIe bytes each way from hlala_seed_batch_transfer_bytes.  Nothing else runs."""
 import argparse
 import os
 import sys
@@ -376,6 +380,61 @@ def wide_bam(P, lib, args):
     shutil.rmtree(tmp, ignore_errors=True)
 
 
+def resident_decoder(P, lib, inf, w, bam, intervals, args):
+    """--resident-decoder (the seventh path; its output is meant for profiles/bam_resident_decoder_gpu.txt): the BAM is decoded with every GPU stage, HLALA_BAM_EAGER unset,
+    and its windows of --resident-window units become batches of a context of the sample's world -- by hlala_seed_batch_window + hlala_batch_create (the sixth path, the
+    sample page-locked window by window as the host program does) and by hlala_seed_batch_create_resident (the seventh), alternating in one call, one warm-up and --runs
+    timed runs each, a fresh decode per run.  Printed per run: the wall clock from "window asked for" to "batch created" summed over the windows, and the bytes that
+    crossed PCIe each way during the walk (hlala_seed_batch_transfer_bytes; for the sixth path plus what hlala_batch_create uploads, computed from the window)."""
+    import ctypes as C
+    assert not os.environ.get("HLALA_BAM_EAGER"), "the seventh path is measured with HLALA_BAM_EAGER unset"
+    t0 = time.time()
+    ctx = P.Context(w["graph"], w["contigs"], device=args.device)
+    print("context of the sample's world: %.1f s" % (time.time() - t0))
+    flags = P.SEEDS_PACKED | P.SEEDS_GPU_PARSE | P.SEEDS_GPU_GROUP | P.SEEDS_GPU_SORT | P.SEEDS_GPU_FILL | P.SEEDS_GPU_FILL_WIDE
+    lib.hlala_seed_batch_pin.argtypes = [C.c_void_p, C.c_int]
+    lib.hlala_batch_destroy.argtypes = [C.c_void_p]
+    Wn = args.resident_window
+    res = {"sixth": [], "resident": []}; moved = {}; info = rcnt = None
+    for run in range(args.runs + 1):
+        for path in ("sixth", "resident"):
+            S = inf.bam_open_seeds(bam, intervals, threads=args.threads, flags=flags)
+            N = S.n_units; wins = [(u, min(Wn, N - u)) for u in range(0, N, Wn)]
+            if path == "sixth":
+                lib.hlala_seed_batch_pin(S.h, 2)
+            up0, down0 = S.transfer_bytes(); total = 0.0; up = 0
+            for u0, n in wins:
+                b = C.c_void_p()
+                t = time.perf_counter()
+                if path == "sixth":
+                    d = S.window(u0, n)
+                    rc = lib.hlala_batch_create(ctx.h, C.byref(d), C.byref(b)); assert rc == 0, ctx.last_error()
+                    total += time.perf_counter() - t
+                    nr = 2 * n; nb = int(d.read_off[nr] - d.read_off[0]); c0, c1 = int(d.chain_off[0]), int(d.chain_off[nr]); ng = int(d.cigar_off[c1] - d.cigar_off[c0])
+                    up += (nb + nr + 1) // 2 + nb + 17 * (c1 - c0) + 4 * ng + 4 * (3 * nr + 2 * (c1 - c0) + 3)
+                else:
+                    st = P.BatchFillStats()
+                    rc = lib.hlala_seed_batch_create_resident(S.h, ctx.h, u0, n, C.byref(b), C.byref(st)); assert rc == 0, ctx.last_error()
+                    total += time.perf_counter() - t
+                lib.hlala_batch_destroy(b)
+            up1, down1 = S.transfer_bytes()
+            if run:
+                res[path].append(total * 1e3); moved[path] = (up + up1 - up0, down1 - down0)
+                print("%-9s run %d: window asked for -> batch created, all %d windows: %.1f ms; PCIe up %.3f GB, down %.3f GB" % (path, run, len(wins), total * 1e3, (up + up1 - up0) / 1e9, (down1 - down0) / 1e9))
+            info = (N, S.fill_counts(), S.fill_wide_counts())
+            if path == "resident":
+                rcnt = S.resident_counts()
+            S.close()
+    print("the sample: %d units; filled on the GPU %d, host units %d; wide units %d; resident windows %d with %d units, %d pieces of host units staged, %d fell back; windows of %d units" % (
+        info[0], info[1][0], info[1][1], info[2][0], rcnt[0], rcnt[1], rcnt[2], rcnt[3], Wn))
+    for path in ("sixth", "resident"):
+        v = res[path]
+        print("window asked for -> batch created, %s path: median %.1f ms, range %.1f .. %.1f of %d runs; PCIe up %.3f GB, down %.3f GB per run" % (
+            path, float(np.median(v)), min(v), max(v), len(v), moved[path][0] / 1e9, moved[path][1] / 1e9))
+    print("every resident run below every sixth-path run: %s (slowest resident %.1f ms, fastest sixth %.1f ms)" % (max(res["resident"]) < min(res["sixth"]), max(res["resident"]), min(res["sixth"])))
+    ctx.close()
+
+
 def out_bytes(off, r0, r1):
     """the bytes hlala_batch_create uploads for reads [r0, r1) of a packed sample: packed bases, qualities, 17 bytes per chain + its CIGAR, the 32-bit offset arrays"""
     nb = int(off["read_off"][r1] - off["read_off"][r0]); nc = int(off["chain_off"][r1] - off["chain_off"][r0]); ng = int(off["cigar_count"][r1] - off["cigar_count"][r0])
@@ -385,7 +444,8 @@ def out_bytes(off, r0, r1):
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--resident-units", type=int, default=0, help="only hlala_batch_create_from_fill against hlala_bam_fill_window + hlala_batch_create, on a synthetic fill state of this many pairs")
-    ap.add_argument("--resident-window", type=int, default=262144, help="units per window of --resident-units")
+    ap.add_argument("--resident-window", type=int, default=262144, help="units per window of --resident-units and --resident-decoder")
+    ap.add_argument("--resident-decoder", action="store_true", help="only the seventh path: the generated BAM decoded with every GPU stage, its windows through hlala_seed_batch_window + hlala_batch_create against hlala_seed_batch_create_resident")
     ap.add_argument("--wide-units", type=int, default=0, help="only hlala_bam_fill_create_wide against hlala_bam_fill_create with the wide units as host units, on a synthetic fill state of this many pairs")
     ap.add_argument("--wide-bam-pairs", type=int, default=0, help="only the decoder with HLALA_SEEDS_GPU_FILL against HLALA_SEEDS_GPU_FILL | HLALA_SEEDS_GPU_FILL_WIDE on a BAM of this many pairs written here")
     ap.add_argument("--wide-share", type=float, default=0.05, help="share of the units of --wide-units / --wide-bam-pairs that carry 17 to 200 alignments on mate 0")
@@ -445,6 +505,14 @@ def main():
     print("host engine: %s; decoder threads: %s" % (lib.hlala_bam_inflate_engine().decode(), args.threads or "default"))
     inf = None if args.no_gpu else P.Inflater(lib, device=args.device, chunk_bytes=args.chunk_mb << 20)
     keys = ("index", "inflate", "parse", "group", "name_sort", "layout")
+    if args.resident_decoder:
+        assert inf, "--resident-decoder needs a GPU"
+        resident_decoder(P, lib, inf, w, bam, intervals, args)
+        inf.close()
+        if tmp:
+            import shutil
+            shutil.rmtree(tmp, ignore_errors=True)
+        return
 
     def run(label, opener, timed):
         t = time.time(); S = opener(); wall = time.time() - t
