@@ -181,6 +181,54 @@ def filter_positions(lib, e, params=None):
     return use[:o.n_pos], ign[:o.n_reads], {k: int(getattr(st, k)) for k, _ in FilterStats._fields_}
 
 
+FILTER_GPU_MAX_BUCKET = 4096       # HLALA_FILTER_GPU_MAX_BUCKET
+FILTER_GPU_COUNTS = ("buckets", "buckets_sorted", "largest_bucket", "heap_sorts", "bytes_up", "bytes_down")
+
+
+def _filter_call(call, what, last_error, e, params, raw):
+    """one filter entry point on the dict Batch.exon_positions() returns.  raw: (rc, text, pos_use, read_ignored, stats, counts) whatever the code, the two arrays
+    filled with 0xAA before the call (a refusal must leave them so); otherwise (pos_use, read_ignored, stats, counts), a code other than 0 raised with .code set."""
+    o, keep = exon_positions_struct(e)
+    prm = params or default_filter_params()
+    use = np.full(max(1, o.n_pos), 0xAA, np.uint8); ign = np.full(max(1, o.n_reads), 0xAA, np.uint8); st = FilterStats(); cn = (C.c_int64 * 6)()
+    rc = call(C.byref(o), C.byref(prm), use.ctypes.data_as(c_u8p), ign.ctypes.data_as(c_u8p), C.byref(st), cn)
+    out = (use[:o.n_pos], ign[:o.n_reads], {k: int(getattr(st, k)) for k, _ in FilterStats._fields_}, dict(zip(FILTER_GPU_COUNTS, (int(x) for x in cn))))
+    if raw:
+        return (int(rc), last_error() if rc != 0 else "") + out
+    if rc != 0:
+        err = HlalaError(f"{what} failed ({rc}): {last_error()}"); err.code = int(rc)
+        raise err
+    return out
+
+
+def filter_positions_gpu(ctx, e, params=None, raw=False):
+    """hlala_filter_positions_gpu on the dict Batch.exon_positions() returns: (pos_use, read_ignored, stats dict, counts dict), every output equal to
+    filter_positions.  HLALA_E_CAPACITY (-4; .code of the exception, text "not available: ...") for an exon position with more than FILTER_GPU_MAX_BUCKET entries:
+    take filter_positions then."""
+    fn = ctx.lib.hlala_filter_positions_gpu
+    fn.argtypes = [C.c_void_p, C.POINTER(ExonPositionsOut), C.POINTER(FilterParams), c_u8p, c_u8p, C.POINTER(FilterStats), C.POINTER(C.c_int64)]; fn.restype = C.c_int
+    return _filter_call(lambda *a: fn(ctx.h, *a), "hlala_filter_positions_gpu", ctx.last_error, e, params, raw)
+
+
+def filter_gpu_times(ctx, enable=True):
+    """hlala_filter_gpu_times: device milliseconds of the launches of the last filter_positions_gpu on ctx (zeros if it was not timed); enable: time the next calls"""
+    ms = (C.c_double * 6)()
+    ctx.lib.hlala_filter_gpu_times.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double)]
+    if ctx.lib.hlala_filter_gpu_times(ctx.h, int(bool(enable)), ms) != 0:
+        raise HlalaError("hlala_filter_gpu_times failed")
+    return dict(zip(("mapq_keys", "sort_scan", "first20", "reads", "coverage", "use"), (float(x) for x in ms)))
+
+
+def host_filter_model(e, params=None, tie_rule=0, raw=False):
+    """hlala_host_filter_model (libhlala_host.so): the launches of filter_positions_gpu run serially on the host, same outputs; tie_rule 1 (tests only) orders a
+    bucket by a stable descending sort instead of the library's introsort."""
+    h = _host_lib()
+    fn = h.hlala_host_filter_model
+    fn.argtypes = [C.POINTER(ExonPositionsOut), C.POINTER(FilterParams), c_u8p, c_u8p, C.POINTER(FilterStats), C.POINTER(C.c_int64), C.c_int32]; fn.restype = C.c_int
+    h.hlala_host_last_error.restype = C.c_char_p
+    return _filter_call(lambda *a: fn(*a, int(tie_rule)), "hlala_host_filter_model", lambda: h.hlala_host_last_error().decode(errors="replace"), e, params, raw)
+
+
 def _graph_from_handle(lib, h):
     d = GraphDesc()
     lib.hlala_graph_file_desc.argtypes = [C.c_void_p, C.POINTER(GraphDesc)]
@@ -1159,6 +1207,7 @@ EXPORTED_SYMBOLS = [
     "hlala_bam_fill_create", "hlala_bam_fill_window", "hlala_bam_fill_last_error", "hlala_bam_fill_destroy", "hlala_seed_batch_fill_counts", "hlala_seed_batch_fill_ms",
     "hlala_batch_create_from_fill", "hlala_debug_batch_inputs", "hlala_seed_batch_create_resident", "hlala_seed_batch_peek_window", "hlala_seed_batch_resident_counts",
     "hlala_bam_fill_create_wide", "hlala_bam_fill_wide_stats", "hlala_seed_batch_fill_wide_counts",
+    "hlala_filter_positions_gpu", "hlala_filter_gpu_times",
     "hlala_locus_cluster_kmers", "hlala_type_locus", "hlala_kmer_presence", "hlala_kmer_keep_reads", "hlala_kmer_presence_kept", "hlala_kmer_forget_reads", "hlala_unit_alignment_stats", "hlala_typer_write_summary", "hlala_typer_begin_output", "hlala_locus_write_files", "hlala_locus_write_pairs_file", "hlala_typer_end_output",
 ]
 

@@ -38,6 +38,7 @@
 #include "kernel_bamnameorder.hip"
 #include "kernel_bamfill.hip"
 #include "kernel_bamresident.hip"
+#include "kernel_filter.hip"
 
 namespace hlala {
 size_t proj_slab_bytes_host(int stride, int maxNodesPerLevel) { return proj_slab_bytes(stride, maxNodesPerLevel); }
@@ -124,6 +125,7 @@ struct hlala_ctx {
     // reads kept for the k-mer questions (hlala_kmer_keep_reads): one chunk per call, blocks of the pool
     struct KeptReads { uint8_t* store = nullptr; long long* start = nullptr; int* length = nullptr; int n = 0; };
     std::vector<KeptReads> kept;
+    bool flt_timed = false; double flt_ms[6] = {0, 0, 0, 0, 0, 0};      // hlala_filter_gpu_times: the launches of the last hlala_filter_positions_gpu, timed only on request
     std::string err;
 };
 
@@ -1888,6 +1890,141 @@ extern "C" int hlala_pair_loglik(hlala_ctx* c, const double* LL, const int32_t* 
     ReaderScope rscope_(c, nullptr);
     if(!c || !LL || !mism) return HLALA_E_ARG;
     return pair_loglik_impl(c, LL, mism, nullptr, nullptr, C, R, pairLL, misAvg, misMin, nullptr, nullptr, nullptr, nullptr);
+}
+
+// ---- the typer's read / allele filters on the device (kernel_filter.hip; filter_gpu_core.h; the host's hlala_filter_positions is the specification)
+extern "C" int hlala_filter_positions_gpu(hlala_ctx* c, const hlala_exon_positions_out* pos, const hlala_filter_params* prm, uint8_t* pos_use, uint8_t* read_ignored, hlala_filter_stats* stats,
+                                          int64_t* counts)
+{
+    using namespace hlala_filter;
+    DEV_GUARD(c);
+    ReaderScope rscope_(c, nullptr);
+    if(!c) return HLALA_E_ARG;
+    if(const char* a = flt_check_args(pos, prm, pos_use)) { c->err = std::string("hlala_filter_positions_gpu: ") + a; return HLALA_E_ARG; }
+    int64_t Cn[FC_N] = {0, 0, 0, 0, 0, 0};
+    for(double& m : c->flt_ms) m = 0;
+    if(pos->n_reads == 0) {                                     // the host writes nothing but zeroed counters
+        if(stats) memset(stats, 0, sizeof(*stats));
+        if(counts) memcpy(counts, Cn, sizeof(Cn));
+        return HLALA_OK;
+    }
+    const u32 nr = (u32)pos->n_reads, np = (u32)pos->n_pos, nch = (u32)pos->n_chars;
+    std::vector<void*> tmp; int rc = 0;
+    hipEvent_t ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    // (everything queued -- uploads from the caller's arrays, kernels on the scratch -- ends before the blocks go back to the pool)
+    auto done = [&](int r) { (void)hipStreamSynchronize(c->active); for(void* p : tmp) pool_release(c, p); for(hipEvent_t e : ev) if(e) (void)hipEventDestroy(e); return r; };
+    auto mark = [&](int k) { if(c->flt_timed && ev[k]) (void)hipEventRecord(ev[k], c->active); };
+    if(c->flt_timed) for(hipEvent_t& e : ev) HIP_TRY_F(c, hipEventCreate(&e), done);
+    double pc[256]; hlala_host::filter_phred_table(pc);        // the host's exp / log: the device only compares
+    FltIn I; memset(&I, 0, sizeof(I)); I.nReads = nr; I.nPos = np; I.nChars = nch; I.P = *prm;
+    int32_t *dPosOff, *dPosExon, *dGenoOff; uint8_t *dMapq, *dMate = nullptr, *dChars, *dRev = nullptr; double *dWok, *dPc;
+    if((rc = dev_upload(c, tmp, pos->pos_off, (size_t)nr + 1, &dPosOff))) return done(rc);
+    if((rc = dev_upload(c, tmp, pos->pos_exon, (size_t)np, &dPosExon))) return done(rc);
+    if((rc = dev_upload(c, tmp, pos->pos_mapq, (size_t)np, &dMapq))) return done(rc);
+    if(pos->pos_mate && (rc = dev_upload(c, tmp, pos->pos_mate, (size_t)np, &dMate))) return done(rc);
+    if((rc = dev_upload(c, tmp, pos->geno_off, (size_t)np + 1, &dGenoOff))) return done(rc);
+    if((rc = dev_upload(c, tmp, pos->geno_chars, (size_t)nch, &dChars))) return done(rc);
+    if((rc = dev_upload(c, tmp, pos->read_weighted_ok, (size_t)2 * nr, &dWok))) return done(rc);
+    if(prm->long_read_strand_filter && (rc = dev_upload(c, tmp, pos->read_reverse, (size_t)2 * nr, &dRev))) return done(rc);
+    if((rc = dev_upload(c, tmp, pc, (size_t)256, &dPc))) return done(rc);
+    I.posOff = dPosOff; I.posExon = dPosExon; I.posMapq = dMapq; I.posMate = dMate; I.genoOff = dGenoOff; I.genoChars = dChars; I.wok = dWok; I.readReverse = dRev; I.pc = dPc;
+    Cn[FC_BYTES_UP] = flt_bytes_up(pos, prm); Cn[FC_BYTES_DOWN] = flt_bytes_down(pos, read_ignored);
+    FltWork W; memset(&W, 0, sizeof(W));
+    if((rc = dev_alloc(c, tmp, (size_t)np, &W.ok))) return done(rc);
+    if((rc = dev_alloc(c, tmp, (size_t)np, &W.posRead))) return done(rc);
+    if((rc = dev_alloc(c, tmp, (size_t)np, &W.key))) return done(rc);
+    if((rc = dev_alloc(c, tmp, (size_t)np, &W.val))) return done(rc);
+    if((rc = dev_alloc(c, tmp, (size_t)np, &W.sorted))) return done(rc);
+    if((rc = dev_alloc(c, tmp, (size_t)np, &W.entRep))) return done(rc);
+    if((rc = dev_alloc(c, tmp, (size_t)np, &W.entIgnore, true))) return done(rc);
+    if((rc = dev_alloc(c, tmp, (size_t)np, &W.posFlag, true))) return done(rc);
+    if((rc = dev_alloc(c, tmp, (size_t)np, &W.posUse))) return done(rc);
+    if((rc = dev_alloc(c, tmp, (size_t)nr, &W.kicked, true))) return done(rc);
+    if((rc = dev_alloc(c, tmp, (size_t)nr, &W.kickedRobust, true))) return done(rc);
+    if((rc = dev_alloc(c, tmp, (size_t)nr, &W.ignoreRead, true))) return done(rc);
+    if((rc = dev_alloc(c, tmp, (size_t)FS_N, &W.stats, true))) return done(rc);
+    if((rc = dev_alloc(c, tmp, (size_t)FM_N, &W.misc, true))) return done(rc);
+    u32 misc[FM_N];
+    auto read_misc = [&]() -> int {
+        HIP_TRY(c, hipMemcpyAsync(misc, W.misc, sizeof(misc), hipMemcpyDeviceToHost, c->active)); HIP_TRY(c, hipStreamSynchronize(c->active));
+        if(misc[FM_BAD]) { c->err = std::string("hlala_filter_positions_gpu: ") + flt_bad_text(misc[FM_BAD]); return HLALA_E_ARG; }
+        return HLALA_OK;
+    };
+    mark(0);
+    hipLaunchKernelGGL(k_flt_mapq, dim3(((nr > np ? nr : np) + 255u) / 256u), dim3(256), 0, c->active, I, W);
+    if((rc = check_launch(c, "k_flt_mapq"))) return done(rc);
+    if((rc = read_misc())) return done(rc);
+    const u32 nb = misc[FM_NB];                                 // exon positions up to the last one with an entry; 0: no position passed the mapq test
+    u32 nOK = 0;
+    if(nb > (1u << 26)) { c->err = "not available: hlala_filter_positions_gpu takes exon positions below 2^26, the locus has one of " + std::to_string(nb - 1); return done(HLALA_E_CAPACITY); }
+    if(nb > 0) {
+        if((rc = dev_alloc(c, tmp, (size_t)nb + 1, &W.hist, true))) return done(rc);
+        if((rc = dev_alloc(c, tmp, (size_t)nb + 1, &W.bOff))) return done(rc);
+        hipLaunchKernelGGL(k_flt_keys, dim3((np + 255u) / 256u), dim3(256), 0, c->active, I, W, nb);
+        hipLaunchKernelGGL(k_flt_largest, dim3((nb + 255u) / 256u), dim3(256), 0, c->active, W, nb);
+        if((rc = check_launch(c, "k_flt_keys / k_flt_largest"))) return done(rc);
+        mark(1);
+        int bits = 1; while(bits < 32 && (nb >> bits)) bits++;
+        size_t cubSort = 0, cubScan = 0; void* dCub = nullptr; u32* dKeyOut = nullptr;
+        if((rc = dev_alloc(c, tmp, (size_t)np, &dKeyOut))) return done(rc);
+        HIP_TRY_F(c, hipcub::DeviceRadixSort::SortPairs(nullptr, cubSort, (const u32*)W.key, dKeyOut, (const u32*)W.val, W.sorted, (int)np, 0, bits, c->active), done);
+        HIP_TRY_F(c, hipcub::DeviceScan::ExclusiveSum(nullptr, cubScan, (const u32*)W.hist, W.bOff, (int)(nb + 1), c->active), done);
+        const size_t cubBytes = cubSort > cubScan ? cubSort : cubScan;
+        { unsigned char* q = nullptr; if((rc = dev_alloc(c, tmp, cubBytes ? cubBytes : 1, &q))) return done(rc); dCub = q; }
+        size_t cb = cubBytes;
+        HIP_TRY_F(c, hipcub::DeviceRadixSort::SortPairs(dCub, cb, (const u32*)W.key, dKeyOut, (const u32*)W.val, W.sorted, (int)np, 0, bits, c->active), done);
+        cb = cubBytes;
+        HIP_TRY_F(c, hipcub::DeviceScan::ExclusiveSum(dCub, cb, (const u32*)W.hist, W.bOff, (int)(nb + 1), c->active), done);
+        HIP_TRY_F(c, hipMemcpyAsync(&nOK, W.bOff + nb, sizeof(u32), hipMemcpyDeviceToHost, c->active), done);
+        if((rc = read_misc())) return done(rc);
+        Cn[FC_BUCKETS] = misc[FM_BUCKETS]; Cn[FC_LARGEST] = misc[FM_LARGEST];
+        if(misc[FM_LARGEST] > FLT_MAX_BUCKET) {
+            c->err = "not available: an exon position with " + std::to_string(misc[FM_LARGEST]) + " entries, more than HLALA_FILTER_GPU_MAX_BUCKET = " + std::to_string(FLT_MAX_BUCKET);
+            return done(HLALA_E_CAPACITY);
+        }
+        if(nOK > np) { c->err = "hlala_filter_positions_gpu: the buckets hold more entries than there are positions"; return done(HLALA_E_DEVICE); }
+    }
+    const u32 cap = ((misc[FM_LARGEST] + 63u) / 64u) * 64u;     // LDS of the bucket kernels: what the largest bucket needs
+    mark(2);
+    if(nb > 0 && nOK > 0) {
+        hipLaunchKernelGGL(k_flt_first20, dim3(nb), dim3(64), flt_lds_bytes(cap), c->active, I, W, nb, cap);
+        if((rc = check_launch(c, "k_flt_first20"))) return done(rc);
+    }
+    mark(3);
+    if(prm->filter_first20) {
+        hipLaunchKernelGGL(k_flt_reads, dim3((nr + 255u) / 256u), dim3(256), 0, c->active, I, W);
+        if((rc = check_launch(c, "k_flt_reads"))) return done(rc);
+    }
+    mark(4);
+    if(nb > 0 && nOK > 0) {
+        hipLaunchKernelGGL(k_flt_coverage, dim3(nb), dim3(64), flt_lds_bytes(cap), c->active, I, W, nb, cap);
+        if((rc = check_launch(c, "k_flt_coverage"))) return done(rc);
+    }
+    mark(5);
+    if(np > 0) {
+        hipLaunchKernelGGL(k_flt_use, dim3((np + 255u) / 256u), dim3(256), 0, c->active, I, W, nOK);
+        if((rc = check_launch(c, "k_flt_use"))) return done(rc);
+    }
+    mark(6);
+    unsigned long long S[FS_N];
+    HIP_TRY_F(c, hipMemcpyAsync(S, W.stats, sizeof(S), hipMemcpyDeviceToHost, c->active), done);
+    if((rc = read_misc())) return done(rc);                     // (nothing of the caller's has been written yet)
+    Cn[FC_SORTED] = misc[FM_SORTED]; Cn[FC_HEAPS] = misc[FM_HEAPS];
+    if(np > 0) HIP_TRY_F(c, hipMemcpyAsync(pos_use, W.posUse, (size_t)np, hipMemcpyDeviceToHost, c->active), done);
+    if(read_ignored) HIP_TRY_F(c, hipMemcpyAsync(read_ignored, W.ignoreRead, (size_t)nr, hipMemcpyDeviceToHost, c->active), done);
+    HIP_TRY_F(c, hipStreamSynchronize(c->active), done);
+    if(c->flt_timed) for(int k = 0; k < 6; k++) { float ms = 0; if(hipEventElapsedTime(&ms, ev[k], ev[k + 1]) == hipSuccess) c->flt_ms[k] = ms; }
+    if(stats) { int64_t* o = (int64_t*)stats; for(int k = 0; k < FS_N; k++) o[k] = (int64_t)S[k]; }
+    if(counts) memcpy(counts, Cn, sizeof(Cn));
+    return done(HLALA_OK);
+}
+// the launches of the last hlala_filter_positions_gpu as the header lists them (zeros when that call was not timed); enable: whether the next calls are timed
+extern "C" int hlala_filter_gpu_times(hlala_ctx* c, int enable, double* ms)
+{
+    if(!c) return HLALA_E_ARG;
+    if(ms) memcpy(ms, c->flt_ms, sizeof(c->flt_ms));
+    c->flt_timed = enable != 0;
+    return HLALA_OK;
 }
 
 // ---- known-answer kernels

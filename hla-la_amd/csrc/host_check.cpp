@@ -12,6 +12,7 @@
 #include "bam_nameorder_model.h"
 #include "bam_fill_model.h"
 #include "bam_resident_model.h"
+#include "filter_gpu_model.h"
 
 static thread_local std::string g_err;
 
@@ -190,6 +191,18 @@ int hlala_host_bam_fill_wide_adversary(int32_t n, int32_t* score)
     if(n < 0 || (n && !score)) return -1;
     hlala_bamfill::fil_adversary((uint32_t)n, score);
     return 0;
+}
+// The launches of hlala_filter_positions_gpu (kernel_filter.hip) run serially over the same core (filter_gpu_model.h): its arguments, return codes and every output,
+// counts[6] included, without a device.  tie_rule 0: the rule; 1 (tests only): a stable descending sort in fil_sort_wide's place.
+int hlala_host_filter_model(const hlala_exon_positions_out* pos, const hlala_filter_params* prm, uint8_t* pos_use, uint8_t* read_ignored, hlala_filter_stats* stats, int64_t* counts,
+                            int32_t tie_rule)
+{
+    std::string why;
+    int rc = HLALA_E_ARG;
+    try { rc = hlala_filter::filter_model(pos, prm, pos_use, read_ignored, stats, counts, tie_rule, &why); }
+    catch(const std::exception&) { why = "out of memory"; rc = HLALA_E_ARG; }
+    g_err = why.empty() ? std::string() : (why.rfind("not available:", 0) == 0 ? why : "hlala_host_filter_model: " + why);
+    return rc;
 }
 // What hlala_batch_create / _unpaired does to a window before it uploads it, and so what hlala_batch_create_from_fill's kernels (kernel_bamresident.hip) must leave in
 // the batch: the five 32-bit arrays, the smallest index of every violation class, the return code and (hlala_host_last_error) its text, without a device.

@@ -1,10 +1,11 @@
 // host_filters.cpp -- read / allele filters between the exon positions and the likelihoods (hla/HLATyper.cpp:1496-1862, :2102-2120).
 //
-// Host code by necessity: the "first 20" of an exon position are the first filterFirst20N entries after std::sort (+ std::reverse)
-// of the reads' weighted-OK fractions (:1557-1565), and those fractions tie all the time (1.0 for every clean read), so the outcome
-// is whatever order the C++ library's sort leaves tied keys in.  Running the same std::sort on the same index sequence reproduces the
-// reference; no reformulation for the GPU can.  Everything else is flat arrays: positions are bucketed by exon position with a
-// counting pass (read order preserved inside a bucket), alleles are numbered per bucket.
+// The specification of this stage.  The "first 20" of an exon position are the first filterFirst20N entries after std::sort (+ std::reverse) of the reads'
+// weighted-OK fractions (:1557-1565), and those fractions tie all the time (1.0 for every clean read), so the outcome is whatever order the C++ library's sort
+// leaves tied keys in.  Running the same std::sort on the same index sequence reproduces the reference, and this file does exactly that.  It was once the only way:
+// since bam_fill_wide_core.h: fil_sort_wide restates libstdc++'s introsort step by step, the same order can be produced on the device as well (filter_gpu_core.h
+// maps a bucket's doubles to integer scores that compare alike; kernel_filter.hip; hlala_filter_positions_gpu, opt-in and pinned to this file byte for byte).
+// Everything else is flat arrays: positions are bucketed by exon position with a counting pass (read order preserved inside a bucket), alleles are numbered per bucket.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -35,6 +36,9 @@ extern "C" int hlala_filter_positions(const hlala_exon_positions_out* pos, const
     catch(const std::exception&) { return HLALA_E_ARG; }      // (bad_alloc on absurd sizes: nothing may cross the C boundary)
 }
 
+// PhredToPCorrect of every byte: the one table of this stage, for this file and for the device path (which uploads it: the host's exp / log decide)
+void hlala_host::filter_phred_table(double pc[256]) { for(int q = 0; q < 256; q++) pc[q] = phred_to_pcorrect((unsigned char)q); }
+
 int hlala_host::filter_positions_impl(const hlala_exon_positions_out* pos, const hlala_filter_params* prm, uint8_t* pos_use, uint8_t* read_ignored, hlala_filter_stats* stats,
                                       std::vector<std::vector<AlleleTally>>* tallies)
 {
@@ -42,7 +46,7 @@ int hlala_host::filter_positions_impl(const hlala_exon_positions_out* pos, const
     const int nReads = pos->n_reads, nPos = pos->n_pos;
     hlala_filter_stats S; memset(&S, 0, sizeof(S));
     if(nReads > 0 && (!pos->pos_off || !pos->pos_exon || !pos->pos_mapq || !pos->geno_off || !pos->geno_chars || !pos->read_weighted_ok)) return HLALA_E_ARG;
-    double pc[256]; for(int q = 0; q < 256; q++) pc[q] = phred_to_pcorrect((unsigned char)q);
+    double pc[256]; filter_phred_table(pc);
     std::vector<uint8_t> mapqOK((size_t)nPos, 0);
     int maxExon = -1;
     for(int j = 0; j < nPos; j++) {

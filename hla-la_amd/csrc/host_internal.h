@@ -20,6 +20,8 @@ struct AlleleTally {
 // hlala_filter_positions; tallies (optional) is indexed by exon position, alleles in order of first appearance
 int filter_positions_impl(const hlala_exon_positions_out* pos, const hlala_filter_params* prm, uint8_t* pos_use, uint8_t* read_ignored, hlala_filter_stats* stats,
                           std::vector<std::vector<AlleleTally>>* tallies);
+// the table of Utilities::PhredToPCorrect that filter_positions_impl tests mapQ_position with (-1 for byte 0, negative for bytes below 33)
+void filter_phred_table(double pc[256]);
 
 // CPUs this process may keep busy: the hardware threads, or fewer under a CFS quota of its control group (cgroup v2 cpu.max, v1 cpu.cfs_quota_us) -- a
 // container on a 256-thread host may own 16 of them, and threads beyond twice the quota only get each other throttled (measured: the decoder of an

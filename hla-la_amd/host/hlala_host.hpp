@@ -576,6 +576,11 @@ public:
     // through the GPU batch by batch (processBAM::acquire); what the typing needs of a batch -- includeInHLA, the per-unit alignment
     // statistics and the exon positions of every locus -- is taken while the batch is resident and appended on the host.
     // align_seconds (optional) receives the time spent in alignment proper (the reference's "Speed:" line, processBAM.cpp:1894-1898).
+    // the read / allele filters of every locus through hlala_filter_positions_gpu instead of hlala_filter_positions (same outputs; off by default).  filter_loci: of
+    // the last HLATypeInference, loci filtered on the GPU and loci that took the host function (the switch off: 0, 0)
+    void set_gpu_filter(bool on) { gpu_filter_ = on; }
+    bool gpu_filter() const { return gpu_filter_; }
+    int64_t filter_loci[2] = {0, 0};
     int64_t pair_overflow_counts[3] = {0, 0, 0};      // of the last HLATypeInference: pairs listed for the overflow class of the pairing stage, scored there, refused for want of slab
     std::vector<bestGuess> HLATypeInference(mapper::processBAM& pB, const std::string& outputDirectory, const std::vector<std::string>& loci_for_HLAtyping,
                                             double* align_seconds = nullptr, int64_t* chain_errors = nullptr)
@@ -702,7 +707,7 @@ public:
         struct JoinAll { std::vector<std::thread>& t; ~JoinAll() { for(std::thread& x : t) if(x.joinable()) x.join(); } } joinPairWriters{pairWriters};
         double lociClock[6] = {0, 0, 0, 0, 0, 0};      // filters (all loci side by side), buffers, likelihoods + all pairs + call, k-mer lists (HLALA_HOST_DEBUG=1 prints them)
         auto tL = std::chrono::steady_clock::now();
-        // the host part of every locus first, the loci side by side: the read / allele filters (hla/HLATyper.cpp:1509-1880; host code by design: libstdc++'s tie order)
+        // the host part of every locus first, the loci side by side: the read / allele filters (hla/HLATyper.cpp:1509-1880; host code that calls the library's std::sort, or with set_gpu_filter the same stage on the first context below)
         // and what the likelihood kernel reads of a position -- first genotype character, genotype length, first quality (hla/HLATyper.cpp:2080-2277)
         struct Prep { std::vector<uint8_t> use, ignored, g0, q0; std::vector<int32_t> glen; hlala_filter_stats fs; size_t nR = 0, nP = 0; std::string err; };
         std::vector<Prep> prep(acc.size());
@@ -721,7 +726,7 @@ public:
                     pos.pos_off = A.pos_off.data(); pos.pos_exon = A.pos_exon.data(); pos.pos_level = A.pos_level.data(); pos.pos_mate = A.mate.data(); pos.pos_mapq = A.pmapq.data(); pos.pos_novel_gap = A.novel.data();
                     pos.geno_off = A.geno_off.data(); pos.geno_chars = A.geno.data(); pos.qual_chars = A.qual.data(); pos.read_reverse = A.rrev.data(); pos.read_mapq = A.rmapq.data();
                     Q.use.assign(nP + 1, 0); Q.ignored.assign(nR + 1, 0);
-                    if(hlala_filter_positions(&pos, &filterParams, Q.use.data(), Q.ignored.data(), &Q.fs) != HLALA_OK) throw std::runtime_error("hlala_filter_positions failed");
+                    if(!gpu_filter_ && hlala_filter_positions(&pos, &filterParams, Q.use.data(), Q.ignored.data(), &Q.fs) != HLALA_OK) throw std::runtime_error("hlala_filter_positions failed");
                     Q.g0.assign(nP + 1, 0); Q.q0.assign(nP + 1, 0); Q.glen.assign(nP + 1, 0);
                     for(size_t j = 0; j < nP; j++) { Q.g0[j] = A.geno[A.geno_off[j]]; Q.q0[j] = A.qual[A.geno_off[j]]; Q.glen[j] = A.geno_off[j + 1] - A.geno_off[j]; }
                 } catch(const std::exception& e) { prep[li].err = e.what(); }
@@ -729,6 +734,17 @@ public:
             if(acc.size() <= 1) { for(size_t li = 0; li < acc.size(); li++) prepare(li); }
             else { ThreadJoiner th; for(size_t li = 0; li < acc.size(); li++) th.start([&, li]() { prepare(li); }); th.join(); }
             for(const Prep& Q : prep) if(!Q.err.empty()) throw std::runtime_error(Q.err);
+            // set_gpu_filter: the filters of the loci on the first context, one locus after the other (a context serves one call at a time); a locus with an exon
+            // position beyond HLALA_FILTER_GPU_MAX_BUCKET entries is answered HLALA_E_CAPACITY with nothing written and takes the host function
+            filter_loci[0] = filter_loci[1] = 0;
+            for(size_t li = 0; li < acc.size() && gpu_filter_; li++) {
+                Prep& Q = prep[li];
+                const int rc = hlala_filter_positions_gpu(c, &res[li].pos, &filterParams, Q.use.data(), Q.ignored.data(), &Q.fs, nullptr);
+                if(rc == HLALA_OK) { filter_loci[0]++; continue; }
+                if(rc != HLALA_E_CAPACITY) chk(rc, "hlala_filter_positions_gpu");
+                if(hlala_filter_positions(&res[li].pos, &filterParams, Q.use.data(), Q.ignored.data(), &Q.fs) != HLALA_OK) throw std::runtime_error("hlala_filter_positions failed");
+                filter_loci[1]++;
+            }
         }
         lociClock[0] += lap(tL);
         // (read names: the report looks up the units of the reads at the locus only -- a few thousand of the sample's millions; zero pages of the table that nobody touches stay unmapped)
@@ -837,7 +853,7 @@ public:
     bool has_locus(const std::string& locus) const { hlala_locus* L = nullptr; if(hlala_typer_locus(t_, locus.c_str(), 0, nullptr, &L) != HLALA_OK) return false; hlala_locus_free(L); return true; }
 
 private:
-    hlala_typer* t_ = nullptr; bool owns_ = true;
+    hlala_typer* t_ = nullptr; bool owns_ = true, gpu_filter_ = false;
 };
 
 }  // namespace hla

@@ -920,9 +920,11 @@ int  hlala_exon_positions(hlala_ctx* ctx, hlala_batch* b, const hlala_locus_desc
 /* Read / allele filters between the exon positions and the likelihoods (hla/HLATyper.cpp:1496-1720 filterFirst20, :1722-1862
  * high-coverage allele filter, and the use test of the likelihood loop :2102-2120).  pos_use[j] = 1 iff position j enters the
  * likelihood: mapQ_position >= min_per_position_mapq, its read is not ignored, its allele is not ignored at its exon position.
- * This step runs on the HOST: which reads make the "first 20" of a position is decided by std::sort on tied keys (:1557-1565), i.e.
- * by the C++ library's unspecified tie order; calling the same library routine on the same sequence is the only way to agree with
- * the reference, and the data is a few hundred thousand small records per locus.  No context is needed.                          */
+ * hlala_filter_positions runs on the HOST and is the specification: which reads make the "first 20" of a position is decided by
+ * std::sort on tied keys (:1557-1565), i.e. by the C++ library's unspecified tie order, and it calls the same library routine on the
+ * same sequence.  No context is needed.  That used to be the only way to agree with the reference; since the library's introsort is
+ * restated step by step for the device (csrc/bam_fill_wide_core.h: fil_sort_wide) the stage can also run there:
+ * hlala_filter_positions_gpu below, opt-in, equal to this function byte for byte and counter for counter.                       */
 typedef struct {
     int32_t filter_first20;              /* filterFirst20 (true, HLATyper.cpp:73); also the divisor of first20_prop, :1593 (sic)   */
     int32_t first20_n;                   /* filterFirst20N (20)                                                                     */
@@ -945,6 +947,23 @@ typedef struct {
 } hlala_filter_stats;
 int  hlala_filter_positions(const hlala_exon_positions_out* pos, const hlala_filter_params* prm, uint8_t* pos_use /* [n_pos] */,
                             uint8_t* read_ignored /* [n_reads] or NULL */, hlala_filter_stats* stats /* or NULL */);
+
+/* The same stage on the GPU (opt-in; csrc/kernel_filter.hip): host arrays in and out like hlala_filter_positions, every output equal to it.  Uploaded: pos_off,
+ * pos_exon, pos_mapq, pos_mate, geno_off, geno_chars, read_weighted_ok, and read_reverse with the strand filter on; nothing else of `pos` is read.  One wavefront
+ * per exon position orders the position's entries in LDS as std::sort + std::reverse order them, so an exon position holds at most HLALA_FILTER_GPU_MAX_BUCKET
+ * entries that pass the mapq test: one larger anywhere and the call returns HLALA_E_CAPACITY with a text (hlala_last_error(ctx)) that starts "not available:" and
+ * names the size, nothing written -- take hlala_filter_positions then (the per-read counters couple the positions: there is no partial split).  HLALA_E_ARG, nothing
+ * written: what hlala_filter_positions answers so to (a quality byte whose PhredToPCorrect lies outside [0, 1], a negative pos_exon, the strand filter without
+ * read_reverse), and what it cannot check: a NaN in read_weighted_ok (std::sort is undefined there), pos_off / geno_off that do not ascend or leave their arrays.
+ * counts[6] (may be NULL): exon positions with entries, of those sorted (filterFirst20 ran), entries of the largest, heap sorts the introsort entered, bytes of the
+ * caller's arrays uploaded, bytes of the caller's arrays written.  Runs on the context's reader stream; a context serves one call at a time.                    */
+#define HLALA_FILTER_GPU_MAX_BUCKET 4096
+int  hlala_filter_positions_gpu(hlala_ctx* ctx, const hlala_exon_positions_out* pos, const hlala_filter_params* prm, uint8_t* pos_use /* [n_pos] */,
+                                uint8_t* read_ignored /* [n_reads] or NULL */, hlala_filter_stats* stats /* or NULL */, int64_t counts[6] /* or NULL */);
+/* Measurement only (tools/filter_rate.py).  enable != 0: the following calls of hlala_filter_positions_gpu on this context put events between their launches.
+ * ms[6] (may be NULL): device milliseconds of the last call, zeros when it was not timed: k_flt_mapq with its read-back and k_flt_keys / k_flt_largest, the key
+ * sort and scan with their read-back, k_flt_first20, k_flt_reads, k_flt_coverage, k_flt_use.                                                                  */
+int  hlala_filter_gpu_times(hlala_ctx* ctx, int enable, double ms[6] /* or NULL */);
 
 /* The call of one locus from the all-pairs table (hla/HLATyper.cpp:2366-2541).  Pair (c1 <= c2) sits at the index
  * hlala_pair_loglik uses.  order = pair indices sorted by LL descending, Mism_avg ascending (std::sort + std::reverse, :2381-2403).
