@@ -229,6 +229,59 @@ def host_filter_model(e, params=None, tie_rule=0, raw=False):
     return _filter_call(lambda *a: fn(*a, int(tie_rule)), "hlala_host_filter_model", lambda: h.hlala_host_last_error().decode(errors="replace"), e, params, raw)
 
 
+CALL_ORDER_MAX_HEAP = 4096         # HLALA_CALL_ORDER_MAX_HEAP
+CALL_ORDER_TILE = 1024             # csrc/call_order_core.h: ORD_TILE (call_order_params() reads the library's own)
+CALL_ORDER_COUNTS = ("path", "levels", "tile_ranges", "largest_tile", "heap_sorts", "largest_heap", "bytes_up", "bytes_down")
+CALL_ORDER_HOST, CALL_ORDER_DEVICE, CALL_ORDER_REFUSED_NAN, CALL_ORDER_REFUSED_HEAP, CALL_ORDER_REFUSED_ALLOC = range(5)      # HLALA_CALL_ORDER_*: counts["path"]
+
+
+def call_order_params():
+    """hlala_host_pair_order_params: the constants of the device path for the order of the pair table -- tile size, heap cap, threads of a level's workgroup,
+    elements per side of one step of its scans"""
+    v = [C.c_int32() for _ in range(4)]
+    h = _host_lib(); h.hlala_host_pair_order_params.restype = None
+    h.hlala_host_pair_order_params(*[C.byref(x) for x in v])
+    return dict(zip(("tile", "max_heap", "block", "chunk"), (x.value for x in v)))
+
+
+def _pair_order_call(call, what, last_error, ll, ma, raw):
+    """one entry point for the order of a pair table.  raw: (rc, text, order, counts) whatever the code, `order` filled with -7 before the call (a refusal must
+    leave it so); otherwise (order, counts), a code other than 0 raised with .code set."""
+    a = [np.ascontiguousarray(x, np.float64) for x in (ll, ma)]
+    n = len(a[0]); assert len(a[1]) == n
+    order = np.full(max(1, n), -7, np.int32); cn = (C.c_int64 * 8)()
+    rc = call(n, a[0].ctypes.data_as(c_f64p), a[1].ctypes.data_as(c_f64p), order.ctypes.data_as(c_i32p), cn)
+    out = (order[:n], dict(zip(CALL_ORDER_COUNTS, (int(x) for x in cn))))
+    if raw:
+        return (int(rc), last_error() if rc != 0 else "") + out
+    if rc != 0:
+        err = HlalaError(f"{what} failed ({rc}): {last_error()}"); err.code = int(rc)
+        raise err
+    return out
+
+
+def host_pair_order_model(ll, ma, raw=False):
+    """hlala_host_pair_order_model (libhlala_host.so): the launches of Context.pair_order_gpu run serially on the host: (order, counts).  A range beyond
+    CALL_ORDER_MAX_HEAP met with no depth left is sorted all the same; counts["path"] then says CALL_ORDER_REFUSED_HEAP, what the device answers."""
+    h = _host_lib()
+    fn = h.hlala_host_pair_order_model
+    fn.argtypes = [C.c_int64, c_f64p, c_f64p, c_i32p, C.POINTER(C.c_int64)]; fn.restype = C.c_int
+    h.hlala_host_last_error.restype = C.c_char_p
+    return _pair_order_call(fn, "hlala_host_pair_order_model", lambda: h.hlala_host_last_error().decode(errors="replace"), ll, ma, raw)
+
+
+def host_pair_order_reference(ll, ma):
+    """hlala_host_pair_order_reference: std::sort + std::reverse with the comparator of hlala_call_locus -- the specification of the order, for any n"""
+    h = _host_lib()
+    fn = h.hlala_host_pair_order_reference
+    fn.argtypes = [C.c_int64, c_f64p, c_f64p, c_i32p]; fn.restype = C.c_int
+    a = [np.ascontiguousarray(x, np.float64) for x in (ll, ma)]
+    order = np.zeros(len(a[0]), np.int32)
+    if fn(len(a[0]), a[0].ctypes.data_as(c_f64p), a[1].ctypes.data_as(c_f64p), order.ctypes.data_as(c_i32p)) != 0:
+        raise HlalaError("hlala_host_pair_order_reference failed")
+    return order
+
+
 def _graph_from_handle(lib, h):
     d = GraphDesc()
     lib.hlala_graph_file_desc.argtypes = [C.c_void_p, C.POINTER(GraphDesc)]
@@ -1208,6 +1261,7 @@ EXPORTED_SYMBOLS = [
     "hlala_batch_create_from_fill", "hlala_debug_batch_inputs", "hlala_seed_batch_create_resident", "hlala_seed_batch_peek_window", "hlala_seed_batch_resident_counts",
     "hlala_bam_fill_create_wide", "hlala_bam_fill_wide_stats", "hlala_seed_batch_fill_wide_counts",
     "hlala_filter_positions_gpu", "hlala_filter_gpu_times",
+    "hlala_set_call_order_gpu", "hlala_call_order_counts", "hlala_pair_order_gpu", "hlala_call_order_times",
     "hlala_locus_cluster_kmers", "hlala_type_locus", "hlala_kmer_presence", "hlala_kmer_keep_reads", "hlala_kmer_presence_kept", "hlala_kmer_forget_reads", "hlala_unit_alignment_stats", "hlala_typer_write_summary", "hlala_typer_begin_output", "hlala_locus_write_files", "hlala_locus_write_pairs_file", "hlala_typer_end_output",
 ]
 
@@ -1401,6 +1455,32 @@ class Context:
     def kmer_forget_reads(self):
         self.lib.hlala_kmer_forget_reads.argtypes = [C.c_void_p]; self.lib.hlala_kmer_forget_reads.restype = None
         self.lib.hlala_kmer_forget_reads(self.h)
+
+    def set_call_order_gpu(self, on: bool):
+        """hlala_set_call_order_gpu: call_locus / type_locus make the order of the pair table on the device (off by default; same order, ties included)."""
+        self.lib.hlala_set_call_order_gpu.argtypes = [C.c_void_p, C.c_int]
+        self._check(self.lib.hlala_set_call_order_gpu(self.h, int(bool(on))), "hlala_set_call_order_gpu")
+
+    def call_order_counts(self):
+        """hlala_call_order_counts: the CALL_ORDER_COUNTS of the last call_locus / type_locus / pair_order_gpu on this context."""
+        cn = (C.c_int64 * 8)()
+        self.lib.hlala_call_order_counts.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        self._check(self.lib.hlala_call_order_counts(self.h, cn), "hlala_call_order_counts")
+        return dict(zip(CALL_ORDER_COUNTS, (int(x) for x in cn)))
+
+    def pair_order_gpu(self, ll, ma, raw=False):
+        """hlala_pair_order_gpu: the order alone, for any n >= 1: (order, counts).  HLALA_E_CAPACITY (-4; .code of the exception, text "not available: ...") where
+        the device path refuses: a NaN key, or a range beyond CALL_ORDER_MAX_HEAP met with no depth left."""
+        fn = self.lib.hlala_pair_order_gpu
+        fn.argtypes = [C.c_void_p, C.c_int64, c_f64p, c_f64p, c_i32p, C.POINTER(C.c_int64)]; fn.restype = C.c_int
+        return _pair_order_call(lambda *a: fn(self.h, *a), "hlala_pair_order_gpu", self.last_error, ll, ma, raw)
+
+    def call_order_times(self, enable=True):
+        """hlala_call_order_times: device milliseconds of the phases of the last device-path order on this context (zeros if it was not timed); enable: time the next"""
+        ms = (C.c_double * 4)()
+        self.lib.hlala_call_order_times.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double)]
+        self._check(self.lib.hlala_call_order_times(self.h, int(bool(enable)), ms), "hlala_call_order_times")
+        return dict(zip(("load", "levels", "tile", "emit"), (float(x) for x in ms)))
 
     def set_pair_overflow(self, scratch_bytes: int):
         """hlala_set_pair_overflow: 0 = off (the default); else pairs beyond the pairing capacities are scored out of that much device scratch."""

@@ -39,6 +39,7 @@
 #include "kernel_bamfill.hip"
 #include "kernel_bamresident.hip"
 #include "kernel_filter.hip"
+#include "kernel_callorder.hip"
 
 namespace hlala {
 size_t proj_slab_bytes_host(int stride, int maxNodesPerLevel) { return proj_slab_bytes(stride, maxNodesPerLevel); }
@@ -126,6 +127,8 @@ struct hlala_ctx {
     struct KeptReads { uint8_t* store = nullptr; long long* start = nullptr; int* length = nullptr; int n = 0; };
     std::vector<KeptReads> kept;
     bool flt_timed = false; double flt_ms[6] = {0, 0, 0, 0, 0, 0};      // hlala_filter_gpu_times: the launches of the last hlala_filter_positions_gpu, timed only on request
+    // the order of the pair table on the device (hlala_set_call_order_gpu; kernel_callorder.hip): the switch, the counters of the last order, its phases when timed
+    bool ord_gpu = false, ord_timed = false; int64_t ord_counts[HLALA_CALL_ORDER_COUNTS] = {0, 0, 0, 0, 0, 0, 0, 0}; double ord_ms[4] = {0, 0, 0, 0};
     std::string err;
 };
 
@@ -2135,6 +2138,116 @@ extern "C" int hlala_kat_phred(hlala_ctx* c, int n, const double* p_correct, uin
     return HLALA_OK;
 }
 
+// ---- the order of the pair table on the device (kernel_callorder.hip; call_order_core.h; std::sort + std::reverse on the host is the specification)
+// dLL / dMA: the tables on the device, n entries; dOrder: n indices on the device.  Everything runs on c->active.  HLALA_OK: dOrder written.  HLALA_E_CAPACITY: "not
+// available" -- Cn[OC_PATH] and `why` say which way -- and dOrder not written.  Anything else is an error of the device.  Cn: the eight counters, always filled.
+static int order_on_device(hlala_ctx* c, long long n, const double* dLL, const double* dMA, int* dOrder, int64_t* Cn, std::string* why)
+{
+    using namespace hlala_order;
+    for(int k = 0; k < OC_N; k++) Cn[k] = 0;
+    for(double& m : c->ord_ms) m = 0;
+    std::vector<void*> tmp;
+    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    auto done = [&](int r) { (void)hipStreamSynchronize(c->active); for(void* p : tmp) pool_release(c, p); for(hipEvent_t e : ev) if(e) (void)hipEventDestroy(e); return r; };
+    auto mark = [&](int k) { if(c->ord_timed && ev[k]) (void)hipEventRecord(ev[k], c->active); };
+    auto refuse = [&](int path, const std::string& text) { Cn[OC_PATH] = path; *why = "not available: " + text; return done(HLALA_E_CAPACITY); };
+    if(c->ord_timed) for(hipEvent_t& e : ev) HIP_TRY_F(c, hipEventCreate(&e), done);
+    const u32 un = (u32)n;
+    const size_t capNext = (size_t)(n / ORD_TILE + 1), capTiles = (size_t)ord_list_capacity((uint64_t)n), capHeaps = (size_t)(n / ORD_TILE + 1);
+    OrdEl* dA = nullptr; u32 *dI = nullptr, *dJ = nullptr, *dCnt = nullptr; OrdRange *dCur = nullptr, *dNext = nullptr, *dTiles = nullptr, *dHeaps = nullptr;
+    if(dev_alloc(c, tmp, (size_t)n, &dA) || dev_alloc(c, tmp, (size_t)n, &dI) || dev_alloc(c, tmp, (size_t)n, &dJ) || dev_alloc(c, tmp, capNext, &dCur) || dev_alloc(c, tmp, capNext, &dNext) ||
+       dev_alloc(c, tmp, capTiles, &dTiles) || dev_alloc(c, tmp, capHeaps, &dHeaps) || dev_alloc(c, tmp, (size_t)OD_N, &dCnt, true)) {
+        (void)hipGetLastError();
+        return refuse(HLALA_CALL_ORDER_REFUSED_ALLOC, "no device scratch for the order of " + std::to_string(n) + " pairs (" + c->err + ")");
+    }
+    u32 cnt[OD_N];
+    auto read_counters = [&]() -> int {
+        HIP_TRY(c, hipMemcpyAsync(cnt, dCnt, sizeof(cnt), hipMemcpyDeviceToHost, c->active)); HIP_TRY(c, hipStreamSynchronize(c->active));
+        Cn[OC_BYTES_DOWN] += (int64_t)sizeof(cnt);
+        if(cnt[OD_OVERFLOW]) { c->err = "the order of the pair table: a list or a stack of the device path overflowed (" + std::to_string(cnt[OD_OVERFLOW]) + ")"; return HLALA_E_DEVICE; }
+        return HLALA_OK;
+    };
+    int rc = 0;
+    mark(0);
+    { const u32 g = (un + 255u) / 256u; hipLaunchKernelGGL(k_ord_load, dim3(g < 4096u ? g : 4096u), dim3(256), 0, c->active, un, dLL, dMA, dA, dCnt); }
+    OrdLists Ls; Ls.tiles = dTiles; Ls.heaps = dHeaps; Ls.capNext = (u32)capNext; Ls.capTiles = (u32)capTiles; Ls.capHeaps = (u32)capHeaps;
+    Ls.next = dCur;
+    hipLaunchKernelGGL(k_ord_root, dim3(1), dim3(64), 0, c->active, un, Ls, dCnt);
+    if((rc = check_launch(c, "k_ord_load / k_ord_root"))) return done(rc);
+    mark(1);
+    if((rc = read_counters())) return done(rc);
+    if(cnt[OD_NAN]) return refuse(HLALA_CALL_ORDER_REFUSED_NAN, "a NaN among the keys of " + std::to_string(n) + " pairs: std::sort is undefined there");
+    for(u32 nCur = cnt[OD_NEXT]; nCur > 0; nCur = cnt[OD_NEXT]) {
+        if(nCur > capNext || Cn[OC_LEVELS] > 2 * 64) { c->err = "the order of the pair table: the list of a level is inconsistent"; return done(HLALA_E_DEVICE); }
+        Cn[OC_LEVELS]++;
+        HIP_TRY_F(c, hipMemsetAsync(dCnt + OD_NEXT, 0, sizeof(u32), c->active), done);
+        Ls.next = dNext;
+        hipLaunchKernelGGL(k_ord_level, dim3(nCur), dim3(ORD_BLOCK), 0, c->active, dA, dI, dJ, (const OrdRange*)dCur, Ls, dCnt);
+        if((rc = check_launch(c, "k_ord_level"))) return done(rc);
+        if((rc = read_counters())) return done(rc);
+        std::swap(dCur, dNext);
+    }
+    mark(2);
+    Cn[OC_TILE_RANGES] = cnt[OD_TILES]; Cn[OC_LARGEST_TILE] = cnt[OD_LARGEST_TILE];
+    if(cnt[OD_REFUSED]) {
+        Cn[OC_HEAPS] = cnt[OD_HEAPS]; Cn[OC_LARGEST_HEAP] = cnt[OD_LARGEST_HEAP];
+        return refuse(HLALA_CALL_ORDER_REFUSED_HEAP, "of " + std::to_string(n) + " pairs a range of " + std::to_string(cnt[OD_LARGEST_HEAP]) +
+                      " was met with no depth left, more than HLALA_CALL_ORDER_MAX_HEAP = " + std::to_string(ORD_MAX_HEAP));
+    }
+    if(cnt[OD_TILES] > capTiles || cnt[OD_HEAPLIST] > capHeaps) { c->err = "the order of the pair table: a list is inconsistent"; return done(HLALA_E_DEVICE); }
+    if(cnt[OD_TILES]) hipLaunchKernelGGL((k_ord_tile<ORD_TILE>), dim3(cnt[OD_TILES]), dim3(64), 0, c->active, dA, (const OrdRange*)dTiles, dCnt);
+    if(cnt[OD_HEAPLIST]) hipLaunchKernelGGL((k_ord_tile<ORD_MAX_HEAP>), dim3(cnt[OD_HEAPLIST]), dim3(64), 0, c->active, dA, (const OrdRange*)dHeaps, dCnt);
+    mark(3);
+    hipLaunchKernelGGL(k_ord_emit, dim3((un + 255u) / 256u), dim3(256), 0, c->active, un, (const OrdEl*)dA, dOrder);
+    if((rc = check_launch(c, "k_ord_tile / k_ord_emit"))) return done(rc);
+    mark(4);
+    if((rc = read_counters())) return done(rc);
+    Cn[OC_HEAPS] = cnt[OD_HEAPS]; Cn[OC_LARGEST_HEAP] = cnt[OD_LARGEST_HEAP];
+    Cn[OC_PATH] = HLALA_CALL_ORDER_DEVICE;
+    if(c->ord_timed) for(int k = 0; k < 4; k++) { float ms = 0; if(hipEventElapsedTime(&ms, ev[k], ev[k + 1]) == hipSuccess) c->ord_ms[k] = ms; }
+    return done(HLALA_OK);
+}
+extern "C" int hlala_set_call_order_gpu(hlala_ctx* c, int on)
+{
+    if(!c) return HLALA_E_ARG;
+    c->ord_gpu = on != 0;
+    return HLALA_OK;
+}
+extern "C" int hlala_call_order_counts(hlala_ctx* c, int64_t* counts)
+{
+    if(!c || !counts) return HLALA_E_ARG;
+    memcpy(counts, c->ord_counts, sizeof(c->ord_counts));
+    return HLALA_OK;
+}
+extern "C" int hlala_call_order_times(hlala_ctx* c, int enable, double* ms)
+{
+    if(!c) return HLALA_E_ARG;
+    if(ms) memcpy(ms, c->ord_ms, sizeof(c->ord_ms));
+    c->ord_timed = enable != 0;
+    return HLALA_OK;
+}
+extern "C" int hlala_pair_order_gpu(hlala_ctx* c, int64_t n, const double* ll, const double* ma, int32_t* order, int64_t* counts)
+{
+    DEV_GUARD(c);
+    ReaderScope rscope_(c, nullptr);
+    if(!c) return HLALA_E_ARG;
+    if(n < 1 || n >= ((int64_t)1 << 31) || !ll || !ma || !order) { c->err = "hlala_pair_order_gpu: n outside [1, 2^31) or a null pointer"; return HLALA_E_ARG; }
+    std::vector<void*> tmp;
+    auto done = [&](int r) { (void)hipStreamSynchronize(c->active); for(void* p : tmp) pool_release(c, p); return r; };
+    double *dLL = nullptr, *dMA = nullptr; int* dOrder = nullptr; int rc = 0;
+    if((rc = dev_upload(c, tmp, ll, (size_t)n, &dLL)) || (rc = dev_upload(c, tmp, ma, (size_t)n, &dMA)) || (rc = dev_alloc(c, tmp, (size_t)n, &dOrder))) return done(rc);
+    std::string why;
+    rc = order_on_device(c, n, dLL, dMA, dOrder, c->ord_counts, &why);
+    c->ord_counts[hlala_order::OC_BYTES_UP] = 16 * n;
+    if(rc == HLALA_OK) {
+        HIP_TRY_F(c, hipMemcpyAsync(order, dOrder, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, c->active), done);
+        HIP_TRY_F(c, hipStreamSynchronize(c->active), done);
+        c->ord_counts[hlala_order::OC_BYTES_DOWN] += 4 * n;
+    } else if(rc == HLALA_E_CAPACITY) c->err = why;
+    if(counts) memcpy(counts, c->ord_counts, sizeof(c->ord_counts));
+    return done(rc);
+}
+
 static int call_locus_impl(hlala_ctx* c, int32_t C, const double* pairLL, const double* misAvg, const double* misMin, const double* dLLin, const double* dMAin, const double* dMMin,
                           int32_t* order, double* p_normalized, double* cluster_marginal, hlala_call_out* out)
 {
@@ -2171,6 +2284,16 @@ static int call_locus_impl(hlala_ctx* c, int32_t C, const double* pairLL, const 
     // copies hlala_type_locus has queued; those have to have arrived, so that path drains the stream first and nothing overlaps.  One thread, nP log nP comparisons
     // (DESIGN.md section D-H has the measured time).  The elements carry their keys: std::sort's sequence of comparisons and moves does not depend on the element type, so
     // the permutation is the one the reference's sort of bare indices produces, at half the time of looking the keys up through the index; 24 bytes per pair of host memory.
+    // With hlala_set_call_order_gpu the same order is made on the device from the tables that are there already (kernel_callorder.hip: the library's steps level by
+    // level); where that path answers "not available" the host path below runs on the same call, and the counters say why.
+    bool ordered = false;
+    if(c->ord_gpu) {
+        std::string why;
+        rc = order_on_device(c, nP, dLL, dMA, dI1, c->ord_counts, &why);
+        if(rc == HLALA_OK) ordered = true;
+        else if(rc != HLALA_E_CAPACITY) return done(rc);
+    } else for(int64_t& k : c->ord_counts) k = 0;
+    if(!ordered) {
     if(dLLin) HIP_TRY_F(c, hipStreamSynchronize(st), done);
     struct Keyed { double ll, ma; int32_t i; };
     std::vector<Keyed> keyed; std::vector<int32_t> hOrder;
@@ -2184,6 +2307,8 @@ static int call_locus_impl(hlala_ctx* c, int32_t C, const double* pairLL, const 
     for(long long i = 0; i < nP; i++) hOrder[(size_t)i] = keyed[(size_t)i].i;
     HIP_TRY_F(c, hipMemcpyAsync(dI1, hOrder.data(), (size_t)nP * sizeof(int32_t), hipMemcpyHostToDevice, st), done);
     HIP_TRY_F(c, hipStreamSynchronize(st), done);                                                                            // (hOrder is a local)
+    c->ord_counts[hlala_order::OC_BYTES_UP] = 4 * nP;
+    }
     size_t cubBytes = 0;
     HIP_TRY_F(c, hipcub::DeviceRadixSort::SortPairs(nullptr, cubBytes, dCK, dCK2, dVal, dVal2, (int)n2, 0, 64, st), done);
     char* dCub = nullptr; if((rc = dev_alloc(c, tmp, cubBytes ? cubBytes : 1, &dCub))) return done(rc);

@@ -13,6 +13,7 @@
 #include "bam_fill_model.h"
 #include "bam_resident_model.h"
 #include "filter_gpu_model.h"
+#include "call_order_model.h"
 
 static thread_local std::string g_err;
 
@@ -203,6 +204,32 @@ int hlala_host_filter_model(const hlala_exon_positions_out* pos, const hlala_fil
     catch(const std::exception&) { why = "out of memory"; rc = HLALA_E_ARG; }
     g_err = why.empty() ? std::string() : (why.rfind("not available:", 0) == 0 ? why : "hlala_host_filter_model: " + why);
     return rc;
+}
+// The launches of the device path for the order of the pair table (kernel_callorder.hip) run serially over the same core (call_order_model.h): order[n] and
+// counts[8] (may be null) as hlala_pair_order_gpu fills them, except that a range beyond HLALA_CALL_ORDER_MAX_HEAP met with no depth left is sorted all the same and
+// counts[0] says that the device refuses it.  HLALA_E_CAPACITY ("not available:") for a NaN key, nothing written.
+int hlala_host_pair_order_model(int64_t n, const double* ll, const double* ma, int32_t* order, int64_t* counts)
+{
+    std::string why;
+    int rc = HLALA_E_ARG;
+    try { rc = hlala_order::pair_order_model(n, ll, ma, order, counts, &why); }
+    catch(const std::exception&) { why = "out of memory"; rc = HLALA_E_ARG; }
+    g_err = why.empty() ? std::string() : (why.rfind("not available:", 0) == 0 ? why : "hlala_host_pair_order_model: " + why);
+    return rc;
+}
+// The specification of that order for any n: std::sort + std::reverse with the comparator of hlala_call_locus, as the library this is built with runs them.
+int hlala_host_pair_order_reference(int64_t n, const double* ll, const double* ma, int32_t* order)
+{
+    if(const char* bad = hlala_order::ord_check_args(n, ll, ma, order)) { g_err = std::string("hlala_host_pair_order_reference: ") + bad; return HLALA_E_ARG; }
+    try { hlala_order::pair_order_reference(n, ll, ma, order); }
+    catch(const std::exception&) { g_err = "hlala_host_pair_order_reference: out of memory"; return HLALA_E_ARG; }
+    g_err.clear();
+    return HLALA_OK;
+}
+// the constants of the device path that the tests place their sizes at: tile, heap cap, threads of a level's workgroup, elements of one step of its scans
+void hlala_host_pair_order_params(int32_t* tile, int32_t* max_heap, int32_t* block, int32_t* chunk)
+{
+    *tile = (int32_t)hlala_order::ORD_TILE; *max_heap = (int32_t)hlala_order::ORD_MAX_HEAP; *block = (int32_t)hlala_order::ORD_BLOCK; *chunk = (int32_t)hlala_order::ORD_CHUNK;
 }
 // What hlala_batch_create / _unpaired does to a window before it uploads it, and so what hlala_batch_create_from_fill's kernels (kernel_bamresident.hip) must leave in
 // the batch: the five 32-bit arrays, the smallest index of every violation class, the return code and (hlala_host_last_error) its text, without a device.

@@ -10,7 +10,7 @@
 // terminate), this program prints the message to stderr and exits with a non-zero status -- HLA-LA.pl treats any non-zero status as
 // failure (:567-570).  Extra, optional arguments of this program: --devices <gpu,gpu,...> (or --device <gpu>): the batches of the sample are
 // dealt round-robin to one context per listed GPU (a GPU may be listed twice: two contexts on it), results do not depend on the list;
-// --decodeSlots <samples that decode at one time, default CPUs / 16>, --tailPool <k: GPU batches per launch of the widest DP classes>, --pairOverflow <MiB of device scratch for pairs beyond the pairing capacities, default 0: such pairs are refused>, --decodeThreads <host threads of the BAM decoder, default all>, --gpuFilter 0|1 <the typer's read / allele filters on the first listed GPU, default 0>, --gpuInflate 0|1 <BGZF blocks inflated on the first listed GPU, default 0>, --gpuInflateKernel 0|1 <which kernel inflates them there: 0 matches resolved in the output buffer, 1 the block's history in LDS; default 0; read only where blocks are inflated on the GPU>, --gpuParse 0|1 <the BAM records found, filtered and parsed there as well, default 0; 1 implies --gpuInflate 1>, --gpuGroup 0|1 <the records grouped by read name there as well, default 0; 1 implies --gpuParse 1>, --gpuSort 0|1 <the units put into read-name order there as well, default 0; 1 implies --gpuGroup 1>, --gpuFill 0|1 <the sample laid out and its windows filled there as well, default 0; 1 implies --gpuSort 1>, --gpuFillWide 0|1 <units with a mate of 17 to 4096 alignments filled there as well, default 0; 1 implies --gpuFill 1>, --gpuResident 0|1 <the windows of the batches built on the GPU from the filled sample instead of coming down and going up again, default 0; 1 implies --gpuFill 1>, --verifyCRC 0|1 <the CRC-32 of every BGZF block checked against its inflated bytes, on the GPU where they are inflated there, default 0>, --batchPairs <units per GPU batch>, --rngSeed <base of the end-cell draws>,
+// --decodeSlots <samples that decode at one time, default CPUs / 16>, --tailPool <k: GPU batches per launch of the widest DP classes>, --pairOverflow <MiB of device scratch for pairs beyond the pairing capacities, default 0: such pairs are refused>, --decodeThreads <host threads of the BAM decoder, default all>, --gpuFilter 0|1 <the typer's read / allele filters on the first listed GPU, default 0>, --gpuCallOrder 0|1 <the order of every locus's pair table made on the GPU, default 0>, --gpuInflate 0|1 <BGZF blocks inflated on the first listed GPU, default 0>, --gpuInflateKernel 0|1 <which kernel inflates them there: 0 matches resolved in the output buffer, 1 the block's history in LDS; default 0; read only where blocks are inflated on the GPU>, --gpuParse 0|1 <the BAM records found, filtered and parsed there as well, default 0; 1 implies --gpuInflate 1>, --gpuGroup 0|1 <the records grouped by read name there as well, default 0; 1 implies --gpuParse 1>, --gpuSort 0|1 <the units put into read-name order there as well, default 0; 1 implies --gpuGroup 1>, --gpuFill 0|1 <the sample laid out and its windows filled there as well, default 0; 1 implies --gpuSort 1>, --gpuFillWide 0|1 <units with a mate of 17 to 4096 alignments filled there as well, default 0; 1 implies --gpuFill 1>, --gpuResident 0|1 <the windows of the batches built on the GPU from the filled sample instead of coming down and going up again, default 0; 1 implies --gpuFill 1>, --verifyCRC 0|1 <the CRC-32 of every BGZF block checked against its inflated bytes, on the GPU where they are inflated there, default 0>, --batchPairs <units per GPU batch>, --rngSeed <base of the end-cell draws>,
 // --loci A,B,... (default: the reference's 17 loci, hla/HLATyper.cpp:42).  Several samples in one call (BASELINE config 4): comma-separated lists of
 // equal length in --sampleID, --outputDirectory, --FASTQ1, --FASTQ2 (--FASTQU); sample i runs on device i % #devices, all samples side by side.
 // Not rebuilt: the --BAM entry (the Perl driver never uses it: it extracts reads itself and passes FASTQ files), read simulation /
@@ -307,10 +307,14 @@ int action_HLA_one(const std::map<std::string, std::string>& arguments, const st
     // --gpuFilter 1: the typer's read / allele filters of every locus on the first GPU (hlala_filter_positions_gpu; same outputs as the host function, which still
     // takes a locus with an exon position beyond HLALA_FILTER_GPU_MAX_BUCKET entries)
     if(arguments.count("gpuFilter") && std::atoi(arguments.at("gpuFilter").c_str()) != 0) HLAtyper.set_gpu_filter(true);
+    // --gpuCallOrder 1: the order of every locus's pair table on the GPU (hlala_set_call_order_gpu; the same order, ties included; a table the device path refuses
+    // is ordered on the host as before)
+    if(arguments.count("gpuCallOrder") && std::atoi(arguments.at("gpuCallOrder").c_str()) != 0) HLAtyper.set_gpu_call_order(true);
     const auto tInfer = std::chrono::steady_clock::now();
     std::vector<hla::HLATyper::bestGuess> calls = HLAtyper.HLATypeInference(BAMprocessor, outputDirectory_for_HLA, loci, &alignSeconds, &chainErrors);
     const double inferSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - tInfer).count();
     if(HLAtyper.gpu_filter()) std::cout << "Typer filters: " << HLAtyper.filter_loci[0] << " loci on the GPU, " << HLAtyper.filter_loci[1] << " on the host\n" << std::flush;
+    if(HLAtyper.gpu_call_order()) std::cout << "Pair table order: " << HLAtyper.call_order_loci[0] << " loci on the GPU, " << HLAtyper.call_order_loci[1] << " on the host\n" << std::flush;
     if(BAMprocessor.gpu_resident()) std::cout << "BAM windows: " << BAMprocessor.windows_resident.load() << " built on the GPU, " << BAMprocessor.windows_host.load() << " through the host\n" << std::flush;
     if(pairOverflow > 0) std::cout << "Pairs beyond the pairing capacities: " << HLAtyper.pair_overflow_counts[1] << " scored in the overflow class, " << HLAtyper.pair_overflow_counts[2] << " refused\n" << std::flush;
     const size_t pairs = longReads.length() ? 0 : (size_t)BAMprocessor.n_units, unpaired = longReads.length() ? (size_t)BAMprocessor.n_units : 0;

@@ -581,6 +581,11 @@ public:
     void set_gpu_filter(bool on) { gpu_filter_ = on; }
     bool gpu_filter() const { return gpu_filter_; }
     int64_t filter_loci[2] = {0, 0};
+    // the order of every locus's pair table made on the GPU (hlala_set_call_order_gpu on the typing context; same order, ties included; off by default).
+    // call_order_loci: of the last HLATypeInference, loci ordered on the device and loci whose order the host made (refused there, or the switch off)
+    void set_gpu_call_order(bool on) { gpu_call_order_ = on; }
+    bool gpu_call_order() const { return gpu_call_order_; }
+    int64_t call_order_loci[2] = {0, 0};
     int64_t pair_overflow_counts[3] = {0, 0, 0};      // of the last HLATypeInference: pairs listed for the overflow class of the pairing stage, scored there, refused for want of slab
     std::vector<bestGuess> HLATypeInference(mapper::processBAM& pB, const std::string& outputDirectory, const std::vector<std::string>& loci_for_HLAtyping,
                                             double* align_seconds = nullptr, int64_t* chain_errors = nullptr)
@@ -778,6 +783,8 @@ public:
         };
         JoinAll joinWritersFirst{pairWriters};       // (declared after everything the writers touch: on the way out of an exception they are joined before any of it goes)
         struct Forget { mapper::processBAM& p; int n; ~Forget() { for(int d = 0; d < n; d++) hlala_kmer_forget_reads(p.batch_ctx(d)); } } forget{pB, nDev};
+        call_order_loci[0] = call_order_loci[1] = 0;
+        chk(hlala_set_call_order_gpu(c, gpu_call_order_ ? 1 : 0), "hlala_set_call_order_gpu");
         for(size_t li = 0; li < acc.size(); li++) {
             Acc& A = acc[li]; Res& R = res[li]; Prep& Q = prep[li];
             const size_t nR = Q.nR, nP = Q.nP;
@@ -789,6 +796,7 @@ public:
             lociClock[1] += lap(tL);
             // per-read likelihoods -> all pairs -> call, the tables left on the device in between (the per-read table of a class-I locus is 100 MB that nobody on the host reads)
             chk(hlala_type_locus(c, &xin, nullptr, nullptr, R.pairLL.data(), R.misAvg.data(), R.misMin.data(), R.order.data(), R.pNorm.data(), marginal.data(), &R.call), "hlala_type_locus");
+            { int64_t oc[HLALA_CALL_ORDER_COUNTS]; chk(hlala_call_order_counts(c, oc), "hlala_call_order_counts"); call_order_loci[oc[0] == HLALA_CALL_ORDER_DEVICE ? 0 : 1]++; }
             lociClock[2] += lap(tL);
             if(std::getenv("HLALA_HOST_DEBUG")) std::cerr << "host-debug: locus " << A.locus << ": " << C << " clusters, " << nR << " reads, " << nP << " positions\n";
             for(int a = 0; a < 2; a++) {                                              // k-mers of the two called alleles, :2652-2688 ...
@@ -853,7 +861,7 @@ public:
     bool has_locus(const std::string& locus) const { hlala_locus* L = nullptr; if(hlala_typer_locus(t_, locus.c_str(), 0, nullptr, &L) != HLALA_OK) return false; hlala_locus_free(L); return true; }
 
 private:
-    hlala_typer* t_ = nullptr; bool owns_ = true, gpu_filter_ = false;
+    hlala_typer* t_ = nullptr; bool owns_ = true, gpu_filter_ = false, gpu_call_order_ = false;
 };
 
 }  // namespace hla

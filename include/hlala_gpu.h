@@ -992,6 +992,32 @@ int  hlala_call_locus(hlala_ctx* ctx, int32_t C, const double* pairLL, const dou
 int  hlala_type_locus(hlala_ctx* ctx, const hlala_exon_in* in, double* LL /* [C*R] or NULL */, int32_t* mism /* [C*R] or NULL */,
                       double* pairLL, double* misAvg, double* misMin /* [C(C+1)/2] each */, int32_t* order, double* p_normalized, double* cluster_marginal, hlala_call_out* out);
 
+/* The order of the pair table made on the GPU (opt-in; csrc/kernel_callorder.hip, the rule in csrc/call_order_core.h): the steps of libstdc++'s std::sort run level
+ * by level -- every range of a level partitioned in closed form, ranges that fit a tile finished in LDS -- then the reversal.  `order` equals the host path's index
+ * for index, ties included.  hlala_set_call_order_gpu(ctx, on != 0): hlala_call_locus and hlala_type_locus take the device path and skip the host sort, its 24 bytes
+ * per pair of host memory and the upload of the order; off (the default): nothing changes, no launch, no allocation, no byte.  The device path answers "not
+ * available" for a NaN in either key (the sort is undefined there), for a range of more than HLALA_CALL_ORDER_MAX_HEAP pairs met with no depth left (only
+ * adversarial tables get there) and for a failed scratch allocation (32 bytes per pair): the host path then runs on the same call and the call succeeds as before.
+ * hlala_call_order_counts: of the last hlala_call_locus / hlala_type_locus / hlala_pair_order_gpu on the context: counts[0] the path taken (HLALA_CALL_ORDER_*),
+ * [1] grid levels, [2] ranges finished by the tile kernel, [3] the largest of them, [4] heap sorts entered, [5] the largest range met with no depth left, [6] bytes
+ * moved to the device for the order, [7] bytes moved from it (the host path: the uploaded order; the device path: its counters).  A call refused for a heap range
+ * ran no tile: [4] then counts the ranges beyond the cap alone, [5] is the largest of them.
+ * hlala_pair_order_gpu: the order alone for any n >= 1, host arrays in and out; counts (may be NULL) as above.  HLALA_E_CAPACITY with a text (hlala_last_error) that
+ * starts "not available:" and nothing written to `order` where the device path refuses; HLALA_E_ARG for n < 1, n >= 2^31 or a null pointer.                     */
+#define HLALA_CALL_ORDER_MAX_HEAP 4096
+#define HLALA_CALL_ORDER_COUNTS 8
+#define HLALA_CALL_ORDER_HOST 0            /* counts[0]: the host path, the switch being off                          */
+#define HLALA_CALL_ORDER_DEVICE 1          /*            the device path                                              */
+#define HLALA_CALL_ORDER_REFUSED_NAN 2     /*            the host path: the device path met a NaN key                 */
+#define HLALA_CALL_ORDER_REFUSED_HEAP 3    /*            the host path: a heap range beyond the cap (counts[5])       */
+#define HLALA_CALL_ORDER_REFUSED_ALLOC 4   /*            the host path: no device scratch                             */
+int  hlala_set_call_order_gpu(hlala_ctx* ctx, int on);
+int  hlala_call_order_counts(hlala_ctx* ctx, int64_t counts[HLALA_CALL_ORDER_COUNTS]);
+int  hlala_pair_order_gpu(hlala_ctx* ctx, int64_t n, const double* ll, const double* ma, int32_t* order /* [n] */, int64_t counts[HLALA_CALL_ORDER_COUNTS] /* or NULL */);
+/* Measurement only (tools/call_order_rate.py).  enable != 0: the following device-path orders on this context put events between their phases.  ms[4] (may be
+ * NULL): device milliseconds of the last one, zeros when it was not timed: load, grid levels (read-backs included), tile and heap kernels, emit.               */
+int  hlala_call_order_times(hlala_ctx* ctx, int enable, double ms[4] /* or NULL */);
+
 /* Reference contigs of a graph directory (host code): one contig per row of <graph_dir>/sequences.txt -- the stretch
  * [Start_1based, Stop_1based] of the BAM reference it names (column Chr, or PRG_<SequenceID>; extended_reference_genome == 0: the whole
  * sequence of mapping_PRGonly/referenceGenome.fa) with the levels of translation/<SequenceID>.txt (processBAM::initBAM
